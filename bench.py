@@ -236,6 +236,51 @@ def launch_ranks(n, argv, script=None, python=None, poll=0.2, timeout=3600.0):
     return 0 if not bad else (bad[0] if bad[0] > 0 else 1)
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20          # --dump-outputs: 60 MiB of array data, headroom for the .npy headers under the 64 MB (64e6 B) ceiling
+
+
+def output_arrays(out):
+    """{name: numpy array} of a forward's result as its caller receives it: one dict (--batch 1) or a list of per-pair dicts
+    (names pairNN_<key>).  Floating tensors become float32 (float64 stays), integer and bool tensors float64 (exact below 2**53)."""
+    items = out.items() if isinstance(out, dict) else (
+        ('pair%02d_%s' % (p, k), v) for p, d in enumerate(out) for k, v in d.items())
+    arrays = {}
+    for name, v in items:
+        if not isinstance(v, torch.Tensor):
+            continue
+        v = v.detach().cpu()
+        arrays[name] = v.numpy() if v.dtype == torch.float64 else v.to(torch.float64 if not v.is_floating_point() else torch.float32).numpy()
+    return arrays
+
+
+def sample_arrays(arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Arrays that fit `budget` bytes together.  Every array has the same share, budget / number of arrays (fixed by the arguments: pairs x
+    output keys); one within its share is kept whole, a larger one is cut to a fixed sample of its rows, seeded by its name and kept in row
+    order.  The rows an array keeps depend on its own name and shape only: an output of data-dependent length (the correspondences) that
+    grows or shrinks in another build moves no other array's sample."""
+    import zlib
+    share = budget // max(1, len(arrays))
+    kept = {}
+    for name, a in arrays.items():
+        if a.nbytes > share and a.ndim > 0 and a.shape[0] > 1:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            pick = np.random.default_rng([seed, zlib.crc32(name.encode())]).choice(a.shape[0], size=min(rows, a.shape[0]), replace=False)
+            a = a[np.sort(pick)]
+        kept[name] = a
+    return kept
+
+
+def dump_outputs(out, directory):
+    """Writes the result of one forward as DIR/<name>.npy (float32 / float64), a seeded row sample where the whole exceeds the budget."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = sample_arrays(output_arrays(out))
+    if sum(a.nbytes + 128 for a in arrays.values()) > 64 * 10 ** 6:
+        raise SystemExit('bench.py: --dump-outputs: the sampled outputs exceed 64 MB')
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a))
+    return arrays
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -283,6 +328,9 @@ def main():
                     'MAX all-reduce of the job clock then run on the GPU at world size 1 (tests/test_gpu_bench.py)')
     ap.add_argument('--fake-device', action='store_true', help='launcher self-test: gloo rendezvous, sharding, barriers and the '
                     'MAX-over-ranks clock run for real, the step is a host sleep (no GPU needed; tests/test_bench_launch.py)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed region, write what the last timed step returned '
+                    '(rank 0: the per-pair output dicts of its forward) as DIR/<name>.npy, float32 / float64, at most 64 MB in all '
+                    '(larger outputs: a fixed seeded sample of rows); the same arguments give the same inputs, so two builds compare output for output')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         seen = None if args.fake_device else visible_gpus()         # (no HIP call in the launcher: torch.cuda.device_count() is one on ROCm)
@@ -367,9 +415,15 @@ def main():
         data['features'] = feats
         return model(data) if PB == 1 else forward_pairs(model, data)
 
+    captured = {'index': None, 'out': None}          # --dump-outputs: the result of step `index` while the headline region runs
+
+    def capture(i, out):
+        if i == captured['index']:
+            captured['out'] = out
+
     def step(i):
         pts, lens = pairs[i]
-        return forward(precompute_data_stack_mode(pts, lens, b.num_stages, b.init_voxel_size, b.init_radius, cfg.neighbor_limits))
+        capture(i, forward(precompute_data_stack_mode(pts, lens, b.num_stages, b.init_voxel_size, b.init_radius, cfg.neighbor_limits)))
 
     import threading
 
@@ -414,7 +468,7 @@ def main():
                                                           cfg.neighbor_limits)
                         ev = torch.cuda.Event()
                         ev.record(side)
-                        put((data, ev))
+                        put((i, data, ev))
             except BaseException as e:       # handed to the main thread below
                 failed.append(e)
             put(None)
@@ -428,12 +482,12 @@ def main():
                 item = q.get()
                 if item is None:
                     break
-                data, ev = item
+                i, data, ev = item
                 main.wait_event(ev)
                 for key in ('points', 'neighbors', 'subsampling', 'upsampling'):
                     for t in data[key]:
                         t.record_stream(main)          # allocated on the side stream, consumed on the main stream
-                forward(data)
+                capture(i, forward(data))
                 keep = [data] + keep[:1]
         finally:
             stop.set()
@@ -506,11 +560,14 @@ def main():
     # bracket: in the headline region they cost ~2 % of the rate (region 1 against regions 2 and 3, profiles/r06_batch_inflight_sweep.txt).
     se3_ops.KERNEL_TIMINGS = {} if os.environ.get('SE3_BENCH_PY_EVENTS') == '1' else None      # (A/B switch: round 5 recorded the families' event pairs here)
     se3_lib.lib().se3_debug_kernel_timing(1)        # every RPE attention launch gets its own HIP event pair
+    if args.dump_outputs and rank == 0:
+        captured['index'] = total_steps - 1
     t0 = time.perf_counter()
     run_all(list(range(args.warmup, total_steps)))
     torch.cuda.synchronize()
     sharding.barrier(dev)
     elapsed = sharding.max_over_ranks(time.perf_counter() - t0, dev)
+    captured['index'] = None
     host_cpu_s = time.process_time() - cpu0           # CPU seconds of this rank's process (all host threads) over the timed region
     if getattr(se3_batched, '_LOCK_WAIT', None) is not None:
         print('host time waiting for chain locks since the start (s): %s; timed region %.3f s of wall x %d threads' % (
@@ -530,6 +587,11 @@ def main():
     # (grows with the number of timed steps -- 0.013 s per step at 20, 0.036 at 60 -- through the roofline's own per-launch HIP events, which stay
     #  alive until the run is over: DESIGN section 5)
     roofline = collect_roofline(se3_lib, {}, args)     # (waits for the recorded launches, releases their events, timing off)
+    if args.dump_outputs and rank == 0:
+        if captured['out'] is None:
+            raise SystemExit('bench.py: --dump-outputs needs at least one timed step (--steps)')
+        dump_outputs(captured['out'], args.dump_outputs)
+        captured['out'] = None
 
     # Dispersion: the SAME K steps between the same bracket, `--repeat-regions` more times (per-launch event timing off: the headline region
     # above carries it).  `value` stays the first region -- the contract's "exactly K steps" -- and the repeats say how far a single region moves.

@@ -1,6 +1,8 @@
-"""Run by tests/test_dropin_recipe.py in a fresh interpreter (the aliases rewrite sys.modules): executes the recipe of INTEGRATION.md
-section 1 -- the text of its first python block, read from the file -- in front of the reference's UNCHANGED experiment files and
-prints one JSON line.  TEST INFRASTRUCTURE: needs /root/reference (build container only)."""
+"""`python tests/dropin_probe.py <experiment>` (one experiment per fresh interpreter: the aliases rewrite sys.modules): executes the recipe
+of INTEGRATION.md section 1 -- the text of its first python block, read from the file -- in front of the reference's UNCHANGED experiment
+files, prints one JSON line and exits non-zero unless the reference's model is built on this package's operators.  Needs the reference
+tree (SE3ET_REFERENCE_ROOT), so it is run by hand where that exists and is not part of the test suite; tests/test_dropin_recipe.py takes
+recipe_text() from here, so the documentation and the suite cannot drift."""
 import json
 import logging
 import os
@@ -77,7 +79,7 @@ def main(experiment):
     got = tg(idx, ov)
     np.random.seed(3)
     want = np.random.choice(np.arange(int((ov > tg.overlap_threshold).sum())), tg.num_targets, replace=False)
-    print(json.dumps({
+    out = {
         'experiment': experiment,
         'foreign_modules': foreign,
         'model_class_module': type(model).__module__,
@@ -91,8 +93,25 @@ def main(experiment):
         'only_ours': sorted(set(ours) - set(theirs)),
         'mismatched': sorted(k for k in set(theirs) & set(ours) if describe(theirs)[k] != describe(ours)[k]),
         'metrics_from': sys.modules['geotransformer.modules.registration.metrics'].__file__,
-    }))
+    }
+    print(json.dumps(out))
+    return out
+
+
+def check(out):
+    """The reference's own GeoTransformer class, built on this package's operators: no foreign operator module, the mirrored modules, the
+    target generator drawing like superpoint_target.py:30-35, the same state-dict names / shapes / dtypes."""
+    assert out['foreign_modules'] == [], 'operator modules not from se3et_amd: %s' % out['foreign_modules']
+    assert out['model_class_module'] == 'model'
+    assert out['transformer_module'].startswith('se3et_amd.modules.geotransformer')
+    assert out['target_generator_module'] == 'se3et_amd.modules.geotransformer.superpoint_target'
+    assert out['node_correspondences_module'] == 'se3et_amd.modules.registration.matching'
+    assert out['point_to_node_partition_module'] == 'se3et_amd.modules.ops.pointcloud_partition'
+    assert out['target_rng_matches'], 'SuperPointTargetGenerator does not draw like superpoint_target.py:30-35'
+    assert out['only_reference'] == [] and out['only_ours'] == [] and out['mismatched'] == [], out
+    assert out['n_keys'] > 300
+    assert '/reference/' in out['metrics_from'] or 'geotransformer/modules/registration/metrics.py' in out['metrics_from']
 
 
 if __name__ == '__main__':
-    main(sys.argv[1])
+    check(main(sys.argv[1]))

@@ -22,6 +22,9 @@ Fixtures
   c3_se3eti_kitti_20k.npz  BASELINE.json configs[2] at FULL size: SE3ET-I (KITTI configuration) on the 20k+20k pair
   demo_se3ete.npz          the reference's real pair data/demo/{ref,src,gt}.npy (demo.py:44-58) through the genuine collate and SE3ET-E
   table_tiecanon.npz       tie-canonical checksums of the reference's tables for the clouds that hold exact distance ties (C3, cap pair)
+  ref_ext_tables.npz       the reference extension's grid subsampling / radius search on the seeded clouds of the tests that compare
+                           against it (C oracle, host twin, device search): lengths, shapes and checksums
+  vgtk_constants.npz       the EPN toolkit's octahedral tables and rotation labels on 20 seeded rotations
 """
 import os
 import sys
@@ -511,6 +514,74 @@ def gen_vgtk():
                         intra_out=_np(intra_out), intra_cotangent=_np(intra_cot), intra_feats_grad=_np(intra_feats.grad))
 
 
+def float_checksum(t):
+    """index_checksum of the float32 bit patterns: equal only for bit-identical arrays in the same order."""
+    return _index_checksum(np.ascontiguousarray(np.asarray(t, np.float32)).view(np.uint32))
+
+
+# (the seeded inputs of the tests that compare against the reference's OWN compiled extension -- oracle/_ref/libref_ext.so, built by
+#  oracle/ref_ext/Makefile -- regenerated there from these parameters)
+ORACLE_CASES = [(5000, 4000, 1.0, 0.05), (12000, 9000, 2.0, 0.05), (3000, 100, 0.5, 0.1), (30, 2, 0.3, 0.1)]
+HOST_LATTICE_CASES = [(3000, 0.02, 0.0625), (1200, 0.05, 0.11), (40, 0.05, 0.3), (11, 0.01, 0.05), (5, 0.1, 0.25)]
+DEVICE_LATTICE_CASES = [(6000, 5000, 0.001, 0.0625, 38), (2500, 2000, 0.01, 0.125, 36)]
+
+
+def gen_ref_ext():
+    """The reference extension's grid subsampling and radius search on the seeded clouds of tests/test_oracle_vs_reference.py,
+    tests/test_host_ext.py (lattice) and tests/test_gpu_radius_ties.py (the reference binary): lengths, shapes and checksums -- float bit
+    patterns, order-sensitive index checksums, and the tie-canonical form (helpers.tie_canonical) where a test allows tied entries to move."""
+    from test_radius_ties_cpu import lattice_cloud
+    ext = ref_shims._RefExt(ref_shims.REF_EXT_SO)
+    res = {}
+    for n1, n2, scale, voxel in ORACLE_CASES:
+        key = 'oracle/%d_%d_%g_%g/' % (n1, n2, scale, voxel)
+        g = np.random.default_rng(0)
+        pts = torch.from_numpy((g.uniform(0, 1, (n1 + n2, 3)) * scale).astype(np.float32))
+        nrm = torch.from_numpy(g.normal(size=(n1 + n2, 3)).astype(np.float32))
+        sp, sl, sn = ext.grid_subsampling(pts, torch.tensor([n1, n2]), nrm, voxel)
+        t = ext.radius_neighbors(sp, sp, sl, sl, voxel * 2.5)[:, :38]
+        res.update({key + 'lengths': sl.numpy(), key + 'points': float_checksum(sp), key + 'normals': float_checksum(sn),
+                    key + 'neighbors_shape': np.array(t.shape), key + 'neighbors_tiecanon': _index_checksum(tie_canonical(sp, sp, t)[0])})
+    gen = torch.Generator().manual_seed(9)                  # drawn in the order of test_host_radius_neighbors_equal_the_reference_build_on_a_lattice
+    for n, cell, radius in HOST_LATTICE_CASES:
+        key = 'host_lattice/%d_%g_%g/' % (n, cell, radius)
+        pts = (torch.randint(0, 24, (2 * n, 3), generator=gen).float() * cell).contiguous()
+        lens = torch.tensor([n, n])
+        t = ext.radius_neighbors(pts, pts, lens, lens, radius)
+        res.update({key + 'shape': np.array(t.shape), key + 'checksum': _index_checksum(t.numpy())})
+    for n1, n2, step, radius, limit in DEVICE_LATTICE_CASES:
+        key = 'device_lattice/%d_%d_%g_%g_%d/' % (n1, n2, step, radius, limit)
+        s = torch.from_numpy(np.concatenate([lattice_cloud(n1, (0.6, 0.5, 0.3), step, 41), lattice_cloud(n2, (0.5, 0.6, 0.3), step, 42)], 0))
+        sl = torch.tensor([n1, n2])
+        t = ext.radius_neighbors(s, s, sl, sl, radius)[:, :limit]
+        res.update({key + 'shape': np.array(t.shape), key + 'checksum': _index_checksum(t.numpy())})
+    np.savez_compressed(os.path.join(HERE, 'ref_ext_tables.npz'), **res)
+
+
+def gen_toolkit():
+    """The EPN toolkit's construction-time tables (vgtk.so3conv.get_octahedron_vertices, vgtk.functional.get_relativeV_index) and
+    label_relative_rotation_simple on 20 seeded rotations: what tests/test_dropin_recipe.py holds se3et_amd.vgtk to.  The shims'
+    trimesh is a stand-in, so the edge centres (ecs) only hold as a set."""
+    ref_shims.install()
+    import vgtk.functional as fr
+    import vgtk.so3conv as sptk
+    a = sptk.get_octahedron_vertices()
+    ta = fr.get_relativeV_index(a[2], a[0])
+    g = np.random.default_rng(0)
+    anchors = torch.tensor(a[2], dtype=torch.float32)
+    rots, labels = [], []
+    for _ in range(20):
+        q, _r = np.linalg.qr(g.normal(size=(3, 3)))
+        q = torch.tensor(q * np.sign(np.linalg.det(q)), dtype=torch.float32)
+        r, lab = fr.label_relative_rotation_simple(anchors, q)
+        rots.append(_np(torch.as_tensor(r)))
+        labels.append(int(lab))
+    res = {name: np.asarray(a[i]) for i, name in enumerate(('vs', 'v_adjs', 'vRs', 'ecs', 'face_normals'))}
+    res.update(relative_index0=np.asarray(ta[0]), relative_index1=np.asarray(ta[1]), label_rotations=np.stack(rots),
+               labels=np.array(labels))
+    np.savez_compressed(os.path.join(HERE, 'vgtk_constants.npz'), **res)
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'precompute', 'micro', 'synthw']
     if 'tables' in which:
@@ -531,6 +602,10 @@ if __name__ == '__main__':
         gen_synthw('se3eti.kitti', 'synthw_se3eti_kitti.npz', pair='c3_4k')
     if 'vgtk' in which:
         gen_vgtk()
+    if 'ref_ext' in which:
+        gen_ref_ext()
+    if 'toolkit' in which:
+        gen_toolkit()
     if 'train' in which:
         gen_train('se3ete.3dmatch', 'train_micro_se3ete.npz')
         gen_train('se3eti.3dmatch', 'train_micro_se3eti.npz')

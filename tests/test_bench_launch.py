@@ -122,3 +122,37 @@ def test_train_bench_launches_its_own_ranks_and_keeps_the_replicas_in_sync():
     assert line['n_gpus'] == 2 and line['ranks_seen'] == 2 and line['steps'] == 3
     assert line['replicas_in_sync'] is True
     assert abs(line['lr'] - 2e-2) < 1e-12                      # the reference scales the learning rate by the world size (base_trainer.py:191-196)
+
+
+def test_dump_outputs_fits_the_budget_and_keeps_the_same_sample(tmp_path):
+    """--dump-outputs: every tensor of the per-pair output dicts as <name>.npy in float32 / float64 (integers and masks exact), the whole
+    within 64 MB by a seeded row sample of the large arrays (the same rows in every run), small arrays whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = [dict(feats_f=torch.randn(40000, 256, generator=g), matching_scores=torch.randn(256, 65, 65, generator=g),
+                 ref_corr_points=torch.randn(60000, 3, generator=g),
+                 ref_node_corr_indices=torch.arange(256) * (2 ** 40), ref_node_corr_knn_masks=torch.rand(256, 64, generator=g) > 0.5,
+                 estimated_transform=torch.eye(4, dtype=torch.float64), note='not an array') for _ in range(3)]
+    written = bench.dump_outputs(outs, str(tmp_path / 'a'))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(n + '.npy' for n in written) and len(files) == 18
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 * 10 ** 6
+    loaded = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in loaded.values())
+    assert np.array_equal(loaded['pair01_estimated_transform'], np.eye(4)) and loaded['pair01_estimated_transform'].dtype == np.float64
+    assert np.array_equal(loaded['pair02_ref_node_corr_indices'], (np.arange(256) * 2.0 ** 40))
+    assert np.array_equal(loaded['pair00_ref_node_corr_knn_masks'], outs[0]['ref_node_corr_knn_masks'].numpy())
+    f = loaded['pair00_feats_f']
+    assert 0 < f.shape[0] < 40000 and f.shape[1] == 256
+    rows = [int(np.nonzero((outs[0]['feats_f'].numpy() == r).all(1))[0][0]) for r in f[:5]]
+    assert rows == sorted(rows)
+    again = bench.dump_outputs(outs, str(tmp_path / 'b'))
+    assert all(np.array_equal(written[k], again[k]) for k in written)
+    # an output of data-dependent length (the correspondences of another build) moves no other array's sample
+    outs[1]['ref_corr_points'] = outs[1]['ref_corr_points'][:20000]
+    other = bench.dump_outputs(outs, str(tmp_path / 'c'))
+    assert other['pair01_ref_corr_points'].shape[0] < written['pair01_ref_corr_points'].shape[0]
+    assert all(np.array_equal(written[k], other[k]) for k in written if k != 'pair01_ref_corr_points')

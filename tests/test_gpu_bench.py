@@ -70,3 +70,24 @@ def test_bench_at_the_drivers_step_counts():
     # (round 6: 1.7-1.9 busy cores per rank with the flag against 3.8-4.2 without; round 5 read 0.8 -- the difference sits in the package, not in
     #  bench.py or the tie pass, and was not found: DESIGN section 5)
     assert line['host_cpu_s_per_step'] < 0.8 * 3 * line['ms_per_step'] * 1e-3
+
+
+def test_bench_dumps_the_last_timed_step_on_the_prefetch_path(tmp_path):
+    """`--dump-outputs` end to end with ONE batch in flight and the pyramid prefetch (run_prefetched: a second host thread builds the next
+    pyramid): the per-pair output dicts of the last timed step as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / 'dump'
+    line = _bench(['--gpus', '1', '--inflight', '1', '--batch', '2', '--steps', '2', '--warmup', '1', '--dump-outputs', str(out)] + LIGHT)
+    assert line['steps'] == 2 and line['config']['batches_in_flight_per_gpu'] == 1 and line['config']['pyramid_prefetch']
+    files = sorted(os.listdir(out))
+    for p in range(2):
+        for key in ('ref_points', 'feats_f', 'ref_feats_c', 'matching_scores', 'ref_corr_points', 'corr_scores', 'estimated_transform'):
+            assert 'pair%02d_%s.npy' % (p, key) in files, (p, key)
+    assert all(f.startswith(('pair00_', 'pair01_')) and f.endswith('.npy') for f in files)
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    for p in range(2):
+        T = arrays['pair%02d_estimated_transform' % p]
+        assert T.shape == (4, 4) and np.isfinite(T).all() and np.allclose(T[3], [0, 0, 0, 1]) and np.allclose(T[:3, :3] @ T[:3, :3].T, np.eye(3), atol=1e-4)
+        assert arrays['pair%02d_ref_points' % p].shape == (5000, 3)
