@@ -654,6 +654,32 @@ int se3_count_inliers_ranges(const float* src_points, const float* ref_points, i
                              int num_transforms, const int64_t* range_begin, const int64_t* range_end, float radius,
                              int32_t* votes, void* stream);
 
+/* ---- Evaluation: ground-truth patch overlaps and the Evaluator's metrics for stacked pairs -----------------------------------
+ * se3_gt_node_overlaps_stack replaces get_node_correspondences (geotransformer/modules/registration/matching.py:230-315) for
+ * num_clouds / 2 pairs stacked ref0, src0, ref1, src1, ... (even num_clouds <= SE3_MAX_BATCH): points_f / points_c the stacked fine
+ * points / nodes, node_lengths (HOST, num_clouds) the nodes per cloud; knn (total nodes, K) int64 GLOBAL fine-point indices, knn_masks
+ * (total nodes, K) and node_masks (total nodes) uint8 as se3_point_to_node_partition_stack returns them; K in {64, 128}; transforms
+ * (pairs, 4, 4) DEVICE ground truth (src -> ref).  pos_radius_sq = pos_radius^2 rounded to float.  Outputs, pair p's block starting
+ * at D_p = sum_{q<p} N_q M_q (N / M = its ref / src node counts): overlaps (D_B) float32, row-major (N_p, M_p) blocks, 0 where the
+ * patches do not overlap; corr_indices (D_B, 2) int64 pair-local (ref, src) node indices and corr_overlaps (D_B) of the pairs with
+ * overlap > 0 in row-major order, pair_counts[p] (DEVICE int64) of them valid from D_p on.  workspace: se3_gt_node_overlaps_workspace_bytes(
+ * total nodes) bytes.  Three launches, no host synchronisation. */
+size_t se3_gt_node_overlaps_workspace_bytes(int64_t total_nodes);
+int se3_gt_node_overlaps_stack(const float* points_f, const float* points_c, const int64_t* node_lengths, int num_clouds,
+                               const int64_t* knn, const uint8_t* knn_masks, const uint8_t* node_masks, int K, const float* transforms,
+                               float pos_radius, float pos_radius_sq, void* workspace, float* overlaps, int64_t* corr_indices,
+                               float* corr_overlaps, int64_t* pair_counts, void* stream);
+/* se3_registration_metrics_stack: the Evaluator of experiments/se3ete.3dmatch/loss.py:198-262 (kitti == 0) or
+ * experiments/se3eti.kitti/loss.py:94-151 (kitti != 0) for num_pairs pairs in one launch.  pair_table (DEVICE, num_pairs x 16 int64),
+ * one row per pair: [0] overlaps block (float*, (N, M) as above), [1] N, [2] M, [3] / [4] predicted ref / src node indices (int64*),
+ * [5] their count, [6] / [7] ref / src correspondence points (float* (n, 3)), [8] their count n, [9] estimated transform (float* 4x4),
+ * [10] ground-truth transform (float* 4x4), [11] stage-0 src points (float* (m, 3), 3DMatch only), [12] m; [13..15] unused.
+ * rows (num_pairs, 6) float32: PIR, IR, RRE (degrees), RTE, RMSE (NaN with kitti), RR.  Empty sets give NaN as the mean of an empty
+ * tensor does; a predicted node index outside the pair's block makes PIR NaN.  Counts are integers and the RMSE sum has a fixed order:
+ * a pair's row does not depend on the others. */
+int se3_registration_metrics_stack(const int64_t* pair_table, int num_pairs, float acceptance_overlap, float acceptance_radius,
+                                   float rmse_threshold, float rre_threshold, float rte_threshold, int kitti, float* rows, void* stream);
+
 /* Mutual top-k correspondence mask (local_global_registration.py:104-131): mask[b, i, j] = 1 iff scores[b, i, j] is among the k
  * largest of row i AND of column j of patch pair b (ties by index), exceeds `threshold`, and row_masks[b, i] & col_masks[b, j].
  * scores (batch, rows, cols) float32, masks uint8; rows * cols <= 16384. */

@@ -356,9 +356,11 @@ def registration_pairs(lgr, patches, stacked=None):
 
 
 @torch.no_grad()
-def forward_pairs(model, data_dict, with_registration=True):
+def forward_pairs(model, data_dict, with_registration=True, ground_truth=False):
     """Inference forward of B pairs stacked as ref0, src0, ref1, src1, ... (data_dict from se3et_amd.data with 2 B lengths).
-    Returns a list of B output dicts with the keys of SE3ET.forward."""
+    Returns a list of B output dicts with the keys of SE3ET.forward.  ground_truth=True (needs data_dict['transform'] (B, 4, 4)): every
+    dict also carries gt_node_corr_indices / gt_node_corr_overlaps (get_node_correspondences, csrc/evaluation.hip) and the dense
+    (N_p, M_p) overlap block gt_node_corr_overlap_map that se3et_amd.evaluation.evaluate_pairs reads."""
     lengths = data_dict['lengths']
     nc = len(lengths[0])
     if nc % 2 or nc < 2:
@@ -379,6 +381,13 @@ def forward_pairs(model, data_dict, with_registration=True):
     # the points only, so it goes first: the number of non-empty nodes per cloud travels to the host behind the backbone and the transformer
     # (read after them, when it has long arrived -- no wait, as in SE3ET._forward)
     _, node_masks, knn, knn_masks = _ops.point_to_node_partition_stack(points_f, points_c, len_f, len_c, K)
+    gt = None
+    if ground_truth:
+        transforms = data_dict['transform']
+        if transforms.dim() != 3 or transforms.shape[0] != B:
+            raise RuntimeError('forward_pairs(ground_truth=True): data_dict["transform"] must be (%d, 4, 4)' % B)
+        gt = _ops.gt_node_overlaps_stack(points_f, points_c, len_c, knn, knn_masks, node_masks, transforms.to(dev, torch.float32),
+                                         model.cfg.model.ground_truth_matching_radius)
     csum = torch.cumsum(node_masks, 0)
     ends = _ops.to_device([o - 1 for o in oc[1:]], torch.int64, dev)
     upto = csum[ends]
@@ -481,4 +490,7 @@ def forward_pairs(model, data_dict, with_registration=True):
         stacked = (ref_cp, src_cp, ref_cm, src_cm, scores[:, :-1, :-1])
         for out, (rc, scp, cs, T) in zip(outs, registration_pairs(model.fine_matching, per_pair, stacked)):
             out.update(ref_corr_points=rc, src_corr_points=scp, corr_scores=cs, estimated_transform=T)
+    if gt is not None:
+        for p, (out, (gi, go)) in enumerate(zip(outs, gt.lists())):
+            out.update(gt_node_corr_indices=gi, gt_node_corr_overlaps=go, gt_node_corr_overlap_map=gt.block(p))
     return outs

@@ -66,6 +66,11 @@ def make_cfg(variant='se3ete', attention_dtype='float32'):
     cfg.loss = ns(weight_coarse_loss=1.0, weight_fine_loss=1.0)
     cfg.optim = ns(lr=1e-4, lr_decay=0.95, lr_decay_steps=4 if kitti else 1, weight_decay=1e-6, max_epoch=160 if kitti else 40, grad_acc_steps=1)
     cfg.neighbor_limits = [38, 36, 36, 38, 38][:stages]
+    # evaluation (experiments/se3ete.3dmatch/config.py:54-59, experiments/se3eti.kitti/config.py:58-62; se3et_amd.evaluation)
+    cfg.eval = ns(acceptance_overlap=0.0, acceptance_radius=1.0 if kitti else 0.1, inlier_ratio_threshold=0.05,
+                  rre_threshold=5.0 if kitti else 15.0, rte_threshold=2.0 if kitti else 0.3)
+    if not kitti:
+        cfg.eval.rmse_threshold = 0.2
     return cfg
 
 

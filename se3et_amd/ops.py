@@ -2103,3 +2103,101 @@ def count_inliers(src, ref, transforms, radius, range_begin=None, range_end=None
                                          range_end.data_ptr() if range_end is not None else None, float(radius),
                                          votes.data_ptr(), _stream()), 'se3_count_inliers_ranges')
     return votes
+
+
+# ---- evaluation (csrc/evaluation.hip) ---------------------------------------------------------------------------------------------------
+class GroundTruthOverlaps:
+    """Result of gt_node_overlaps_stack for B pairs, all on the device: `dense` packs pair p's (N_p, M_p) overlap matrix from entry
+    dense_offsets[p] on; `indices` (capacity, 2) / `overlaps` (capacity,) hold pair p's compacted list from the same offset, `counts` (B,)
+    its length.  `lists()` reads the counts (one host synchronisation) and returns per pair ((C_p, 2) int64, (C_p,) float32) views."""
+
+    def __init__(self, dense, dense_offsets, shapes, indices, overlaps, counts):
+        self.dense, self.dense_offsets, self.shapes = dense, dense_offsets, shapes
+        self.indices, self.overlaps, self.counts = indices, overlaps, counts
+
+    def block(self, p):
+        n, m = self.shapes[p]
+        return self.dense[self.dense_offsets[p]:self.dense_offsets[p] + n * m].view(n, m)
+
+    def lists(self):
+        out = []
+        for p, c in enumerate(self.counts.tolist()):
+            a = self.dense_offsets[p]
+            out.append((self.indices[a:a + c], self.overlaps[a:a + c]))
+        return out
+
+
+def gt_node_overlaps_stack(points_f, points_c, node_lengths, knn, knn_masks, node_masks, transforms, pos_radius):
+    """HIP (csrc/evaluation.hip): get_node_correspondences for the B = len(node_lengths) / 2 pairs of a stacked batch (clouds ref0, src0,
+    ref1, ...) in three launches and no host synchronisation.  knn / knn_masks / node_masks as point_to_node_partition_stack returns them
+    (GLOBAL fine-point indices); transforms (B, 4, 4) ground truth.  Returns a GroundTruthOverlaps."""
+    points_f = _req(points_f.contiguous(), torch.float32, 'points_f', 2)
+    points_c = _req(points_c.contiguous(), torch.float32, 'points_c', 2)
+    knn = _req(knn.contiguous(), torch.int64, 'knn', 2)
+    knn_masks = _req(knn_masks.contiguous(), torch.bool, 'knn_masks', 2)
+    node_masks = _req(node_masks.contiguous(), torch.bool, 'node_masks', 1)
+    transforms = _req(transforms.contiguous(), torch.float32, 'transforms', 3)
+    lengths = [int(n) for n in (node_lengths.tolist() if torch.is_tensor(node_lengths) else node_lengths)]
+    nc, M, K = len(lengths), points_c.shape[0], knn.shape[1]
+    B = nc // 2
+    if nc % 2 or nc < 2 or sum(lengths) != M or knn.shape[0] != M or knn_masks.shape != knn.shape or node_masks.shape[0] != M:
+        raise RuntimeError('gt_node_overlaps_stack: an even number of clouds whose node lengths match the partition')
+    if transforms.shape[0] != B or tuple(transforms.shape[1:]) != (4, 4):
+        raise RuntimeError('gt_node_overlaps_stack: transforms must be (%d, 4, 4)' % B)
+    shapes = [(lengths[2 * p], lengths[2 * p + 1]) for p in range(B)]
+    offs = [0]
+    for n, m in shapes:
+        offs.append(offs[-1] + n * m)
+    dev = points_c.device
+    dense = torch.empty((offs[-1],), dtype=torch.float32, device=dev)
+    indices = torch.empty((offs[-1], 2), dtype=torch.int64, device=dev)
+    overlaps = torch.empty((offs[-1],), dtype=torch.float32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int64, device=dev)
+    ws = torch.empty((max(1, lib().se3_gt_node_overlaps_workspace_bytes(M)),), dtype=torch.uint8, device=dev)
+    pr = float(pos_radius)
+    check(lib().se3_gt_node_overlaps_stack(points_f.data_ptr(), points_c.data_ptr(), _i64_array(lengths), nc, knn.data_ptr(),
+                                           knn_masks.data_ptr(), node_masks.data_ptr(), K, transforms.data_ptr(), pr, pr ** 2,
+                                           ws.data_ptr(), dense.data_ptr(), indices.data_ptr(), overlaps.data_ptr(), counts.data_ptr(),
+                                           _stream()), 'se3_gt_node_overlaps_stack')
+    return GroundTruthOverlaps(dense, offs[:-1], shapes, indices, overlaps, counts)
+
+
+def registration_metrics_stack(pairs, gt_transforms, acceptance_overlap, acceptance_radius, rmse_threshold, rre_threshold, rte_threshold,
+                               kitti):
+    """HIP (csrc/evaluation.hip): the Evaluator's PIR, IR, RRE, RTE, RMSE, RR for B pairs in one launch.  pairs[p] = (overlaps (N, M),
+    ref_node_corr_indices, src_node_corr_indices, ref_corr_points, src_corr_points, estimated_transform (4, 4), src_points or None);
+    gt_transforms (B, 4, 4).  Returns (B, 6) float32 in that column order (RMSE NaN with kitti)."""
+    B = len(pairs)
+    gt_transforms = _req(gt_transforms.contiguous(), torch.float32, 'gt_transforms', 3)
+    if gt_transforms.shape[0] != B or tuple(gt_transforms.shape[1:]) != (4, 4):
+        raise RuntimeError('registration_metrics_stack: gt_transforms must be (%d, 4, 4)' % B)
+    dev = gt_transforms.device
+    table, keep = [], []        # (keep: the contiguous operands stay referenced until the launch is queued)
+    for p, (ov, ri, si, rc, sc, est, sp) in enumerate(pairs):
+        ov = _req(ov.contiguous(), torch.float32, 'overlaps', 2)
+        ri = _req(ri.contiguous(), torch.int64, 'ref_node_corr_indices', 1)
+        si = _req(si.contiguous(), torch.int64, 'src_node_corr_indices', 1)
+        rc = _req(rc.contiguous(), torch.float32, 'ref_corr_points', 2)
+        sc = _req(sc.contiguous(), torch.float32, 'src_corr_points', 2)
+        est = _req(est.contiguous(), torch.float32, 'estimated_transform', 2)
+        if ri.shape != si.shape or rc.shape != sc.shape or rc.shape[1] != 3 or tuple(est.shape) != (4, 4):
+            raise RuntimeError('registration_metrics_stack: pair %d has mismatched shapes' % p)
+        if not kitti:
+            sp = _req(sp.contiguous(), torch.float32, 'src_points', 2)
+            if sp.shape[1] != 3:
+                raise RuntimeError('registration_metrics_stack: src_points must be (n, 3)')
+        for t in (ov, ri, si, rc, sc, est) + ((sp,) if not kitti else ()):
+            if t.device != dev:
+                raise RuntimeError('registration_metrics_stack: all tensors on %s' % dev)
+        keep.append((ov, ri, si, rc, sc, est, sp))
+        table += [ov.data_ptr(), ov.shape[0], ov.shape[1], ri.data_ptr(), si.data_ptr(), ri.shape[0], rc.data_ptr(), sc.data_ptr(),
+                  rc.shape[0], est.data_ptr(), gt_transforms[p].data_ptr(), 0 if kitti else sp.data_ptr(), 0 if kitti else sp.shape[0],
+                  0, 0, 0]
+    rows = torch.empty((B, 6), dtype=torch.float32, device=dev)
+    if B == 0:
+        return rows
+    tab = to_device(table, torch.int64, dev)
+    check(lib().se3_registration_metrics_stack(tab.data_ptr(), B, float(acceptance_overlap), float(acceptance_radius), float(rmse_threshold),
+                                               float(rre_threshold), float(rte_threshold), 1 if kitti else 0, rows.data_ptr(), _stream()),
+          'se3_registration_metrics_stack')
+    return rows
