@@ -680,6 +680,29 @@ int se3_gt_node_overlaps_stack(const float* points_f, const float* points_c, con
 int se3_registration_metrics_stack(const int64_t* pair_table, int num_pairs, float acceptance_overlap, float acceptance_radius,
                                    float rmse_threshold, float rre_threshold, float rte_threshold, int kitti, float* rows, void* stream);
 
+/* ---- RANSAC registration from correspondences for stacked pairs (csrc/ransac.hip) ----------------------------------------------------
+ * Replaces registration_with_ransac_from_correspondences (geotransformer/utils/open3d.py:169-198, Open3D's CPU RANSAC) for num_pairs
+ * pairs: src_points / ref_points (total, 3) float32, pair p owns rows [offsets[p], offsets[p+1]) (int64, DEVICE, num_pairs + 1 entries,
+ * n_p rows).  Each pair scores H = num_iterations hypotheses of ransac_n (3..16) correspondences drawn uniformly with replacement:
+ *   idx_j(h) = ((splitmix64(splitmix64(seed) + h * ransac_n + j) >> 32) * n_p) >> 32        (uint64 wrap-around; splitmix64 with the
+ *   standard constants 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB -- csrc/ransac.hip), independent of the pair's position,
+ * or taken from hypothesis_indices (DEVICE (num_pairs, H, ransac_n) int32, pair-local; an index outside [0, n_p) voids the hypothesis).
+ * A hypothesis is the unweighted float64 Kabsch fit of its sample (src -> ref) rounded to float32; correspondence i is its inlier iff
+ * |T s_i - r_i|^2 < distance_threshold^2 in float32.  The winner has the most inliers, then the smallest inlier error sum, then the lowest
+ * h, and needs at least one inlier: otherwise -- and when ransac_n < 3, n_p < ransac_n or distance_threshold <= 0 -- the pair's result is
+ * the identity with fitness 0, RMSE 0 and best_hypothesis -1.  Outputs: transforms (num_pairs, 4, 4) the winner's own fit (no refit),
+ * fitness (num_pairs) = inliers / n_p, inlier_rmse (num_pairs) = sqrt(error sum / inliers), best_hypothesis (num_pairs) int32; counts /
+ * err_sums (num_pairs, H) int32 / float32 per hypothesis, or both NULL.  Non-finite correspondences are never inliers and a non-finite
+ * sample has 0 inliers.  Each error sum runs serially in correspondence order: a pair's result does not depend on its batch or the run.
+ * ransac_n > 16: SE3_ERR_UNSUPPORTED.  workspace: se3_ransac_correspondences_workspace_bytes(num_pairs, num_iterations) bytes, 16-byte
+ * aligned.  Three launches (fit, score, select), no host synchronisation. */
+size_t se3_ransac_correspondences_workspace_bytes(int num_pairs, int num_iterations);
+int se3_ransac_correspondences_stack(const float* src_points, const float* ref_points, const int64_t* offsets, int num_pairs,
+                                     float distance_threshold, int ransac_n, int num_iterations, uint64_t seed,
+                                     const int32_t* hypothesis_indices, void* workspace, size_t workspace_bytes, float* transforms,
+                                     float* fitness, float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts, float* err_sums,
+                                     void* stream);
+
 /* Mutual top-k correspondence mask (local_global_registration.py:104-131): mask[b, i, j] = 1 iff scores[b, i, j] is among the k
  * largest of row i AND of column j of patch pair b (ties by index), exceeds `threshold`, and row_masks[b, i] & col_masks[b, j].
  * scores (batch, rows, cols) float32, masks uint8; rows * cols <= 16384. */

@@ -132,6 +132,9 @@ SIGNATURES = {
     'se3_gt_node_overlaps_workspace_bytes': (_sz, [_i64]),
     'se3_gt_node_overlaps_stack': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'se3_registration_metrics_stack': (_i32, [_vp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    'se3_ransac_correspondences_workspace_bytes': (_sz, [_i32, _i32]),
+    'se3_ransac_correspondences_stack': (_i32, [_vp, _vp, _vp, _i32, _f32, _i32, _i32, ctypes.c_uint64, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]),
     'se3_mutual_topk_mask': (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     'se3_count_inliers': (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp]),
     'se3_count_inliers_ranges': (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),

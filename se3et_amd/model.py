@@ -71,6 +71,8 @@ def make_cfg(variant='se3ete', attention_dtype='float32'):
                   rre_threshold=5.0 if kitti else 15.0, rte_threshold=2.0 if kitti else 0.3)
     if not kitti:
         cfg.eval.rmse_threshold = 0.2
+    # eval.py --method ransac (experiments/se3ete.3dmatch/config.py:62-65, experiments/se3eti.kitti/config.py:65-68; se3et_amd.ransac)
+    cfg.ransac = ns(distance_threshold=0.3 if kitti else 0.05, num_points=4 if kitti else 3, num_iterations=50000)
     return cfg
 
 

@@ -2105,6 +2105,45 @@ def count_inliers(src, ref, transforms, radius, range_begin=None, range_end=None
     return votes
 
 
+def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed=0, hypothesis_indices=None, per_hypothesis=False):
+    """HIP (csrc/ransac.hip): RANSAC from correspondences for the P = len(offsets) - 1 pairs of stacked src / ref (total, 3), pair p on
+    rows [offsets[p], offsets[p+1]) (offsets int64 on the device), three launches and no host synchronisation.  hypothesis_indices:
+    (P, num_iterations, ransac_n) int32 pair-local samples instead of the seeded sampler.  Returns a dict of device tensors: transforms
+    (P, 4, 4), fitness (P,), inlier_rmse (P,), best_hypothesis (P,) int32 (-1: identity); with per_hypothesis also counts (P, H) int32
+    and err_sums (P, H) float32."""
+    src = _req(src.contiguous(), torch.float32, 'src', 2)
+    ref = _req(ref.contiguous(), torch.float32, 'ref', 2)
+    offsets = _req(offsets.contiguous(), torch.int64, 'offsets', 1)
+    if src.shape != ref.shape or src.shape[1] != 3:
+        raise RuntimeError('ransac_stack: src and ref must both be (total, 3)')
+    P, H, rn = offsets.shape[0] - 1, int(num_iterations), int(ransac_n)
+    if P < 0 or H < 0:
+        raise RuntimeError('ransac_stack: %d pairs, %d iterations' % (P, H))
+    dev = src.device
+    if hypothesis_indices is not None:
+        hypothesis_indices = _req(hypothesis_indices.contiguous(), torch.int32, 'hypothesis_indices', 3)
+        if tuple(hypothesis_indices.shape) != (P, H, rn):
+            raise RuntimeError('ransac_stack: hypothesis_indices must be (%d, %d, %d)' % (P, H, rn))
+    out = dict(transforms=torch.empty((P, 4, 4), dtype=torch.float32, device=dev),
+               fitness=torch.empty((P,), dtype=torch.float32, device=dev),
+               inlier_rmse=torch.empty((P,), dtype=torch.float32, device=dev),
+               best_hypothesis=torch.empty((P,), dtype=torch.int32, device=dev))
+    if per_hypothesis:
+        out['counts'] = torch.empty((P, H), dtype=torch.int32, device=dev)
+        out['err_sums'] = torch.empty((P, H), dtype=torch.float32, device=dev)
+    nbytes = lib().se3_ransac_correspondences_workspace_bytes(P, H)
+    ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
+    check(lib().se3_ransac_correspondences_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn, H,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                 hypothesis_indices.data_ptr() if hypothesis_indices is not None else None,
+                                                 ws.data_ptr(), nbytes, out['transforms'].data_ptr(), out['fitness'].data_ptr(),
+                                                 out['inlier_rmse'].data_ptr(), out['best_hypothesis'].data_ptr(),
+                                                 out['counts'].data_ptr() if per_hypothesis else None,
+                                                 out['err_sums'].data_ptr() if per_hypothesis else None, _stream()),
+          'se3_ransac_correspondences_stack')
+    return out
+
+
 # ---- evaluation (csrc/evaluation.hip) ---------------------------------------------------------------------------------------------------
 class GroundTruthOverlaps:
     """Result of gt_node_overlaps_stack for B pairs, all on the device: `dense` packs pair p's (N_p, M_p) overlap matrix from entry
