@@ -703,6 +703,51 @@ int se3_ransac_correspondences_stack(const float* src_points, const float* ref_p
                                      float* fitness, float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts, float* err_sums,
                                      void* stream);
 
+/* ---- eval.py's benchmark metrics for stacked pairs (csrc/benchmark.hip) ---------------------------------------------------------------
+ * The per-pair metrics and summaries of experiments/se3ete.3dmatch/eval.py:42-357 and experiments/se3eti.kitti/eval.py:32-185.  Every call
+ * handles all pairs (groups) in a fixed number of launches with no host synchronisation; counts are integers and sums run in a fixed order,
+ * so a pair's row is bit-identical alone or in any batch.  The arithmetic contract is stated at the top of csrc/benchmark.hip.
+ *
+ * se3_benchmark_correspondences_stack: evaluate_correspondences (geotransformer/utils/registration.py:133-250).  ref_points / src_points
+ * (total, 3) float32, pair p owns rows [offsets[p], offsets[p+1]) (DEVICE int64, num_pairs + 1); max_count (HOST) >= every pair's count
+ * sizes the grid (a longer pair gets overlap NaN); transforms (num_pairs, 4, 4) DEVICE float32 ground truth (src -> ref).  out
+ * (num_pairs, 4) float64: overlap (nearest transformed src point closer than positive_radius, float32 distances), inlier_ratio,
+ * residual (float64), num_corr; 0 / 0 = NaN for a pair without correspondences.  workspace:
+ * se3_benchmark_correspondences_workspace_bytes(num_pairs) bytes.  A memset and two launches. */
+size_t se3_benchmark_correspondences_workspace_bytes(int num_pairs);
+int se3_benchmark_correspondences_stack(const float* ref_points, const float* src_points, const int64_t* offsets, int num_pairs,
+                                        int64_t max_count, const float* transforms, float positive_radius, void* workspace,
+                                        size_t workspace_bytes, double* out, void* stream);
+/* se3_benchmark_sparse_stack: evaluate_sparse_correspondences (registration.py:253-280) with its set semantics (duplicates count once).
+ * Predicted node pairs ref_node_indices / src_node_indices (DEVICE int64), pair p's on [pred_offsets[p], pred_offsets[p+1]); ground truth
+ * gt_node_corr_indices (g, 2) DEVICE int64 on [gt_offsets[p], gt_offsets[p+1]); node_counts (num_pairs, 2) DEVICE int64 (N_p, M_p);
+ * word_offsets (num_pairs + 1) DEVICE int64 the prefix sums of se3_benchmark_sparse_words(N_p, M_p) (32-bit bitmap words of the pair:
+ * 2 ceil(N M / 32) + 2 ceil(N / 32) + 2 ceil(M / 32)).  Indices outside [0, N) x [0, M) are ignored.  out (num_pairs, 3) float64:
+ * precision, recall, hit_ratio with the reference's + 1e-12 denominators.  workspace: se3_benchmark_sparse_workspace_bytes(node_counts
+ * (HOST, num_pairs x 2), num_pairs) bytes, zeroed by the call.  A memset and one launch. */
+int64_t se3_benchmark_sparse_words(int64_t num_ref_nodes, int64_t num_src_nodes);
+size_t se3_benchmark_sparse_workspace_bytes(const int64_t* node_counts, int num_pairs);
+int se3_benchmark_sparse_stack(const int64_t* ref_node_indices, const int64_t* src_node_indices, const int64_t* pred_offsets,
+                               const int64_t* gt_node_corr_indices, const int64_t* gt_offsets, const int64_t* node_counts,
+                               const int64_t* word_offsets, int num_pairs, void* workspace, size_t workspace_bytes, double* out, void* stream);
+/* se3_benchmark_transform_error_stack: compute_transform_error (datasets/registration/threedmatch/utils.py:131-137, nibabel's mat2quat) and
+ * compute_registration_error (registration.py:51-67) in float64.  gt_transforms / est_transforms (num_pairs, 4, 4), covariances
+ * (num_pairs, 6, 6) float64 DEVICE, has_covariance (num_pairs) DEVICE int32 (0: no covariance; NULL: none has one).  out (num_pairs, 3)
+ * float64: err (NaN without covariance), RRE (degrees), RTE.  One launch. */
+int se3_benchmark_transform_error_stack(const double* gt_transforms, const double* est_transforms, const double* covariances,
+                                        const int32_t* has_covariance, int num_pairs, double* out, void* stream);
+/* se3_benchmark_summary: eval.py's per-group and overall numbers.  rows (P, 6) DEVICE float64 per pair: precision, inlier_ratio, overlap,
+ * err, rre, rte; is_gt (P) DEVICE int32 (3DMatch: 1 for a benchmark pair -- listed in gt.log with id1 > id0 + 1 -- otherwise 0; unused for
+ * KITTI); group g owns pairs [group_offsets[g], group_offsets[g+1]) (DEVICE int64, num_groups + 1); max_group_pairs (HOST) the largest
+ * group, at most 4096 (SE3_ERR_UNSUPPORTED beyond).  group_out (num_groups, 14) and overall (14) float64: PIR, PMR>0, PMR>=0.1, PMR>=0.3,
+ * PMR>=0.5, FMR (inlier_ratio >= inlier_ratio_threshold), IR, OV, FMR_std, RR, mean_RRE, mean_RTE, median_RRE, median_RTE.  3DMatch
+ * (kitti == 0): a benchmark pair is accepted iff err < rmse_threshold^2, RR is over the benchmark pairs, the overall row is the mean over
+ * groups of each group value and FMR_std the population std of the groups' FMR.  KITTI: accepted iff rre < rre_threshold and rte <
+ * rte_threshold over all pairs, exactly one group, FMR_std over its pairs.  Means, medians and stds of empty sets are NaN.  Two launches. */
+int se3_benchmark_summary(const double* rows, const int32_t* is_gt, const int64_t* group_offsets, int num_groups, int64_t max_group_pairs,
+                          int kitti, double inlier_ratio_threshold, double rmse_threshold, double rre_threshold, double rte_threshold,
+                          double* group_out, double* overall, void* stream);
+
 /* Mutual top-k correspondence mask (local_global_registration.py:104-131): mask[b, i, j] = 1 iff scores[b, i, j] is among the k
  * largest of row i AND of column j of patch pair b (ties by index), exceeds `threshold`, and row_masks[b, i] & col_masks[b, j].
  * scores (batch, rows, cols) float32, masks uint8; rows * cols <= 16384. */

@@ -135,6 +135,14 @@ SIGNATURES = {
     'se3_ransac_correspondences_workspace_bytes': (_sz, [_i32, _i32]),
     'se3_ransac_correspondences_stack': (_i32, [_vp, _vp, _vp, _i32, _f32, _i32, _i32, ctypes.c_uint64, _vp, _vp, _sz, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
+    'se3_benchmark_correspondences_workspace_bytes': (_sz, [_i32]),
+    'se3_benchmark_correspondences_stack': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _f32, _vp, _sz, _vp, _vp]),
+    'se3_benchmark_sparse_words': (_i64, [_i64, _i64]),
+    'se3_benchmark_sparse_workspace_bytes': (_sz, [_vp, _i32]),
+    'se3_benchmark_sparse_stack': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp, _vp]),
+    'se3_benchmark_transform_error_stack': (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'se3_benchmark_summary': (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                     _vp, _vp, _vp]),
     'se3_mutual_topk_mask': (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     'se3_count_inliers': (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp]),
     'se3_count_inliers_ranges': (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),

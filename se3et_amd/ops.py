@@ -2240,3 +2240,113 @@ def registration_metrics_stack(pairs, gt_transforms, acceptance_overlap, accepta
                                                float(rre_threshold), float(rte_threshold), 1 if kitti else 0, rows.data_ptr(), _stream()),
           'se3_registration_metrics_stack')
     return rows
+
+
+# ---- eval.py's benchmark metrics (csrc/benchmark.hip) -------------------------------------------------------------------------------------
+def _same_device(dev, tensors, what):
+    for t in tensors:
+        if t.device != dev:
+            raise RuntimeError('%s: all tensors on %s' % (what, dev))
+
+
+def benchmark_correspondences_stack(ref, src, offsets, max_count, transforms, positive_radius):
+    """HIP: evaluate_correspondences for the P = len(offsets) - 1 pairs of stacked ref / src correspondence points (total, 3), pair p on
+    rows [offsets[p], offsets[p+1]) (offsets int64 on the device); max_count (host int) bounds every pair's count; transforms (P, 4, 4)
+    float32 ground truth.  Returns (P, 4) float64: overlap, inlier_ratio, residual, num_corr."""
+    ref = _req(ref.contiguous(), torch.float32, 'ref', 2)
+    src = _req(src.contiguous(), torch.float32, 'src', 2)
+    offsets = _req(offsets.contiguous(), torch.int64, 'offsets', 1)
+    transforms = _req(transforms.contiguous(), torch.float32, 'transforms', 3)
+    P = offsets.shape[0] - 1
+    if ref.shape != src.shape or ref.shape[1] != 3 or tuple(transforms.shape) != (P, 4, 4):
+        raise RuntimeError('benchmark_correspondences_stack: ref / src (total, 3) and transforms (%d, 4, 4) expected' % P)
+    dev = ref.device
+    _same_device(dev, (src, offsets, transforms), 'benchmark_correspondences_stack')
+    out = torch.empty((P, 4), dtype=torch.float64, device=dev)
+    nbytes = lib().se3_benchmark_correspondences_workspace_bytes(P)
+    ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
+    check(lib().se3_benchmark_correspondences_stack(ref.data_ptr(), src.data_ptr(), offsets.data_ptr(), P, int(max_count),
+                                                    transforms.data_ptr(), float(positive_radius), ws.data_ptr(), nbytes, out.data_ptr(),
+                                                    _stream()), 'se3_benchmark_correspondences_stack')
+    return out
+
+
+def benchmark_sparse_stack(ref_idx, src_idx, pred_offsets, gt_idx, gt_offsets, node_counts):
+    """HIP: evaluate_sparse_correspondences for P pairs.  ref_idx / src_idx (total,) and gt_idx (total_gt, 2) int64 on the device, pair p's
+    on [pred_offsets[p], pred_offsets[p+1]) / [gt_offsets[p], gt_offsets[p+1]) (device int64); node_counts: host list of P (N_p, M_p).
+    Returns (P, 3) float64: precision, recall, hit_ratio."""
+    ref_idx = _req(ref_idx.contiguous(), torch.int64, 'ref_node_indices', 1)
+    src_idx = _req(src_idx.contiguous(), torch.int64, 'src_node_indices', 1)
+    gt_idx = _req(gt_idx.contiguous(), torch.int64, 'gt_node_corr_indices', 2)
+    pred_offsets = _req(pred_offsets.contiguous(), torch.int64, 'pred_offsets', 1)
+    gt_offsets = _req(gt_offsets.contiguous(), torch.int64, 'gt_offsets', 1)
+    P = pred_offsets.shape[0] - 1
+    if ref_idx.shape != src_idx.shape or gt_idx.shape[1] != 2 or gt_offsets.shape[0] != P + 1 or len(node_counts) != P:
+        raise RuntimeError('benchmark_sparse_stack: mismatched shapes')
+    dev = ref_idx.device
+    _same_device(dev, (src_idx, gt_idx, pred_offsets, gt_offsets), 'benchmark_sparse_stack')
+    counts = [(int(n), int(m)) for n, m in node_counts]
+    if any(n < 0 or m < 0 for n, m in counts):
+        raise RuntimeError('benchmark_sparse_stack: negative node count')
+    words = [0]
+    for n, m in counts:
+        words.append(words[-1] + lib().se3_benchmark_sparse_words(n, m))
+    host_counts = _i64_array([v for c in counts for v in c] or [0])
+    nbytes = lib().se3_benchmark_sparse_workspace_bytes(host_counts, P)
+    if nbytes != 4 * words[-1]:
+        raise RuntimeError('benchmark_sparse_stack: workspace layout mismatch')
+    ws = torch.empty((max(4, nbytes),), dtype=torch.uint8, device=dev)
+    out = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    if P == 0:
+        return out
+    dev_counts = to_device([v for c in counts for v in c], torch.int64, dev)
+    dev_words = to_device(words, torch.int64, dev)
+    check(lib().se3_benchmark_sparse_stack(ref_idx.data_ptr(), src_idx.data_ptr(), pred_offsets.data_ptr(), gt_idx.data_ptr(),
+                                           gt_offsets.data_ptr(), dev_counts.data_ptr(), dev_words.data_ptr(), P, ws.data_ptr(), nbytes,
+                                           out.data_ptr(), _stream()), 'se3_benchmark_sparse_stack')
+    return out
+
+
+def benchmark_transform_error_stack(gt_transforms, est_transforms, covariances=None, has_covariance=None):
+    """HIP: compute_transform_error and compute_registration_error for P pairs, float64.  gt / est (P, 4, 4), covariances (P, 6, 6) float64
+    and has_covariance (P,) int32 on the device (None: no pair has one).  Returns (P, 3) float64: err (NaN without covariance), rre, rte."""
+    gt = _req(gt_transforms.contiguous(), torch.float64, 'gt_transforms', 3)
+    est = _req(est_transforms.contiguous(), torch.float64, 'est_transforms', 3)
+    P = gt.shape[0]
+    if tuple(gt.shape) != (P, 4, 4) or est.shape != gt.shape:
+        raise RuntimeError('benchmark_transform_error_stack: gt and est must be (P, 4, 4)')
+    if (covariances is None) != (has_covariance is None):
+        raise RuntimeError('benchmark_transform_error_stack: covariances and has_covariance go together')
+    dev = gt.device
+    if covariances is not None:
+        covariances = _req(covariances.contiguous(), torch.float64, 'covariances', 3)
+        has_covariance = _req(has_covariance.contiguous(), torch.int32, 'has_covariance', 1)
+        if tuple(covariances.shape) != (P, 6, 6) or tuple(has_covariance.shape) != (P,):
+            raise RuntimeError('benchmark_transform_error_stack: covariances (P, 6, 6) and has_covariance (P,) expected')
+        _same_device(dev, (covariances, has_covariance), 'benchmark_transform_error_stack')
+    _same_device(dev, (est,), 'benchmark_transform_error_stack')
+    out = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    check(lib().se3_benchmark_transform_error_stack(gt.data_ptr(), est.data_ptr(), None if covariances is None else covariances.data_ptr(),
+                                                    None if has_covariance is None else has_covariance.data_ptr(), P, out.data_ptr(),
+                                                    _stream()), 'se3_benchmark_transform_error_stack')
+    return out
+
+
+def benchmark_summary(rows, is_gt, group_lengths, kitti, inlier_ratio_threshold, rmse_threshold, rre_threshold, rte_threshold):
+    """HIP: eval.py's summaries.  rows (P, 6) float64 (precision, inlier_ratio, overlap, err, rre, rte), is_gt (P,) int32 on the device;
+    group_lengths: host list of the groups' pair counts (consecutive rows).  Returns (groups (G, 14), overall (14,)) float64."""
+    rows = _req(rows.contiguous(), torch.float64, 'rows', 2)
+    is_gt = _req(is_gt.contiguous(), torch.int32, 'is_gt', 1)
+    P, G = rows.shape[0], len(group_lengths)
+    lengths = [int(n) for n in group_lengths]
+    if rows.shape[1] != 6 or is_gt.shape[0] != P or sum(lengths) != P or any(n < 0 for n in lengths):
+        raise RuntimeError('benchmark_summary: rows (P, 6), is_gt (P,) and group lengths summing to P expected')
+    dev = rows.device
+    _same_device(dev, (is_gt,), 'benchmark_summary')
+    offsets = to_device([0] + [int(v) for v in torch.tensor(lengths, dtype=torch.int64).cumsum(0).tolist()], torch.int64, dev)
+    groups = torch.empty((max(G, 1), 14), dtype=torch.float64, device=dev)
+    overall = torch.empty((14,), dtype=torch.float64, device=dev)
+    check(lib().se3_benchmark_summary(rows.data_ptr(), is_gt.data_ptr(), offsets.data_ptr(), G, max(lengths, default=0), 1 if kitti else 0,
+                                      float(inlier_ratio_threshold), float(rmse_threshold), float(rre_threshold), float(rte_threshold),
+                                      groups.data_ptr(), overall.data_ptr(), _stream()), 'se3_benchmark_summary')
+    return groups[:G], overall
