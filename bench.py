@@ -12,9 +12,13 @@ kernels are covered by the other batches).  The raw pairs are resident in HBM be
 the job time is the MAX over ranks; value = pairs / second over all ranks.
 
 Prints ONE JSON line: pairs/s plus a `roofline` object for the RPE self-attention kernels (per-launch HIP events on the
-launch stream, live over the timed region; `roofline.quiet`: the same kernels with one batch in flight), a `roofline_kpconv` object (the
-fused KPConv kernel -- the largest family by time -- against the f16 matrix-core peak, event pairs around its launches), a `cpu_baseline` object (the CPU oracle timed on this box's host cores) and a
-`single_pair` object (the reference-shaped one-pair-per-forward path: pairs/s, kernel launches, host synchronisations).
+launch stream, live over the timed region) and `roofline_step` (the committed whole-step counter passes over this run's step time).  A plain
+run does only that: set-up, warm-up, the K timed steps, `--dump-outputs` if given, the line.  `--full` then measures what takes steps or
+pairs of its own and fills the line's other objects (null in a plain run): `dispersion` (the timed region repeated), `other_schedule`,
+`roofline.quiet` (the same kernels with one batch in flight), `roofline_kpconv` (the fused KPConv kernel -- the largest family by time --
+against the f16 matrix-core peak, event pairs around its launches), `roofline_dense`, `single_pair` (the reference-shaped
+one-pair-per-forward path: pairs/s, kernel launches, host synchronisations), `train_step` and `cpu_baseline` (the CPU oracle timed on the
+host's cores).
 
 Multi-GPU: one process per GPU.  Under `torch.distributed.run` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) every process
 is one rank.  Started directly with `--gpus N > 1`, this process only LAUNCHES: before anything touches a GPU it starts N fresh
@@ -288,16 +292,20 @@ def main():
     ap.add_argument('--warmup', type=int, default=9)
     ap.add_argument('--variant', default='se3ete')
     ap.add_argument('--pair', default='c2_5k')
+    ap.add_argument('--full', action='store_true', help='after the timed region, also measure everything that takes steps or pairs of its '
+                    'own: the repeats of the region (`dispersion`), `other_schedule`, the quiet steps, the KPConv / dense rooflines, the '
+                    'one-pair path, the training step and the CPU baseline (the options below tune them).  Off: the line carries the headline, '
+                    '`roofline` and `roofline_step` only')
     ap.add_argument('--cpu-baseline-pairs', type=int, default=5, help='timed pairs of the CPU baseline (after 3 warm-up pairs; median)')
     ap.add_argument('--cpu-baseline-threads', type=int, default=0, help='torch threads of the CPU baseline (0: min(cores, 8) -- the fastest setting on the host of the GPU box, profiles/r06_cpu_baseline_threads.txt)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--batch', type=int, default=16, help='registration pairs per forward / step (se3et_amd.batched), 1..16; '
                     '1 = the single-pair forward of the reference API')
     ap.add_argument('--switch-interval', type=float, default=1e-3)
     ap.add_argument('--prefetch', type=int, default=None, help='build the pyramid of the next batch on a second host thread / HIP '
                     'stream while the current batch runs through the model (the reference does this in DataLoader workers); every '
                     'timed step still builds its own pyramid inside the timed region.  0: pyramid and model back to back.  Default: 1 for '
-                    '--batch > 1 (+4 %: 297-303 against 285-292 pairs/s in a same-box A/B of the round-3 build; `roofline.quiet` reports the '
+                    '--batch > 1 (+4 %%: 297-303 against 285-292 pairs/s in a same-box A/B of the round-3 build; `roofline.quiet` reports the '
                     'attention kernels without the second stream), 0 for --batch 1 (550 launches per pair: a second host thread only takes '
                     'the interpreter away)')
     ap.add_argument('--attention-dtype', default='float32', choices=['float32', 'bfloat16'], help="'bfloat16': geometric embedding "
@@ -310,20 +318,20 @@ def main():
                     'grow: `roofline` reports them as measured in the timed region and `roofline.quiet` with one batch in flight.  Default 1 '
                     'for --batch 1')
     ap.add_argument('--single-pair-steps', type=int, default=16, help='pairs of the one-pair-per-forward measurement reported as '
-                    '`single_pair` (rank 0 at --gpus 1 only; 0 = skip)')
+                    '`single_pair` (--full; rank 0 at --gpus 1 only; 0 = skip)')
     ap.add_argument('--train-steps', type=int, default=5, help='training steps (fwd + bwd + Adam, one pair each) of the `train_step` object '
-                    '(rank 0 at --gpus 1 only; 0 = skip)')
+                    '(--full; rank 0 at --gpus 1 only; 0 = skip)')
     ap.add_argument('--schedule', default='roofline', choices=['roofline', 'throughput', 'exclusive', 'environment'],
                     help="how the batches in flight may overlap (se3et_amd.batched.set_schedule): 'roofline' (default) keeps the two coarsest backbone "
                          "stages from running beside another batch's transformer -- the RPE self-attention kernels then hold >= 0.40 of HBM IN the "
                          "timed region (0.45-0.47) at 455-458 pairs/s; 'throughput' lets them overlap: 487-493 pairs/s at 0.35-0.37; 'exclusive': no "
                          "backbone beside a transformer, 0.49-0.51 at 434-445.  The line reports the other of the first two in `other_schedule` "
-                         "(one more region of the same K steps).  'environment': whatever SE3_CHAIN / SE3_CHAIN_GROUPS / SE3_BACKBONE_SPLIT say")
-    ap.add_argument('--repeat-regions', type=int, default=2, help='the timed region (the same K steps between the same barrier + synchronize '
-                    'bracket) is run this many MORE times after the headline region; `dispersion` reports all values with their median, min '
-                    'and max (VERDICT round 5 item 6: a 4 %% move must be resolvable against the run-to-run spread).  0: off')
-    ap.add_argument('--roofline-quiet-steps', type=int, default=3, help='extra steps after the timed region with one batch in flight and no '
-                    'other stream, for `roofline.quiet` (0 = skip)')
+                         "(--full: one more region of the same K steps).  'environment': whatever SE3_CHAIN / SE3_CHAIN_GROUPS / SE3_BACKBONE_SPLIT say")
+    ap.add_argument('--repeat-regions', type=int, default=2, help='--full: the timed region (the same K steps between the same barrier + '
+                    'synchronize bracket) is run this many MORE times after the headline region; `dispersion` reports all values with their '
+                    'median, min and max (VERDICT round 5 item 6: a 4 %% move must be resolvable against the run-to-run spread).  0: off')
+    ap.add_argument('--roofline-quiet-steps', type=int, default=3, help='--full: extra steps after the timed region with one batch in flight '
+                    'and no other stream, for `roofline.quiet` (0 = skip)')
     ap.add_argument('--force-dist', action='store_true', help='initialise torch.distributed (RCCL) also with ONE rank: the device barrier and the '
                     'MAX all-reduce of the job clock then run on the GPU at world size 1 (tests/test_gpu_bench.py)')
     ap.add_argument('--fake-device', action='store_true', help='launcher self-test: gloo rendezvous, sharding, barriers and the '
@@ -593,115 +601,116 @@ def main():
         dump_outputs(captured['out'], args.dump_outputs)
         captured['out'] = None
 
-    # Dispersion: the SAME K steps between the same bracket, `--repeat-regions` more times (per-launch event timing off: the headline region
-    # above carries it).  `value` stays the first region -- the contract's "exactly K steps" -- and the repeats say how far a single region moves.
-    region_s = [elapsed]
-    se3_lib.lib().se3_debug_kernel_timing(0)
-    timings = {}
-    for rep in range(max(1, args.repeat_regions)):     # (at least one: the KPConv / dense families are timed in it)
-        se3_ops.KERNEL_TIMINGS = {} if rep == 0 else None
-        torch.cuda.synchronize()
-        sharding.barrier(dev)
-        t_r = time.perf_counter()
-        run_all(list(range(args.warmup, total_steps)))
-        torch.cuda.synchronize()
-        sharding.barrier(dev)
-        region_s.append(sharding.max_over_ranks(time.perf_counter() - t_r, dev))
-        if rep == 0:
-            timings, se3_ops.KERNEL_TIMINGS = se3_ops.KERNEL_TIMINGS, None
-    rates = [world * args.steps * PB / t for t in region_s]
-    dispersion = {'regions': len(rates), 'steps_per_region': args.steps, 'values': [round(v, 2) for v in rates],
-                  'median': round(sorted(rates)[len(rates) // 2], 2), 'min': round(min(rates), 2), 'max': round(max(rates), 2),
-                  'spread_rel': round((max(rates) - min(rates)) / sorted(rates)[len(rates) // 2], 4),
-                  'note': 'values[0] is `value` (the timed region of the contract, with the per-launch HIP events of the roofline kernel); values[1] '
-                          'is the same steps again, same bracket, with the event pairs of the KPConv and dense families instead (roofline_kpconv, '
-                          'roofline_dense); the others carry no events'}
-
-    # The other schedule, same K steps, same bracket, the roofline kernel's event pairs: what the overlap of the batches in flight is worth
-    # to the rate and costs the roofline figure (profiles/r06_frac_vs_overlap.txt)
-    other_schedule = None
-    if args.schedule in ('roofline', 'throughput') and args.inflight > 1 and args.repeat_regions > 0:
-        other = 'throughput' if args.schedule == 'roofline' else 'roofline'
-        se3_batched.set_schedule(other)
-        run_all(list(range(min(args.warmup, 2))))                       # (the chains start empty)
-        torch.cuda.synchronize()
-        sharding.barrier(dev)
-        se3_lib.lib().se3_debug_kernel_timing(1)
-        t_o = time.perf_counter()
-        run_all(list(range(args.warmup, total_steps)))
-        torch.cuda.synchronize()
-        sharding.barrier(dev)
-        el_o = sharding.max_over_ranks(time.perf_counter() - t_o, dev)
-        rf_o = collect_roofline(se3_lib, {}, args)
-        other_schedule = {'schedule': other, 'value': round(world * args.steps * PB / el_o, 3), 'ms_per_step': round(el_o / args.steps * 1e3, 3),
-                          'roofline_frac': rf_o['frac'], 'roofline_avg_us': rf_o['avg_us'],
-                          'note': 'the same K steps between the same bracket under the other schedule of se3et_amd.batched.set_schedule'}
-        se3_batched.set_schedule(args.schedule)
-
-    roofline_kpconv = collect_kpconv_roofline(timings)
-    roofline_dense = collect_dense_roofline(timings)
-    for extra in (roofline_kpconv, roofline_dense):
-        if extra is not None:
-            extra['measured_in'] = 'the first repeat of the timed region (dispersion.values[1]): the same K steps between the same bracket'
+    # A plain run ends here: the headline region (with the roofline kernel's event pairs, as always), the dump and the line need nothing
+    # more.  `--full` adds everything that takes steps or pairs of its own: the repeats of the region, the other schedule, the quiet steps,
+    # the one-pair path, the training step and the CPU baseline (the last alone is about a minute on the host).
+    dispersion = other_schedule = roofline_kpconv = roofline_dense = single_pair = train = cpu_baseline = None
     roofline_step = collect_step_roofline(elapsed, args.steps, args)
-    # The same kernels with nothing else on the GPU: by default other batches (--inflight) or the next batch's pyramid (--prefetch 1) run on
-    # other streams BESIDE the timed kernels, which lengthens them; a few extra steps with one batch in flight (after the timed region)
-    # give the kernels' own rate.
-    if (args.prefetch or args.inflight > 1) and args.roofline_quiet_steps > 0:
-        se3_ops.KERNEL_TIMINGS = {}
-        se3_lib.lib().se3_debug_kernel_timing(1)
-        for i in range(args.warmup, min(total_steps, args.warmup + args.roofline_quiet_steps)):
-            step(i)
-        torch.cuda.synchronize()
-        quiet_timings, se3_ops.KERNEL_TIMINGS = se3_ops.KERNEL_TIMINGS, None
-        quiet = collect_roofline(se3_lib, quiet_timings, args)
-        quiet_kp = collect_kpconv_roofline(quiet_timings)
-        quiet_dense = collect_dense_roofline(quiet_timings)
-        if roofline_dense is not None and quiet_dense is not None:
-            roofline_dense['quiet'] = {k: quiet_dense[k] for k in ('achieved', 'frac', 'launches', 'avg_us')}
-            roofline_dense['ms_per_step_of_this_family'] = round(quiet_dense['avg_us'] * quiet_dense['launches'] / max(args.roofline_quiet_steps, 1) / 1e3, 3)
-        if roofline_kpconv is not None and quiet_kp is not None:
-            roofline_kpconv['quiet'] = {k: quiet_kp[k] for k in ('achieved', 'frac', 'launches', 'avg_us', 'f32_equivalent_tflops')}
-        roofline['quiet'] = {k: quiet[k] for k in ('achieved', 'frac', 'launches', 'avg_us', 'rpe_bias_kernel_avg_us', 'attention_kernel_avg_us',
-                                                   'eq_call_avg_us', 'inv_call_avg_us')}
-        roofline['quiet']['note'] = ('same kernels, same shapes, %d extra step(s) after the timed region with ONE batch in flight and no other '
-                                     'stream active: the rate of the kernels themselves' % args.roofline_quiet_steps)
-        roofline['note'] = ('measured in the timed region, where %s share the GPU with the timed kernels (their durations include the '
-                            'time slices of the other streams); `quiet` = the same kernels alone on the GPU'
-                            % ('%d batches in flight' % args.inflight if args.inflight > 1 else "the next batch's pyramid kernels"))
-        if args.inflight > 1:
-            roofline['note'] += ("; schedule `%s` (se3et_amd.batched.set_schedule): %s" % (args.schedule, {
-                'roofline': "the two coarsest backbone stages of the other batches never run beside a transformer section, the rest of their work does; "
-                            "`other_schedule` = everything may overlap (the library's default): higher rate, the RPE kernels squeezed",
-                'throughput': 'every section of the other batches may run beside the timed kernels; `other_schedule` = the two coarsest backbone '
-                              'stages kept off the GPU during a transformer section',
-                'exclusive': 'no backbone section of the other batches beside a transformer section'}.get(args.schedule, 'as the environment says')))
-
-    # the auxiliary measurements never take the headline line down with them: a failure is reported in their place (and on stderr)
-    def guarded(what, f, *a):
-        try:
-            # every auxiliary measurement starts from an empty caching allocator, as if it ran in a process of its own: the one-pair forwards
-            # after three 16-pair steps on the same stream otherwise spend 3.4 ms of HOST time per pair re-cutting that stream's blocks
-            # (96 against 128 pairs/s, gpu_kernel_ms unchanged; round 6)
-            import gc
-            gc.collect()
+    if args.full:
+        # Dispersion: the SAME K steps between the same bracket, `--repeat-regions` more times (per-launch event timing off: the headline region
+        # above carries it).  `value` stays the first region -- the contract's "exactly K steps" -- and the repeats say how far a single region moves.
+        region_s = [elapsed]
+        se3_lib.lib().se3_debug_kernel_timing(0)
+        timings = {}
+        for rep in range(max(1, args.repeat_regions)):     # (at least one: the KPConv / dense families are timed in it)
+            se3_ops.KERNEL_TIMINGS = {} if rep == 0 else None
             torch.cuda.synchronize()
-            torch.cuda.empty_cache()
-            return f(*a)
-        except Exception as e:
-            import traceback
-            traceback.print_exc()
-            return {'error': '%s failed: %s' % (what, repr(e)[:300])}
+            sharding.barrier(dev)
+            t_r = time.perf_counter()
+            run_all(list(range(args.warmup, total_steps)))
+            torch.cuda.synchronize()
+            sharding.barrier(dev)
+            region_s.append(sharding.max_over_ranks(time.perf_counter() - t_r, dev))
+            if rep == 0:
+                timings, se3_ops.KERNEL_TIMINGS = se3_ops.KERNEL_TIMINGS, None
+        rates = [world * args.steps * PB / t for t in region_s]
+        dispersion = {'regions': len(rates), 'steps_per_region': args.steps, 'values': [round(v, 2) for v in rates],
+                      'median': round(sorted(rates)[len(rates) // 2], 2), 'min': round(min(rates), 2), 'max': round(max(rates), 2),
+                      'spread_rel': round((max(rates) - min(rates)) / sorted(rates)[len(rates) // 2], 4),
+                      'note': 'values[0] is `value` (the timed region of the contract, with the per-launch HIP events of the roofline kernel); values[1] '
+                              'is the same steps again, same bracket, with the event pairs of the KPConv and dense families instead (roofline_kpconv, '
+                              'roofline_dense); the others carry no events'}
 
-    single_pair = None
-    if rank == 0 and args.gpus == 1 and args.single_pair_steps > 0:
-        single_pair = guarded('single_pair', run_single_pair, model, cfg, args, dev, feats)
-    train = None
-    if rank == 0 and args.gpus == 1 and args.train_steps > 0 and args.variant == 'se3ete':
-        train = guarded('train_step', run_train_step, args.variant, args, dev)
-    cpu_baseline = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
-        cpu_baseline = guarded('cpu_baseline', run_cpu_baseline, model, cfg, args)
+        # The other schedule, same K steps, same bracket, the roofline kernel's event pairs: what the overlap of the batches in flight is worth
+        # to the rate and costs the roofline figure (profiles/r06_frac_vs_overlap.txt)
+        if args.schedule in ('roofline', 'throughput') and args.inflight > 1 and args.repeat_regions > 0:
+            other = 'throughput' if args.schedule == 'roofline' else 'roofline'
+            se3_batched.set_schedule(other)
+            run_all(list(range(min(args.warmup, 2))))                       # (the chains start empty)
+            torch.cuda.synchronize()
+            sharding.barrier(dev)
+            se3_lib.lib().se3_debug_kernel_timing(1)
+            t_o = time.perf_counter()
+            run_all(list(range(args.warmup, total_steps)))
+            torch.cuda.synchronize()
+            sharding.barrier(dev)
+            el_o = sharding.max_over_ranks(time.perf_counter() - t_o, dev)
+            rf_o = collect_roofline(se3_lib, {}, args)
+            other_schedule = {'schedule': other, 'value': round(world * args.steps * PB / el_o, 3), 'ms_per_step': round(el_o / args.steps * 1e3, 3),
+                              'roofline_frac': rf_o['frac'], 'roofline_avg_us': rf_o['avg_us'],
+                              'note': 'the same K steps between the same bracket under the other schedule of se3et_amd.batched.set_schedule'}
+            se3_batched.set_schedule(args.schedule)
+
+        roofline_kpconv = collect_kpconv_roofline(timings)
+        roofline_dense = collect_dense_roofline(timings)
+        for extra in (roofline_kpconv, roofline_dense):
+            if extra is not None:
+                extra['measured_in'] = 'the first repeat of the timed region (dispersion.values[1]): the same K steps between the same bracket'
+        # The same kernels with nothing else on the GPU: by default other batches (--inflight) or the next batch's pyramid (--prefetch 1) run on
+        # other streams BESIDE the timed kernels, which lengthens them; a few extra steps with one batch in flight (after the timed region)
+        # give the kernels' own rate.
+        if (args.prefetch or args.inflight > 1) and args.roofline_quiet_steps > 0:
+            se3_ops.KERNEL_TIMINGS = {}
+            se3_lib.lib().se3_debug_kernel_timing(1)
+            for i in range(args.warmup, min(total_steps, args.warmup + args.roofline_quiet_steps)):
+                step(i)
+            torch.cuda.synchronize()
+            quiet_timings, se3_ops.KERNEL_TIMINGS = se3_ops.KERNEL_TIMINGS, None
+            quiet = collect_roofline(se3_lib, quiet_timings, args)
+            quiet_kp = collect_kpconv_roofline(quiet_timings)
+            quiet_dense = collect_dense_roofline(quiet_timings)
+            if roofline_dense is not None and quiet_dense is not None:
+                roofline_dense['quiet'] = {k: quiet_dense[k] for k in ('achieved', 'frac', 'launches', 'avg_us')}
+                roofline_dense['ms_per_step_of_this_family'] = round(quiet_dense['avg_us'] * quiet_dense['launches'] / max(args.roofline_quiet_steps, 1) / 1e3, 3)
+            if roofline_kpconv is not None and quiet_kp is not None:
+                roofline_kpconv['quiet'] = {k: quiet_kp[k] for k in ('achieved', 'frac', 'launches', 'avg_us', 'f32_equivalent_tflops')}
+            roofline['quiet'] = {k: quiet[k] for k in ('achieved', 'frac', 'launches', 'avg_us', 'rpe_bias_kernel_avg_us', 'attention_kernel_avg_us',
+                                                       'eq_call_avg_us', 'inv_call_avg_us')}
+            roofline['quiet']['note'] = ('same kernels, same shapes, %d extra step(s) after the timed region with ONE batch in flight and no other '
+                                         'stream active: the rate of the kernels themselves' % args.roofline_quiet_steps)
+            roofline['note'] = ('measured in the timed region, where %s share the GPU with the timed kernels (their durations include the '
+                                'time slices of the other streams); `quiet` = the same kernels alone on the GPU'
+                                % ('%d batches in flight' % args.inflight if args.inflight > 1 else "the next batch's pyramid kernels"))
+            if args.inflight > 1:
+                roofline['note'] += ("; schedule `%s` (se3et_amd.batched.set_schedule): %s" % (args.schedule, {
+                    'roofline': "the two coarsest backbone stages of the other batches never run beside a transformer section, the rest of their work does; "
+                                "`other_schedule` = everything may overlap (the library's default): higher rate, the RPE kernels squeezed",
+                    'throughput': 'every section of the other batches may run beside the timed kernels; `other_schedule` = the two coarsest backbone '
+                                  'stages kept off the GPU during a transformer section',
+                    'exclusive': 'no backbone section of the other batches beside a transformer section'}.get(args.schedule, 'as the environment says')))
+
+        # the auxiliary measurements never take the headline line down with them: a failure is reported in their place (and on stderr)
+        def guarded(what, f, *a):
+            try:
+                # every auxiliary measurement starts from an empty caching allocator, as if it ran in a process of its own: the one-pair forwards
+                # after three 16-pair steps on the same stream otherwise spend 3.4 ms of HOST time per pair re-cutting that stream's blocks
+                # (96 against 128 pairs/s, gpu_kernel_ms unchanged; round 6)
+                import gc
+                gc.collect()
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                return f(*a)
+            except Exception as e:
+                import traceback
+                traceback.print_exc()
+                return {'error': '%s failed: %s' % (what, repr(e)[:300])}
+
+        if rank == 0 and args.gpus == 1 and args.single_pair_steps > 0:
+            single_pair = guarded('single_pair', run_single_pair, model, cfg, args, dev, feats)
+        if rank == 0 and args.gpus == 1 and args.train_steps > 0 and args.variant == 'se3ete':
+            train = guarded('train_step', run_train_step, args.variant, args, dev)
+        if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+            cpu_baseline = guarded('cpu_baseline', run_cpu_baseline, model, cfg, args)
     ranks_seen = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
 
     if rank == 0:
@@ -723,7 +732,7 @@ def main():
                        'schedule': args.schedule,
                        'chained_sections': sorted(__import__('se3et_amd.batched', fromlist=['x']).CHAINED_SECTIONS),
                        'priority_sections': sorted(__import__('se3et_amd.batched', fromlist=['x']).PRIORITY_SECTIONS),
-                       'attention_dtype': args.attention_dtype},
+                       'attention_dtype': args.attention_dtype, 'full': bool(args.full)},
             'roofline': roofline, 'roofline_kpconv': roofline_kpconv, 'roofline_dense': roofline_dense, 'roofline_step': roofline_step, 'dispersion': dispersion, 'other_schedule': other_schedule, 'cpu_baseline': cpu_baseline, 'single_pair': single_pair, 'train_step': train,
         }
         print(json.dumps(line), flush=True)

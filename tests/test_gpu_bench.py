@@ -2,7 +2,7 @@
 at world size 1, so bench's OWN collectives -- the device barrier in front of and behind the timed region and the MAX all-reduce of the job
 clock on a device tensor -- execute on the GPU (they had never run in any test, `init_distributed` returns early at world
 1); (b) the driver's exact step counts (`--steps 20 --warmup 5` is what BENCH_rNN records) run with three batches in flight and every
-in-flight stream primed before t0."""
+in-flight stream primed before t0 (with `--full`, for the measurements after the timed region); (c) a plain run stops after the headline."""
 import json
 import os
 import subprocess
@@ -41,7 +41,7 @@ def test_bench_collectives_run_on_rccl_at_world_size_one():
 
 
 def test_bench_at_the_drivers_step_counts():
-    line = _bench(['--gpus', '1', '--steps', '20', '--warmup', '5'] + LIGHT)
+    line = _bench(['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'] + LIGHT)
     assert line['steps'] == 20 and line['warmup'] == 5 and line['config']['batches_in_flight_per_gpu'] == 3
     assert line['config']['pairs_per_forward'] == 16            # the default since round 6 (profiles/r06_batch_inflight_sweep.txt)
     assert abs(line['value'] - 20 * 16 / (line['ms_per_step'] * 20 / 1e3)) <= 0.01 * line['value']
@@ -70,6 +70,17 @@ def test_bench_at_the_drivers_step_counts():
     # (round 6: 1.7-1.9 busy cores per rank with the flag against 3.8-4.2 without; round 5 read 0.8 -- the difference sits in the package, not in
     #  bench.py or the tie pass, and was not found: DESIGN section 5)
     assert line['host_cpu_s_per_step'] < 0.8 * 3 * line['ms_per_step'] * 1e-3
+
+
+def test_plain_bench_measures_only_the_headline():
+    """Without `--full` nothing runs after the timed region but the roofline collection and the line, whatever the other options ask for:
+    the repeats, the other schedule, the quiet steps, the one-pair path, the training step and the CPU baseline are all skipped."""
+    line = _bench(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '2'])
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['config']['full'] is False
+    assert abs(line['value'] - 2 * 2 / (line['ms_per_step'] * 2 / 1e3)) <= 0.01 * line['value']
+    for key in ('dispersion', 'other_schedule', 'roofline_kpconv', 'roofline_dense', 'single_pair', 'train_step', 'cpu_baseline'):
+        assert line[key] is None, key
+    assert line['roofline']['launches'] == 2 * 5 and 'quiet' not in line['roofline']
 
 
 def test_bench_dumps_the_last_timed_step_on_the_prefetch_path(tmp_path):
