@@ -638,7 +638,9 @@ int se3_superpoint_scores_stack(const float* feats, const uint8_t* node_masks, c
  * Correspondences are stacked: src/ref (total, 3), scores (total,); problem s uses rows [segment_offsets[s],
  * segment_offsets[s+1]) (int64, DEVICE, num_segments + 1 entries).  If gate_transform (4x4 row-major, DEVICE) is not NULL the
  * weight of a correspondence is score * [ |ref - T src| < gate_radius ] (the refinement re-weighting).  Weights are
- * normalised by (sum + eps).  transforms: (num_segments, 4, 4).  se3_count_inliers: votes[b] = #{i : |ref_i - T_b src_i| < radius}. */
+ * normalised by (sum + eps).  transforms: (num_segments, 4, 4).  se3_count_inliers: votes[b] = #{i : |ref_i - T_b src_i| < radius}.
+ * src/ref/scores may be NULL when there is no row to read (every segment empty; count_inliers: num_points == 0), as an empty
+ * tensor's data pointer is. */
 int se3_weighted_procrustes(const float* src_points, const float* ref_points, const float* scores,
                             const int64_t* segment_offsets, int num_segments, const float* gate_transform, float gate_radius,
                             float eps, float* transforms, void* stream);
@@ -750,7 +752,8 @@ int se3_benchmark_summary(const double* rows, const int32_t* is_gt, const int64_
 
 /* Mutual top-k correspondence mask (local_global_registration.py:104-131): mask[b, i, j] = 1 iff scores[b, i, j] is among the k
  * largest of row i AND of column j of patch pair b (ties by index), exceeds `threshold`, and row_masks[b, i] & col_masks[b, j].
- * scores (batch, rows, cols) float32, masks uint8; rows * cols <= 16384. */
+ * scores (batch, rows, cols) float32, masks uint8; rows * cols <= 16384; NULL pointers only with batch == 0.  A NaN score is never
+ * kept and takes no top-k slot (torch.topk would rank it first). */
 int se3_mutual_topk_mask(const float* scores, const uint8_t* row_masks, const uint8_t* col_masks, int batch, int rows, int cols,
                          int k, float threshold, uint8_t* mask, void* stream);
 

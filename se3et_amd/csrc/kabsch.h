@@ -38,7 +38,18 @@ __device__ void jacobi_eig3(double A[3][3], double V[3][3]) {     // symmetric A
 }
 
 // R = V diag(1, 1, det(V U^T)) U^T for H = U S V^T; t = rc - R sc; writes a row-major 4x4
-__device__ void kabsch(const double H[3][3], const double sc[3], const double rc[3], float* __restrict__ T) {
+__device__ void kabsch(const double H_in[3][3], const double sc[3], const double rc[3], float* __restrict__ T) {
+  // R depends only on the direction of H: scale it by an exact power of two so that max |H| lies in [0.5, 1).  The solve's floors
+  // below (1e-40, 1e-300) are then relative to H, and R is the same for a problem scaled by 2^k.  A zero H stays zero (identity);
+  // NaN entries are skipped by fmax and still reach R; an infinite H is left as it is.
+  double mx = 0.0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) mx = fmax(mx, fabs(H_in[i][j]));
+  int e = 0;
+  if (mx > 0.0 && isfinite(mx)) frexp(mx, &e);
+  double H[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) H[i][j] = ldexp(H_in[i][j], -e);
   double A[3][3], V[3][3];
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) A[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];   // H^T H

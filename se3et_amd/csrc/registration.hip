@@ -7,6 +7,11 @@
 // float64 Jacobi SVD of the 3x3 covariance; problems are segments of a stacked correspondence list (segment s =
 // [offsets[s], offsets[s+1])).  The refinement weights w_i = score_i * [ |r_i - T s_i| < radius ] are evaluated on the fly from
 // the previous transform, so a refinement step is ONE launch.
+//
+// Non-finite input: a NaN score or coordinate makes its own segment's transform NaN (a gated-out NaN score too: score * 0, as the
+// reference re-weights) and leaves the other segments alone; a NaN residual is never an inlier vote.  The mutual top-k mask never
+// keeps a NaN score, and a NaN takes no top-k slot of its row or column (no comparison with it holds) -- torch.topk in the
+// reference ranks NaN first, so a row holding NaN keeps one entry fewer there.
 #include "common.h"
 #include "kabsch.h"
 
@@ -41,12 +46,13 @@ __global__ __launch_bounds__(256) void procrustes_kernel(const float* __restrict
       const float dx = ref[3 * i] - (Tp[0] * sx + Tp[1] * sy + Tp[2] * sz + Tp[3]);
       const float dy = ref[3 * i + 1] - (Tp[4] * sx + Tp[5] * sy + Tp[6] * sz + Tp[7]);
       const float dz = ref[3 * i + 2] - (Tp[8] * sx + Tp[9] * sy + Tp[10] * sz + Tp[11]);
-      if (!(sqrtf(dx * dx + dy * dy + dz * dz) < radius)) w = 0.f;
+      if (!(sqrtf(dx * dx + dy * dy + dz * dz) < radius)) w *= 0.f;      // score * 0: a NaN score stays NaN, as in the reference
     }
     return w;
   };
   // one pass: raw weighted moments in float64 (sum w, sum w s, sum w r, sum w s r^T), centred afterwards -- in double the
-  // cancellation of the centring is harmless (coordinates ~1e0..1e2, 53-bit sums)
+  // cancellation of the centring is harmless up to ~1e3 m from the origin (tests/test_gpu_registration.py holds R of 1 m problems
+  // at 0, 80 and 1e3 m within 1e-6 of a float64 two-pass solve; farther out the error grows with the square of the offset)
   double m[16];
   for (int k = 0; k < 16; k++) m[k] = 0;
   for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
@@ -142,10 +148,10 @@ extern "C" int se3_weighted_procrustes_segments(const float* src_points, const f
                                                 const int64_t* segment_offsets, int num_segments, const float* gate_transforms,
                                                 int gate_per_segment, float gate_radius, float eps, float* transforms,
                                                 void* stream) {
-  SE3_REQUIRE(src_points && ref_points && scores && segment_offsets && transforms, SE3_ERR_INVALID_ARG,
-              "weighted_procrustes: null pointer");
   SE3_REQUIRE(num_segments >= 0, SE3_ERR_INVALID_ARG, "weighted_procrustes: negative segment count");
   if (num_segments == 0) return SE3_OK;
+  // (src / ref / scores of zero rows: an empty tensor's data pointer is null; the kernel reads none of them then)
+  SE3_REQUIRE(segment_offsets && transforms, SE3_ERR_INVALID_ARG, "weighted_procrustes: null pointer");
   procrustes_kernel<<<num_segments, 256, 0, (hipStream_t)stream>>>(src_points, ref_points, scores, segment_offsets,
                                                                    gate_transforms, gate_per_segment ? 16 : 0, gate_radius, eps,
                                                                    transforms);
@@ -163,9 +169,9 @@ extern "C" int se3_weighted_procrustes(const float* src_points, const float* ref
 extern "C" int se3_count_inliers_ranges(const float* src_points, const float* ref_points, int64_t num_points,
                                         const float* transforms, int num_transforms, const int64_t* range_begin,
                                         const int64_t* range_end, float radius, int32_t* votes, void* stream) {
-  SE3_REQUIRE(src_points && ref_points && transforms && votes, SE3_ERR_INVALID_ARG, "count_inliers: null pointer");
   SE3_REQUIRE((range_begin == nullptr) == (range_end == nullptr), SE3_ERR_INVALID_ARG, "count_inliers: ranges go together");
   if (num_transforms <= 0) return SE3_OK;
+  SE3_REQUIRE(transforms && votes && ((src_points && ref_points) || num_points == 0), SE3_ERR_INVALID_ARG, "count_inliers: null pointer");
   vote_kernel<<<num_transforms, 256, 0, (hipStream_t)stream>>>(src_points, ref_points, num_points, transforms, range_begin,
                                                               range_end, radius, votes);
   SE3_CHECK_LAUNCH("count_inliers");
@@ -180,7 +186,7 @@ extern "C" int se3_count_inliers(const float* src_points, const float* ref_point
 
 extern "C" int se3_mutual_topk_mask(const float* scores, const uint8_t* row_masks, const uint8_t* col_masks, int batch, int rows,
                                     int cols, int k, float threshold, uint8_t* mask, void* stream) {
-  SE3_REQUIRE(scores && row_masks && col_masks && mask, SE3_ERR_INVALID_ARG, "mutual_topk_mask: null pointer");
+  SE3_REQUIRE(batch == 0 || (scores && row_masks && col_masks && mask), SE3_ERR_INVALID_ARG, "mutual_topk_mask: null pointer");
   SE3_REQUIRE(batch >= 0 && rows >= 1 && cols >= 1 && k >= 1 && (size_t)rows * cols * sizeof(float) <= 64 * 1024, SE3_ERR_UNSUPPORTED,
               "mutual_topk_mask: batch %d rows %d cols %d k %d (rows * cols <= 16384)", batch, rows, cols, k);
   if (batch == 0) return SE3_OK;
