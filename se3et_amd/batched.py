@@ -11,6 +11,7 @@ Uses the parameters of an ordinary `se3et_amd.model.SE3ET`; nothing here is lear
 import torch
 import torch.nn.functional as F
 
+from . import caches
 from . import functional as SF
 from . import cdriver as _cdriver
 from . import ops as _ops
@@ -136,7 +137,7 @@ def _chained(section):
             st[1] = ev
 
 
-_pack_index_cache = {}     # (cloud order, cloud offsets, device) -> destination row of every stacked row (device tensor shared by the host threads)
+_pack_rows = caches.Derived(64)     # (cloud order, cloud offsets, device) -> destination row of every stacked row (device tensor shared by the host threads)
 
 
 class _Packed:
@@ -160,18 +161,15 @@ class _Packed:
         """pack([x[..., offs[c]:offs[c + 1], :] for c in order]) as ONE scatter of rows (a copy per cloud otherwise: 16 launches for 8 pairs):
         x ([A,] P, C) holds the clouds back to back, cloud order[i] goes to packed rows starts[i] .. + lengths[i]."""
         key = (tuple(order), tuple(offs), str(x.device))
-        dst = _pack_index_cache.get(key)
+        dst = _pack_rows.lookup((), key)
         if dst is None:
             rows = [0] * offs[-1]
             for i, c in enumerate(order):
                 for j in range(offs[c + 1] - offs[c]):
                     rows[offs[c] + j] = self.starts[i] + j
-            dst = SF.shared_tensors(_ops.to_device(rows, torch.int64, x.device))
-            if len(_pack_index_cache) > 64:
-                _pack_index_cache.clear()
-            _pack_index_cache[key] = dst
+            dst = _pack_rows.store((), key, _ops.to_device(rows, torch.int64, x.device))
         out = torch.zeros(x.shape[:-2] + (self.rows, x.shape[-1]), dtype=x.dtype, device=x.device)
-        return out.index_copy_(x.dim() - 2, dst.get()[0], x)
+        return out.index_copy_(x.dim() - 2, dst, x)
 
     def unpack(self, x):
         return [x[..., s0:s0 + n, :] for s0, n in zip(self.starts, self.lengths)]

@@ -9,6 +9,7 @@ import os
 
 import torch
 
+from . import caches
 from . import ops as _ops
 from ._lib import check, lib
 
@@ -167,7 +168,7 @@ def _static_plan(gt, stream):
     return plan, keep
 
 
-_ws = {}
+_ws = caches.Workspace(lambda nbytes: int(nbytes * 1.1) + 256)
 
 
 def transformer_forward(gt, X, PA, R0, embs, eqs):
@@ -195,11 +196,7 @@ def transformer_forward(gt, X, PA, R0, embs, eqs):
     if tuple(X.shape) != (plan.A, plan.rows, plan.C):
         raise RuntimeError('transformer_forward: X %s for (%d, %d, %d)' % (tuple(X.shape), plan.A, plan.rows, plan.C))
     nbytes = lib().se3_transformer_workspace_bytes(ctypes.byref(plan))
-    key = (X.device, stream.value)
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty((int(nbytes * 1.1) + 256,), dtype=torch.uint8, device=X.device)
-        _ws[key] = ws
+    ws = _ws.get(X.device, stream.value, nbytes)
     base = (ws.data_ptr() + 255) // 256 * 256
     out = torch.empty((plan.rows, gt.out_proj.out_features), dtype=torch.float32, device=X.device)
     check(lib().se3_transformer_forward(ctypes.byref(plan), X.data_ptr(), out.data_ptr(), base, ws.numel() - (base - ws.data_ptr()), stream),

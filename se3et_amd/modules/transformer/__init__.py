@@ -24,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ... import caches
 from ... import functional as SF
 from ... import tables
 
@@ -105,23 +106,19 @@ class RPEMultiHeadAttention(nn.Module):
         self.proj_p = nn.Linear(d_model, d_model)
         if equivariant and d_equiv_embed > 0:
             self.proj_eq = nn.Linear(d_equiv_embed, d_model)
+        self._composed = caches.Derived(1, weights=True)          # the composed projection: dies with the module, reached by clear / validate
 
     def stacked_projection(self):
         """(weight, bias, column offsets) of the fused [q | k | W_p^T q | W_eq^T q] projection, cached per weight version."""
-        params = [self.proj_q.weight, self.proj_q.bias, self.proj_k.weight, self.proj_k.bias, self.proj_p.weight]
         use_eq = self.equivariant and self.d_equiv_embed > 0
-        if use_eq:
-            params.append(self.proj_eq.weight)
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        cache = getattr(self, '_stack_cache', None)
-        if cache is None or cache[0] != key:
-            w, b, offs = SF.compose_self_attention_weights(self.proj_q.weight, self.proj_q.bias, self.proj_k.weight,
-                                                           self.proj_k.bias, self.proj_p.weight,
-                                                           self.proj_eq.weight if use_eq else None, self.num_heads)
-            cache = (key, SF.shared_tensors(w, b), offs)          # composed on this thread's stream; other streams wait for it on the GPU
-            self._stack_cache = cache
-        w, b = cache[1].get()
-        return w, b, cache[2]
+        params = (self.proj_q.weight, self.proj_q.bias, self.proj_k.weight, self.proj_k.bias, self.proj_p.weight) + ((self.proj_eq.weight,) if use_eq else ())
+        key = tuple(p.data_ptr() for p in params)          # (module.to() gives the same Parameters other storage without a version bump)
+        hit = self._composed.lookup(params, key)
+        if hit is None:             # composed on this thread's stream; other streams wait for it on the GPU
+            hit = self._composed.store(params, key, SF.compose_self_attention_weights(
+                self.proj_q.weight, self.proj_q.bias, self.proj_k.weight, self.proj_k.bias, self.proj_p.weight,
+                self.proj_eq.weight if use_eq else None, self.num_heads), fingerprint_of=params)
+        return hit
 
     def forward_packed(self, x, starts, lengths, embs, eq_embs):
         """Self attention of several clouds packed row-wise in x ([A,] R, C) (see functional.pack_rows)."""

@@ -4,10 +4,10 @@ PyTorch) and launches the HIP kernels on the current torch stream."""
 import ctypes
 import os
 import threading
-import weakref
 
 import torch
 
+from .caches import CACHE_EPOCH, Derived, Workspace, _Shared, also_clear, clear_caches, clear_weight_caches, validate_weight_caches  # noqa: F401
 from ._lib import check, lib
 
 
@@ -47,68 +47,27 @@ def mm(a, b):
 # are HBM bound and stay on the library, which streams them better), the library otherwise; SE3_LINEAR=library forces the library everywhere.
 LINEAR_F16 = os.environ.get('SE3_LINEAR', 'auto') != 'library'
 LINEAR_F16_MIN_ROWS, LINEAR_F16_MIN_K = 20000, 256
-_linear_piece_cache = {}          # (data_ptr, N, K, device) -> (weakref to the weight tensor, its version counter, pieces)
-
-
-class _Shared:
-    """Device tensors built asynchronously on one stream and read from others (weight pieces, index tables: caches shared by the host
-    threads of `--inflight N`, one HIP stream each).  A reader on another stream waits -- on the GPU, not the host -- for the event recorded
-    behind the kernels that fill them, and tells the caching allocator that its stream uses the memory too.  (Without this the second
-    thread's first GEMM could read weight pieces the first thread's split kernel had not written yet.)"""
-    __slots__ = ('tensors', 'stream', 'event', 'raw')
-
-    def __init__(self, *tensors):
-        self.tensors = tensors
-        self.stream = torch.cuda.current_stream()
-        self.event = torch.cuda.Event()
-        self.event.record(self.stream)
-        self.raw = self.stream.cuda_stream
-
-    def get(self):
-        raw = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-        if raw is not None and raw(self.stream.device.index) == self.raw and torch.cuda.current_device() == self.stream.device.index:
-            return self.tensors                              # the builder's own stream: nothing to wait for (and 2.6 us less host time)
-        cur = torch.cuda.current_stream()
-        if cur != self.stream:
-            if not self.event.query():
-                cur.wait_event(self.event)
-            for t in self.tensors:
-                t.record_stream(cur)
-        return self.tensors
-
-
-def _fingerprint(weight):
-    """Device-side content fingerprint of a weight tensor (wrapping int64 sum of its bit patterns; one small launch when a cache entry is
-    built, no host synchronisation): what validate_weight_caches() compares against the weight's current contents."""
-    with torch.no_grad():
-        return weight.detach().reshape(-1).view(torch.int32).sum(dtype=torch.int64)
+_linear_pieces = Derived(512, weights=True)          # (data_ptr, N, K, row stride, device) -> f16 pieces
 
 
 def _linear_weight_pieces(weight, stream):
-    """f16 hi / lo MFMA fragments of an (N, K) weight.  An entry is used only for the SAME Parameter object (weak reference compared by
-    identity: a freed tensor's address and version can be inherited by another tensor) at the same `_version` (torch bumps it on every
-    in-place update: optimizer steps, load_state_dict, copy_).  Writes that bypass the version counter (`p.data.copy_()`, `p.data = ...`,
-    raw pointers) are invisible to it: SE3ET.load_state_dict / .to() / ._apply() clear the caches, and validate_weight_caches() compares
-    every entry with the weight's current contents on the device.  A column / row block of a Parameter (`weight[:, :k]`: the decoder's
-    split dense layer) is keyed by its own address, shape and row stride and owned by its BASE tensor (the view object is a temporary)."""
+    """f16 hi / lo MFMA fragments of an (N, K) weight, kept while the weight is the same object at the same version (caches.Derived).  A
+    column / row block of a Parameter (`weight[:, :k]`: the decoder's split dense layer) is keyed by its own address, shape and row stride
+    and owned by its BASE tensor (the view object is a temporary)."""
     N, K = weight.shape
     owner = weight._base if weight._base is not None else weight
     key = (weight.data_ptr(), N, K, weight.stride(0), weight.device.index)
-    hit = _linear_piece_cache.get(key)
-    if hit is not None and hit[0]() is owner and hit[1] == owner._version:
-        return hit[2].get()[0]
+    Wp = _linear_pieces.lookup(owner, key)
+    if Wp is not None:
+        return Wp
     Wp = torch.empty((lib().se3_linear_weight_pieces_bytes(N, K),), dtype=torch.uint8, device=weight.device)
     w = weight.detach()
     w = w if w.is_contiguous() else w.contiguous()
     check(lib().se3_linear_split_weights_f16(w.data_ptr(), N, K, Wp.data_ptr(), stream), 'se3_linear_split_weights_f16')
-    with _TIMING_LOCK:
-        if len(_linear_piece_cache) > 512:
-            _linear_piece_cache.clear()
-        _linear_piece_cache[key] = (weakref.ref(owner), owner._version, _Shared(Wp), _fingerprint(weight), weight.stride(0))
-    return Wp
+    return _linear_pieces.store(owner, key, Wp, fingerprint_of=(weight,))
 
 
-_stacked_weight_cache = {}
+_stacked_weights = Derived(128, weights=True)
 
 
 def stacked_weight(weight, groups):
@@ -116,16 +75,12 @@ def stacked_weight(weight, groups):
     laid side by side along the channels returns the layer of their SUM (cross_attention_eq_stack with key-anchor groups).  Kept per weight
     version like the f16 pieces."""
     key = (weight.data_ptr(), tuple(weight.shape), int(groups), weight.device.index)
-    hit = _stacked_weight_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2].get()[0]
+    W = _stacked_weights.lookup(weight, key)
+    if W is not None:
+        return W
     with torch.no_grad():
         W = torch.cat([weight.detach()] * int(groups), 1).contiguous()
-    with _TIMING_LOCK:
-        if len(_stacked_weight_cache) > 128:
-            _stacked_weight_cache.clear()
-        _stacked_weight_cache[key] = (weakref.ref(weight), weight._version, _Shared(W), _fingerprint(weight))
-    return W
+    return _stacked_weights.store(weight, key, W, fingerprint_of=(weight,))
 
 
 def linear_f16_ok(x, weight):
@@ -655,7 +610,12 @@ def scatter_add_rows(g, idx, n):
     return out
 
 
-_gn_workspace = {}       # (device, stream) -> partial-statistics workspace
+# one buffer per launch stream and purpose: Workspace(floor in bytes)
+_ws_gn, _ws_gn_bwd = Workspace(1 << 22), Workspace(1 << 22)          # GroupNorm partial statistics
+_ws_attn = Workspace(1 << 22)             # f16 hi / lo pieces of K and V^T of a stack-mode attention call
+_ws_x6, _ws_emb = Workspace(1 << 24), Workspace(1 << 24)          # operand pieces of the equivariant cross attention; records of the embedding kernels
+# ... that begin with arrival counters (in-kernel finalize / split reduction): zero when first used; every call leaves the counters zero
+_ws_dense, _ws_kpconv_split, _ws_kpconv_union_split = (Workspace(1 << 20, zeroed=True) for _ in range(3))
 
 
 def group_norm_rows(x, weight, bias, groups, eps, leaky_slope, residual, x_bias=None, segments=None):
@@ -671,11 +631,7 @@ def group_norm_rows(x, weight, bias, groups, eps, leaky_slope, residual, x_bias=
             raise RuntimeError('group_norm_rows: residual shape mismatch')
     ws_bytes = lib().se3_group_norm_workspace_bytes(rows, C, groups)
     stream = _stream()
-    key = (x.device, stream.value)                 # one workspace per launch stream (calls on a stream are ordered)
-    ws = _gn_workspace.get(key)
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty((max(ws_bytes, 1 << 22),), dtype=torch.uint8, device=x.device)
-        _gn_workspace[key] = ws
+    ws = _ws_gn.get(x.device, stream.value, ws_bytes)
     out = torch.empty_like(x)
     nseg = 1 if segments is None else len(segments) - 1
     check(lib().se3_group_norm_segments_fwd(x.data_ptr(), x_bias.data_ptr() if x_bias is not None else None,
@@ -696,11 +652,7 @@ def group_norm_rows_bwd(grad_out, x, weight, bias, groups, eps, leaky_slope, res
         residual = _req(residual.contiguous(), torch.float32, 'residual')
     ws_bytes = lib().se3_group_norm_bwd_workspace_bytes(C)
     stream = _stream()
-    key = (x.device, stream.value, 'bwd')
-    ws = _gn_workspace.get(key)
-    if ws is None or ws.numel() < ws_bytes:
-        ws = torch.empty((max(ws_bytes, 1 << 22),), dtype=torch.uint8, device=x.device)
-        _gn_workspace[key] = ws
+    ws = _ws_gn_bwd.get(x.device, stream.value, ws_bytes)
     nseg = 1 if segments is None else len(segments) - 1
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if residual is not None else None
@@ -715,24 +667,7 @@ def group_norm_rows_bwd(grad_out, x, weight, bias, groups, eps, leaky_slope, res
     return dx, params[0], params[1], dres, (params[2] if x_bias is not None else None)
 
 
-_dense_ws = {}
-_kpconv_split_ws = {}
 KPCONV_SPLIT = True           # few-tile layers split their input channels over workgroups (False: A/B runs)
-
-
-def _zeroed_workspace(cache, device, stream, nbytes):
-    """A workspace that begins with arrival counters (in-kernel finalize / split reduction): one per stream, zero when first used; every
-    call leaves the counters zero."""
-    key = (device, stream.value)
-    ws = cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.zeros((max(nbytes, 1 << 20),), dtype=torch.uint8, device=device)
-        cache[key] = ws
-    return ws
-
-
-def _dense_workspace(device, stream, nbytes):
-    return _zeroed_workspace(_dense_ws, device, stream, nbytes)
 
 
 def _check_counters(status, what, ws):
@@ -852,7 +787,7 @@ def dense_norm(x, weight, linear_bias, norm_weight, norm_bias, groups, eps, segm
     nseg = 1 if segments is None else len(segments) - 1
     out = torch.empty(raw.shape[:-1] + (N,), dtype=torch.float32, device=raw.device)
     affine = torch.empty((nseg, 2, N), dtype=torch.float32, device=raw.device)
-    ws = _dense_workspace(raw.device, stream, lib().se3_dense_norm_workspace_bytes(int(groups)))
+    ws = _ws_dense.get(raw.device, stream.value, lib().se3_dense_norm_workspace_bytes(int(groups)))
     aa = pend.affines + [None, None]
     sl = pend.slopes + [1.0, 1.0]
     with _timed('dense', 4.0 * rows * (K + N)):           # (bench.py roofline_dense: activations read + product written)
@@ -878,7 +813,7 @@ def dense_stats(x, weight, linear_bias, norm_weight, norm_bias, groups, eps, seg
     Wp = _linear_weight_pieces(weight, stream)
     nseg = 1 if segments is None else len(segments) - 1
     affine = torch.empty((nseg, 2, N), dtype=torch.float32, device=raw.device)
-    ws = _dense_workspace(raw.device, stream, lib().se3_dense_norm_workspace_bytes(int(groups)))
+    ws = _ws_dense.get(raw.device, stream.value, lib().se3_dense_norm_workspace_bytes(int(groups)))
     aa = pend.affines + [None, None]
     sl = pend.slopes + [1.0, 1.0]
     with _timed('dense', 4.0 * rows * K):                 # (statistics only: the activations read, nothing written)
@@ -890,20 +825,15 @@ def dense_stats(x, weight, linear_bias, norm_weight, norm_bias, groups, eps, seg
     return affine
 
 
-_nonzero_norm_cache = {}
+_nonzero_norms = Derived(256, weights=True)
 
 
 def norm_weight_nonzero(weight):
     """True when no entry of a GroupNorm weight is zero (one host synchronisation per weight version): dense_residual's shortcut form divides
     by the shortcut norm's scale."""
     key = (weight.data_ptr(), weight.device.index, tuple(weight.shape))
-    hit = _nonzero_norm_cache.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        hit = (weakref.ref(weight), weight._version, bool((weight.detach().abs() > 1e-30).all()))
-        if len(_nonzero_norm_cache) > 256:
-            _nonzero_norm_cache.clear()
-        _nonzero_norm_cache[key] = hit
-    return hit[2]
+    hit = _nonzero_norms.lookup(weight, key)
+    return hit if hit is not None else _nonzero_norms.store(weight, key, bool((weight.detach().abs() > 1e-30).all()))
 
 
 def dense_residual(x, weight, affine, residual=None, shortcut=None, final_slope=1.0, segments=None):
@@ -959,7 +889,7 @@ def group_norm_stats(x, weight, bias, groups, eps, x_bias=None, segments=None):
     stream = _stream()
     nseg = 1 if segments is None else len(segments) - 1
     affine = torch.empty((nseg, 2, C), dtype=torch.float32, device=raw.device)
-    ws = _dense_workspace(raw.device, stream, lib().se3_group_norm_stats_workspace_bytes(C))
+    ws = _ws_dense.get(raw.device, stream.value, lib().se3_group_norm_stats_workspace_bytes(C))
     pa = pend.affines[0] if pend.affines else None
     _check_counters(lib().se3_group_norm_stats(raw.data_ptr(), pa.data_ptr() if pa is not None else None, float(pend.slopes[0]) if pa is not None else 1.0,
                                      x_bias.data_ptr() if x_bias is not None else None, weight.data_ptr(), bias.data_ptr(), rows, C,
@@ -1000,22 +930,16 @@ def group_norm_apply(x, residual=None, final_slope=1.0, blocked=False):
     return BlockedFeatures(out, raw.shape, int(blocked), amax, amax_tag) if blocked else out
 
 
-_host_table_cache = {}
+_host_tables = Derived(256, weights=True)
 
 
 def _host_table(t, dtype):
-    """Constant module tables (kernel points, permutation indices) as host arrays, cached per owning tensor object, view and
-    version.  The entry holds a weak reference to the owner (the module's parameter / buffer; for a view, its base): a freed
-    tensor's address and id can be handed to another tensor with other values, so neither alone identifies the table."""
+    """Constant module tables (kernel points, permutation indices) as host arrays, cached per view and owned by the module's parameter /
+    buffer (for a view, its base)."""
     base = t._base if t._base is not None else t
-    key = (id(base), base._version, t.data_ptr(), tuple(t.shape), tuple(t.stride()))
-    hit = _host_table_cache.get(key)
-    if hit is None or hit[1]() is not base:
-        hit = (t.detach().to('cpu', dtype).contiguous(), weakref.ref(base))
-        if len(_host_table_cache) > 256:
-            _host_table_cache.clear()
-        _host_table_cache[key] = hit
-    return hit[0]
+    key = (t.data_ptr(), t.shape, t.stride(), dtype)
+    hit = _host_tables.lookup(base, key)
+    return hit if hit is not None else _host_tables.store(base, key, t.detach().to('cpu', dtype).contiguous())
 
 
 # KPConv path: True / 'auto' = the fused matrix-core kernel (csrc/kpconv_mfma.hip) where the channel counts allow (Cin % 8, Cout % 32),
@@ -1044,71 +968,24 @@ def _builtin_slot_tables(kt, rt):
     return hit[1]
 
 
-_weight_piece_cache = {}          # (data_ptr, Cin, Cout, device) -> (weakref to the weight tensor, its version counter, pieces)
+_kpconv_pieces = Derived(256, weights=True)          # (data_ptr, Cin, Cout, device) -> f16 pieces
 
 
 def _kpconv_weight_pieces(weights, Cin, Cout, stream):
     """f16 hi / lo MFMA fragments of KPConvInterSO3.weights (se3_kpconv_split_weights_f16).  Without autograd (inference) they are kept per
-    weight VERSION: torch bumps `_version` on every in-place update (optimizer steps, load_state_dict, copy_), so a stale entry is never
-    used as long as the weights are not rewritten behind torch's back (`.data` arithmetic, raw pointers) -- call
-    clear_weight_caches() after such an edit.  Under autograd the fragments are rebuilt per call (3 small launches)."""
+    weight object and version (caches.Derived); under autograd the fragments are rebuilt per call (3 small launches)."""
     w = _req(weights.detach().contiguous(), torch.float32, 'weights', 4)
     cacheable = not torch.is_grad_enabled() and w.data_ptr() == weights.data_ptr()
     key = (w.data_ptr(), Cin, Cout, w.device.index)
     if cacheable:
-        hit = _weight_piece_cache.get(key)
-        if hit is not None and hit[0]() is weights and hit[1] == weights._version:
-            return hit[2].get()[0]
+        Wp = _kpconv_pieces.lookup(weights, key)
+        if Wp is not None:
+            return Wp
     Wp = torch.empty((lib().se3_kpconv_weight_pieces_bytes(Cin, Cout),), dtype=torch.uint8, device=w.device)
     check(lib().se3_kpconv_split_weights_f16(w.data_ptr(), Cin, Cout, Wp.data_ptr(), stream), 'se3_kpconv_split_weights_f16')
     if cacheable:
-        with _TIMING_LOCK:
-            if len(_weight_piece_cache) > 256:
-                _weight_piece_cache.clear()
-            _weight_piece_cache[key] = (weakref.ref(weights), weights._version, _Shared(Wp), _fingerprint(weights))
+        _kpconv_pieces.store(weights, key, Wp, fingerprint_of=(weights,))
     return Wp
-
-
-CACHE_EPOCH = [0]          # bumped whenever cached weight pieces are dropped: part of the key of plans that hold raw pointers into them (cdriver)
-
-
-def clear_weight_caches():
-    CACHE_EPOCH[0] += 1
-    _padded_weight_cache.clear()
-    _weight_piece_cache.clear()
-    _linear_piece_cache.clear()
-    _stacked_weight_cache.clear()
-
-
-def validate_weight_caches():
-    """Compares the content fingerprint of every cached weight with the weight's CURRENT values (all sums on the device, one host
-    synchronisation in all) and drops the entries that no longer match or whose Parameter is gone.  For code that writes weights behind
-    torch's version counter (`p.data.copy_()`, EMA swaps through `.data`, hand-written checkpoint loaders).  Returns the number of entries
-    dropped."""
-    entries = []
-    for cache in (_weight_piece_cache, _linear_piece_cache, _stacked_weight_cache, _padded_weight_cache):
-        for key, hit in list(cache.items()):
-            w = hit[0]()
-            if w is not None and cache is _linear_piece_cache and w.data_ptr() != key[0]:
-                # a block of its owner (key: address, N, K, row stride): rebuild the view
-                off = (key[0] - w.data_ptr()) // w.element_size()
-                w = torch.as_strided(w, (key[1], key[2]), (key[3], 1), w.storage_offset() + off) if 0 <= off < w.numel() else None
-            if w is None or w.data_ptr() != key[0]:
-                cache.pop(key, None)
-                entries.append(None)
-            else:
-                entries.append((cache, key, hit[3], _fingerprint(w)))
-    live = [e for e in entries if e is not None]
-    dropped = len(entries) - len(live)
-    if live:
-        same = (torch.stack([e[2].to(live[0][2].device) for e in live]) == torch.stack([e[3].to(live[0][2].device) for e in live])).tolist()
-        for ok, (cache, key, _, _) in zip(same, live):
-            if not ok:
-                cache.pop(key, None)
-                dropped += 1
-    if dropped:
-        CACHE_EPOCH[0] += 1          # plans holding pointers to the dropped pieces (cdriver._static_plan) are rebuilt
-    return dropped
 
 
 def kpconv_slot_sums(x, q_pts, s_pts, idx, kernel_points, kidx, ridx, sigma):
@@ -1179,14 +1056,13 @@ def kpconv_inter_so3_bwd(grad_out, x, q_pts, s_pts, idx, kernel_points, weights,
 
 KPCONV_BACKWARD_DETERMINISTIC = os.environ.get('SE3_KPCONV_BWD', 'fixed') != 'float'      # 64-bit fixed-point scatter (bit-identical runs); 'float': hardware float atomics
 TRAINING_DETERMINISTIC = KPCONV_BACKWARD_DETERMINISTIC      # the other scatter-adds of the training step (max-pool, row gather, LayerNorm parameter sums) follow the same switch
-_neighbor_table_cache = {}
+_neighbor_tables = Derived(64, share=False)          # stream -> (key, table) of the last geometry seen there
 
 
 def _kpconv_neighbor_table(q_pts, s_pts, idx, kernel_points, sigma, P, Ns, NN, stream):
     """The neighbour table of the fused KPConv (valid neighbours compacted + 16 orbit weights each): a function of the geometry only, so the
     layers of a pyramid stage (same query / support points, neighbour indices, kernel points and extent) share it.  Kept per stream for the
-    LAST geometry seen -- identified by the tensor objects themselves (weak references: a freed tensor's address can be reused) and their
-    version counters (in-place changes)."""
+    LAST geometry seen (the same tensor objects at the same versions)."""
     kpd = _req(kernel_points.detach().contiguous(), torch.float32, 'kernel_points', 2)
     # (the kernel points enter by VALUE -- the bytes of their cached host copy: the layers of a stage own different Parameter objects holding
     # the same 15 points, and shared one table only by accident of the cache's depth before round 5: 10 -> 7 table launches per forward)
@@ -1195,21 +1071,19 @@ def _kpconv_neighbor_table(q_pts, s_pts, idx, kernel_points, sigma, P, Ns, NN, s
     if kp_key is None:
         kp_key = kph.numpy().tobytes()
         kph._se3_bytes = kp_key
-    key = (q_pts.data_ptr(), q_pts._version, s_pts.data_ptr(), s_pts._version, idx.data_ptr(), idx._version, kp_key, float(sigma), P, Ns, NN)
-    hit = _neighbor_table_cache.get(stream.value)
-    if hit is not None and hit[0] == key and all(r() is t for r, t in zip(hit[1], (q_pts, s_pts, idx))):
-        return hit[2]
+    key = (kp_key, float(sigma), P, Ns, NN)
+    hit = _neighbor_tables.lookup((q_pts, s_pts, idx), stream.value)
+    if hit is not None and hit[0] == key:
+        return hit[1]
     nbytes = lib().se3_kpconv_neighbor_table_bytes(P, NN)
     tab = torch.empty((nbytes,), dtype=torch.uint8, device=q_pts.device)
     check(lib().se3_kpconv_neighbor_table(q_pts.data_ptr(), s_pts.data_ptr(), idx.data_ptr(), kpd.data_ptr(), float(sigma), P, Ns, NN,
                                           tab.data_ptr(), nbytes, stream), 'se3_kpconv_neighbor_table')
-    _neighbor_table_cache[stream.value] = (key, tuple(weakref.ref(t) for t in (q_pts, s_pts, idx)), tab)
-    return tab
+    return _neighbor_tables.store((q_pts, s_pts, idx), stream.value, (key, tab))[1]
 
 
-_point_orders = {}               # points.data_ptr() -> (weakref to the points tensor, its version, order (G * 16 int32), G)
-_union_plan_cache = {}           # stream -> (key, weakrefs, plan)
-_kpconv_union_split_ws = {}
+_point_orders = Derived(256, prune_dead=True, share=False)          # points.data_ptr() -> (order (G * 16 int32), G), owned by the points tensor
+_union_plans = Derived(64, share=False)               # stream -> plan of the last (geometry, order) seen there
 
 
 def register_point_order(points, lengths, cell):
@@ -1233,11 +1107,7 @@ def register_point_order(points, lengths, cell):
         check(lib().se3_point_order_keys(points.data_ptr(), n, la, len(lens), float(cell), keys.data_ptr(), stream), 'se3_point_order_keys')
         sk, si = torch.sort(keys, stable=True)
         check(lib().se3_point_order_place(sk.data_ptr(), si.data_ptr(), n, la, len(lens), order.data_ptr(), stream), 'se3_point_order_place')
-    with _TIMING_LOCK:
-        if len(_point_orders) > 256:
-            for k in [k for k, v in _point_orders.items() if v[0]() is None]:
-                del _point_orders[k]
-        _point_orders[points.data_ptr()] = (weakref.ref(points), points._version, order, G)
+    _point_orders.store(points, points.data_ptr(), (order, G))
     return order
 
 
@@ -1261,20 +1131,13 @@ def register_point_orders(points_list, lengths_list, cells):
                                        (vp * S)(*[ctypes.cast(la, vp).value for la in las]), (ctypes.c_int * S)(*[len(l) for l in lens]),
                                        (ctypes.c_float * S)(*[float(c) for c in cells]), (vp * S)(*[o.data_ptr() for o in orders]), S, _stream()),
           'se3_point_order_stages')
-    with _TIMING_LOCK:
-        if len(_point_orders) > 256:
-            for k in [k for k, v in _point_orders.items() if v[0]() is None]:
-                del _point_orders[k]
-        for p, o, G in zip(points_list, orders, Gs):
-            _point_orders[p.data_ptr()] = (weakref.ref(p), p._version, o, G)
+    for p, o, G in zip(points_list, orders, Gs):
+        _point_orders.store(p, p.data_ptr(), (o, G))
     return orders
 
 
 def point_order(points):
-    hit = _point_orders.get(points.data_ptr())
-    if hit is None or hit[0]() is not points or hit[1] != points._version:
-        return None
-    return hit[2], hit[3]
+    return _point_orders.lookup(points, points.data_ptr())
 
 
 def _kpconv_union_plan(tab, q_pts, s_pts, idx, order, G, P, NN, stream):
@@ -1282,15 +1145,14 @@ def _kpconv_union_plan(tab, q_pts, s_pts, idx, order, G, P, NN, stream):
     (se3_kpconv_union_plan): a function of (order, neighbour table); kept per stream for the last table seen."""
     # (the plan reads the table's compacted lists and counts only -- the geometry, not the layer's kernel points: layers with tables of
     # their own over the same (queries, supports, neighbour indices) share it)
-    hit = _union_plan_cache.get(stream.value)
-    if hit is not None and hit[1] is order and all(r() is t for r, t in zip(hit[0], (q_pts, s_pts, idx))) and hit[3] == (q_pts._version, s_pts._version, idx._version):
-        return hit[2]
+    plan = _union_plans.lookup((q_pts, s_pts, idx, order), stream.value)
+    if plan is not None:
+        return plan
     nbytes = lib().se3_kpconv_union_plan_bytes(G, NN)
     plan = torch.empty((nbytes,), dtype=torch.uint8, device=q_pts.device)
     order.record_stream(torch.cuda.current_stream())
     check(lib().se3_kpconv_union_plan(tab.data_ptr(), P, NN, order.data_ptr(), G, plan.data_ptr(), nbytes, stream), 'se3_kpconv_union_plan')
-    _union_plan_cache[stream.value] = (tuple(weakref.ref(t) for t in (q_pts, s_pts, idx)), order, plan, (q_pts._version, s_pts._version, idx._version))
-    return plan
+    return _union_plans.store((q_pts, s_pts, idx, order), stream.value, plan)
 
 
 def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, sigma):
@@ -1311,7 +1173,7 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
     Cout = weights.shape[-1]
     if A != 6 or tuple(weights.shape[:3]) != (6, 6, Cin) or Ns != s_pts.shape[0]:
         raise RuntimeError('kpconv_inter_so3: inconsistent shapes')
-    kp, kt, rt = _host_table(kernel_points, torch.float32), _host_table(kidx, torch.int64), _host_table(ridx, torch.int64)
+    kt, rt = _host_table(kidx, torch.int64), _host_table(ridx, torch.int64)
     path = _kpconv_use_matrix_core(Cin, Cout, P)
     fused_ok = bool(path) and Cin % 8 == 0 and Cout % 32 == 0 and Ns * 6 * Cin < 2 ** 31 and _builtin_slot_tables(kt, rt)
     po = point_order(q_pts) if (fused_ok and path is True and KPCONV_UNION and _kpconv_union_pays(Cin, Cout, q_pts is s_pts)) else None
@@ -1340,7 +1202,7 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
             order, G = po
             plan = _kpconv_union_plan(tab, q_pts, s_pts, idx, order, G, P, NN, stream)
             sbytes = lib().se3_kpconv_union_split_workspace_bytes(G, Cin, Cout) if KPCONV_SPLIT else 0
-            sws = _zeroed_workspace(_kpconv_union_split_ws, x.device, stream, sbytes) if sbytes else None
+            sws = _ws_kpconv_union_split.get(x.device, stream.value, sbytes) if sbytes else None
             with _timed('kpconv_fused', 2.0 * 6 * P * 36 * Cin * Cout + 2.0 * P * NN * 16 * 6 * Cin):
                 _check_counters(lib().se3_kpconv_so3_union(x.data_ptr(), tab.data_ptr(), plan.data_ptr(), G, P, Ns, NN, Cin, Cout, Wp.data_ptr(),
                                                            out.data_ptr(), sws.data_ptr() if sws is not None else None,
@@ -1349,7 +1211,7 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
                                 'se3_kpconv_so3_union', sws)
             return out
         sbytes = lib().se3_kpconv_fused_split_workspace_bytes(P, Cin, Cout) if KPCONV_SPLIT else 0
-        sws = _zeroed_workspace(_kpconv_split_ws, x.device, stream, sbytes) if sbytes else None
+        sws = _ws_kpconv_split.get(x.device, stream.value, sbytes) if sbytes else None
         # (bench.py: event pair around the launch; algorithmic flops = contraction 2.6P.36Cin.Cout + the gather as a product 2.P.NN.16.6Cin)
         with _timed('kpconv_fused', 2.0 * 6 * P * 36 * Cin * Cout + 2.0 * P * NN * 16 * 6 * Cin):
             _check_counters(lib().se3_kpconv_so3_fused_scaled(x.data_ptr(), tab.data_ptr(), P, Ns, NN, Cin, Cout, Wp.data_ptr(), out.data_ptr(),
@@ -1357,6 +1219,7 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
                                                               1 if blocked else 0, x_amax.data_ptr() if x_amax is not None else None, stream),
                             'se3_kpconv_so3_fused', sws)
         return out
+    kp = _host_table(kernel_points, torch.float32)          # (only this path reads the kernel points on the host)
     G = torch.empty((P * 6, 36 * Cin), dtype=torch.float32, device=x.device)
     check(lib().se3_kpconv_so3_gather(q_pts.data_ptr(), s_pts.data_ptr(), idx.data_ptr(), x.data_ptr(), kp.data_ptr(),
                                       kt.data_ptr(), rt.data_ptr(), float(sigma), P, Ns, NN, Cin, G.data_ptr(), _stream()),
@@ -1375,23 +1238,19 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
     return mm(G, weights.reshape(Kg, Cout)).view(P, 6, Cout)
 
 
-_padded_weight_cache = {}
+_padded_weights = Derived(64, weights=True)
 
 
 def _padded_transposed_weight(weights, Kg, Kp, Cout):
     """(6, 6, Cin, Cout) KPConv weights as a dense layer's (Cout, Kp) weight: transposed, zero columns from Kg to Kp; kept per weight version."""
     key = (weights.data_ptr(), Kg, Kp, Cout, weights.device.index)
-    hit = _padded_weight_cache.get(key)
-    if hit is not None and hit[0]() is weights and hit[1] == weights._version:
-        return hit[2].get()[0]
+    Wt = _padded_weights.lookup(weights, key)
+    if Wt is not None:
+        return Wt
     with torch.no_grad():
         Wt = torch.zeros((Cout, Kp), dtype=torch.float32, device=weights.device)
         Wt[:, :Kg] = weights.detach().reshape(Kg, Cout).t()
-    with _TIMING_LOCK:
-        if len(_padded_weight_cache) > 64:
-            _padded_weight_cache.clear()
-        _padded_weight_cache[key] = (weakref.ref(weights), weights._version, _Shared(Wt), _fingerprint(weights))
-    return Wt
+    return _padded_weights.store(weights, key, Wt, fingerprint_of=(weights,))
 
 
 def key_stride(M):
@@ -1656,12 +1515,7 @@ def _attention_pieces(A, k_starts, k_lengths, C, v_row_stride, device):
     nbytes = lib().se3_attention_kv_pieces_bytes(int(A), rows, int(C), int(v_row_stride))
     if nbytes == 0:
         return None, 0
-    stream = _stream()
-    key = (device, stream.value, 'attn')
-    ws = _gn_workspace.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty((max(nbytes, 1 << 22),), dtype=torch.uint8, device=device)
-        _gn_workspace[key] = ws
+    ws = _ws_attn.get(device, _stream().value, nbytes)
     return ws.data_ptr(), ws.numel()
 
 
@@ -1703,23 +1557,19 @@ def cross_attention_eq(q, k, vt, num_heads, mode, trace_idx):
 
 # equivariant cross attention of a batch on the bf16 matrix cores at f32 accuracy (SE3_CROSS_EQ=f32 forces the f32 MFMA kernels)
 CROSS_EQ_BF16X6 = os.environ.get('SE3_CROSS_EQ', 'bf16x6') != 'f32'
-_pair_rows_cache = {}
+_pair_row_tables = Derived(64)
 
 
 def _pair_rows(starts, lengths, device):
     """(P * W,) row indices and a (1, P, W, 1) 0/1 mask that cut the packed rows of P clouds into P windows of W rows."""
     key = (tuple(int(s) for s in starts), tuple(int(n) for n in lengths), str(device))
-    hit = _pair_rows_cache.get(key)
+    W = max(key[1])
+    hit = _pair_row_tables.lookup((), key)
     if hit is None:
-        W = max(key[1])
         idx = to_device([s + min(j, n - 1) for s, n in zip(key[0], key[1]) for j in range(W)], torch.int64, device)
         mask = to_device([1.0 if j < n else 0.0 for n in key[1] for j in range(W)], torch.float32, device)
-        hit = (_Shared(idx, mask), W)
-        if len(_pair_rows_cache) > 64:
-            _pair_rows_cache.clear()
-        _pair_rows_cache[key] = hit
-    idx, mask = hit[0].get()
-    return idx, mask.view(1, len(key[1]), hit[1], 1), hit[1]
+        hit = _pair_row_tables.store((), key, (idx, mask))
+    return hit[0], hit[1].view(1, len(key[1]), W, 1), W
 
 
 GRAM_KERNEL = True            # False: index_select + mask + batched library GEMM (A/B runs, tests)
@@ -1796,11 +1646,7 @@ def cross_attention_eq_stack(q, k, vt, q_starts, q_lengths, k_starts, k_lengths,
         # to the f32 kernels by the entry point itself
         stream = _stream()
         ws_bytes = lib().se3_cross_eq_x6_workspace_bytes(A, Rq, k.shape[1], C, vt.stride(1))
-        key = (dev, stream.value, 'x6')
-        ws = _gn_workspace.get(key)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = torch.empty((max(ws_bytes, 1 << 24),), dtype=torch.uint8, device=dev)
-            _gn_workspace[key] = ws
+        ws = _ws_x6.get(dev, stream.value, ws_bytes)
         check(lib().se3_cross_eq_stack_x6_fwd(q.data_ptr(), k.data_ptr(), vt.data_ptr(), _i64_array(q_starts), _i64_array(q_lengths),
                                               _i64_array(k_starts), _i64_array(k_lengths), P, A, C, int(num_heads), Rq, k.shape[1],
                                               q.stride(0), k.stride(0), vt.stride(1), vt.stride(0), 0 if mode == 'a_soft' else 1,
@@ -1821,6 +1667,7 @@ def cross_attention_eq_stack(q, k, vt, q_starts, q_lengths, k_starts, k_lengths,
 _EMB_D_RANGE, _EMB_D_PER_UNIT = 64.0, 64.0        # distance-index table: [0, 64) index units, 64 entries per unit
 _EMB_A_PER_UNIT = 32.0                             # angle-index table: a 32-channel slice (418 entries x 256 B) fits in LDS; Hermite error h^4 / 384 |f''''| ~ 2.5e-9 |f''''|
 _emb_table_cache = {}
+also_clear += [_emb_table_cache.clear, _amax_rings.clear]          # (device-side validation state, a ring cursor: own logic, cleared by clear_caches())
 
 
 def _embedding_table(weight, bias, div_term, x_max, per_unit):
@@ -1861,19 +1708,6 @@ def knn3_stack(points, lengths):
     return knn
 
 
-_emb_ws = {}
-
-
-def _emb_workspace(device, nbytes):
-    """Per-pair record scratch of the embedding kernels, one buffer per launch stream (calls on a stream are ordered)."""
-    key = (device, _stream().value)
-    ws = _emb_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty((max(nbytes, 1 << 24),), dtype=torch.uint8, device=device)
-        _emb_ws[key] = ws
-    return ws
-
-
 def embedding_tables(div_term, w_d, b_d, w_a, b_a, sigma_a):
     """The two validated tables (distance, angle) of a geometric embedding: pass them as `tables=` to several geometric_embedding calls of
     one forward (all clouds of a batch) to validate the weights once instead of once per cloud."""
@@ -1907,7 +1741,7 @@ def geometric_embedding(points, div_term, w_d, b_d, w_a, b_a, sigma_d, sigma_a, 
         eq = torch.empty((A, N, N, 4), dtype=torch.float32, device=points.device)
         wigner_d1 = wigner_d1.detach().contiguous()
     entry = lib().se3_geo_embedding_fwd if dtype == torch.float32 else lib().se3_geo_embedding_bf16_fwd
-    ws = _emb_workspace(points.device, lib().se3_geo_embedding_workspace_bytes(N))
+    ws = _ws_emb.get(points.device, _stream().value, lib().se3_geo_embedding_workspace_bytes(N))
     check(entry(points.data_ptr(), knn.data_ptr(), N, C, tab_d.data_ptr(), tab_d.shape[0], _EMB_D_PER_UNIT, tab_a.data_ptr(),
                 tab_a.shape[0], _EMB_A_PER_UNIT, float(sigma_d), float(sigma_a), w_d.data_ptr(), b_d.data_ptr(), w_a.data_ptr(),
                 b_a.data_ptr(), div_term.data_ptr(), wigner_d1.data_ptr() if eq is not None else None, A, emb.data_ptr(),

@@ -38,7 +38,7 @@ def test_batches_in_flight_give_the_sequential_results(threads, schedule):
     batched.set_schedule(schedule)
     cfg = make_cfg('se3ete')
     model = load_synthetic_weights(create_model(cfg)).cuda().eval()
-    ops.clear_weight_caches()
+    ops.clear_caches()
     builders = [_batch(cfg, 2 * t, 2) for t in range(threads)]
     streams = [torch.cuda.Stream() for _ in range(threads)]
     got, failed = [None] * threads, []

@@ -291,6 +291,49 @@ def test_c_issued_transformer_sees_weights_written_behind_the_version_counter():
         cdriver.ENABLED = saved
 
 
+def test_composed_self_attention_projection_sees_weights_written_behind_the_version_counter():
+    """The composed [q | k | W_p^T q | W_eq^T q] projection of a self-attention layer is a weight-derived cache entry like the f16 pieces:
+    after `proj_q.weight.data.copy_()` (no version bump, same address) validate_weight_caches() must drop it, stacked_projection() must
+    return the composition of the CURRENT weights (q rows: the float32 -> float64 -> float32 round trip of proj_q.weight, exact; qp rows: a
+    float64 library product, held to a fresh composition at 1e-6 of their largest magnitude) and the forward must change."""
+    from se3et_amd import cdriver, functional as SF, ops
+    from se3et_amd.batched import forward_pairs
+    from se3et_amd.data import precompute_data_stack_mode
+    from se3et_amd.model import create_model, load_synthetic_weights, make_cfg
+    from se3et_amd.synthetic import make_pair
+    cfg = make_cfg('se3ete')
+    model = load_synthetic_weights(create_model(cfg)).cuda().eval()
+    b = cfg.backbone
+    ref, src, _ = make_pair('c2_5k', index=0)
+    pts = torch.from_numpy(np.concatenate([ref, src], 0)).cuda()
+
+    def run():
+        dd = precompute_data_stack_mode(pts, torch.tensor([len(ref), len(src)]), b.num_stages, b.init_voxel_size, b.init_radius, cfg.neighbor_limits)
+        dd['features'] = torch.ones((pts.shape[0], 1), device='cuda')
+        return forward_pairs(model, dd)[0]
+
+    tr = model.transformer.transformer
+    att = next(layer for block, layer in zip(tr.blocks, tr.layers) if block.startswith('self')).attention.attention
+    saved = cdriver.ENABLED
+    try:
+        cdriver.ENABLED = True
+        before = run()
+        with torch.no_grad():
+            att.proj_q.weight.data.copy_(att.proj_q.weight.data * 1.5)            # behind the version counter
+        assert ops.validate_weight_caches() >= 1
+        w, _, offs = att.stacked_projection()
+        C = att.proj_q.weight.shape[0]
+        assert torch.equal(w[:C], att.proj_q.weight)
+        fresh = SF.compose_self_attention_weights(att.proj_q.weight, att.proj_q.bias, att.proj_k.weight, att.proj_k.bias, att.proj_p.weight,
+                                                  att.proj_eq.weight if offs['qe'] is not None else None, att.num_heads)[0]
+        qp, qp_fresh = w[offs['qp']:], fresh[offs['qp']:]
+        assert float((qp - qp_fresh).abs().max()) <= 1e-6 * float(qp_fresh.abs().max())
+        got = run()
+        assert not torch.equal(got['ref_feats_c'], before['ref_feats_c'])
+    finally:
+        cdriver.ENABLED = saved
+
+
 @pytest.mark.parametrize('scale', [1e4, 1e-4])
 def test_forward_with_scaled_input_features(scale):
     """un-normalised input features.  The features x s with the first layer's weights / s are the same network: the

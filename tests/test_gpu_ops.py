@@ -915,12 +915,12 @@ def test_weight_caches_survive_writes_behind_the_version_counter():
     assert ops.validate_weight_caches() == 0
     # (a) same address, same shape, same version, another tensor object
     key = (w.data_ptr(), 128, 256, w.stride(0), w.device.index)
-    assert key in ops._linear_piece_cache
-    entry = ops._linear_piece_cache[key]
+    entry = ops._linear_pieces.entry(key)
+    assert entry is not None
     other = torch.nn.Parameter(torch.empty_like(w), requires_grad=False)
     other.data = w.data                          # shares the storage (same data_ptr), its own version counter (0 like w's)
     assert other.data_ptr() == w.data_ptr() and other._version == w._version
-    assert entry[0]() is w and entry[0]() is not other
+    assert entry[0][0] is w and entry[0][0] is not other
     w.data.copy_(w.data * 0.5)                   # stale pieces in the cache now; `other` must not be served them
     y2 = ops.linear_f16(x, other)
     assert float((y2.double() - ref(other)).abs().max()) < 1e-5
@@ -1284,8 +1284,7 @@ def test_union_kpconv_edge_shapes(P, Ns, NN, Cin, Cout, box, clouds):
             assert float((whole - union).abs().max()) <= 5e-6 * float(ref.abs().max())
             assert torch.equal(SF.kpconv_inter_so3(*args).cpu(), union)         # the arrival counters are back at zero
         # the passes of the plan: the dense box of the last case exceeds the cap
-        hit = ops._union_plan_cache.get(ops._stream().value)
-        plan = hit[2].cpu().numpy()
+        plan = ops._union_plans.entry(ops._stream().value)[1].cpu().numpy()
         a16 = lambda v: (v + 15) & ~15
         nsub = plan[a16(G * 64):a16(G * 64) + 4 * G].view(np.int32)
         assert nsub.min() >= 1 and nsub.max() <= 16

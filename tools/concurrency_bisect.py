@@ -75,7 +75,7 @@ def main():
             rec.append(('embedding', sum(chk(o.float()) for o in outs if o is not None)))
             if KEEP:
                 N_ = a[0].shape[0]
-                wsb = ops._emb_ws[(a[0].device, ops._stream().value)][:N_ * N_ * 80].clone()
+                wsb = ops._ws_emb.get(a[0].device, ops._stream().value, N_ * N_ * 80)[:N_ * N_ * 80].clone()
                 tls.embs.append(tuple(None if o is None else o.detach().clone() for o in outs) + (k['knn'].clone(), a[0].clone(), wsb))
         return out
     BT.transformer_pairs, SF.geometric_embedding = transformer_pairs, geometric_embedding
@@ -100,10 +100,10 @@ def main():
         return run
 
     def cold():
-        ops.clear_weight_caches()
-        for d in (ops._gn_workspace, ops._dense_ws, ops._kpconv_split_ws) + (() if state['variant'] == 'warmws' else (ops._emb_ws,)) + (ops._emb_table_cache, ops._neighbor_table_cache,
-                  ops._pair_rows_cache, ops._nonzero_norm_cache, ops._host_table_cache, BT._pack_index_cache, cdriver._ws):
-            d.clear()
+        warm = dict(ops._ws_emb.buffers)
+        ops.clear_caches()
+        if state['variant'] == 'warmws':          # this variant keeps the embedding workspaces of the trial before
+            ops._ws_emb.buffers.update(warm)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
 

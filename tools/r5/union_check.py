@@ -25,8 +25,7 @@ def timeit(f, n=10):
 
 def plan_stats(q, G, NN):
     """sub-tiles per group and union rows, read back from the cached plan of the current stream"""
-    hit = ops._union_plan_cache.get(ops._stream().value)
-    plan = hit[2].cpu().numpy()
+    plan = ops._union_plans.entry(ops._stream().value)[1].cpu().numpy()
     a16 = lambda v: (v + 15) & ~15
     o = a16(G * 64)
     nsub = plan[o:o + 4 * G].view(np.int32)
