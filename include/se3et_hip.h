@@ -111,6 +111,20 @@ int se3_radius_neighbors_grid(const float* q_points, int64_t nq, const int64_t* 
 /* (max_count_is_zero != 0: the caller cleared max_count itself -- e.g. one fill for the counters of all searches of a pyramid -- and the
  * call does not clear it again; the search only ever raises the values.) */
 
+/* Count-only radius search with the histogram of the counts: what the reference's neighbour-limit calibration needs
+ * (geotransformer/utils/data.py:212-252: counts up to hist_n = ceil(4/3 pi (radius / voxel + 1)^3) = 180 / 607, beyond
+ * SE3_MAX_NEIGHBOR_LIMIT -- no list is kept here, so no such cap applies).  For every query, count = the number of support points of the
+ * same batch element with d2 = (dx*dx + dy*dy) + dz*dz < radius*radius (float32, unfused: the test of se3_radius_neighbors; with
+ * q == s the point itself counts).  Cloud b adds into row slot_of_cloud_host[b] of hist (DEVICE int32 (num_slots, hist_n)):
+ * hist[slot][count] += 1 when count < hist_n, dropped[slot] += 1 otherwise (DEVICE int32 (num_slots)); max_count[b] (DEVICE int32
+ * (batch)) is raised to the cloud's largest, uncapped count.  All three are ACCUMULATED: the caller clears them (once for any number of
+ * calls).  Integer-exact and order-independent: the same values run to run, alone or stacked.  grid_workspace: NULL (every support point of
+ * the cloud is tested) or what se3_radius_grid_build made for s_points and this radius.  q_lengths_host / s_lengths_host /
+ * slot_of_cloud_host are HOST arrays of `batch` entries; 1 <= hist_n <= 4096, batch <= SE3_MAX_BATCH, slots in [0, num_slots). */
+int se3_radius_count_hist(const float* q_points, int64_t nq, const float* s_points, int64_t ns, const int64_t* q_lengths_host,
+                          const int64_t* s_lengths_host, int batch, float radius, const void* grid_workspace, int hist_n,
+                          const int* slot_of_cloud_host, int num_slots, int32_t* hist, int32_t* dropped, int32_t* max_count, void* stream);
+
 /* ---- A2, exact ties: the reference's order of exactly tied distances (round 6; csrc/radius_ties.hip) ----------------------------------
  * The reference's row is the head of ALL in-radius matches in the order of its k-d tree walk, std::sort-ed (unstable) on the distance alone
  * (extensions/extra/nanoflann/nanoflann.hpp:857-1002,1286-1287,1348-1407; cpu/radius_neighbors/radius_neighbors_cpu.cpp:29-90): which
@@ -813,6 +827,11 @@ int se3_grid_subsample_host(const float* points, const float* normals, int64_t n
                             float* s_points, float* s_normals, int64_t* s_lengths);
 int se3_radius_neighbors_host(const float* q_points, int64_t nq, const float* s_points, int64_t ns, const int64_t* q_lengths,
                               const int64_t* s_lengths, int batch, float radius, int64_t limit, int64_t* out, int64_t* max_count);
+/* se3_radius_count_hist on HOST memory (every pointer host; same contract, same numbers): a cell list of its own, linear in the points.
+ * The queries of a cloud are shared among SE3_HOST_THREADS threads (environment, default 1). */
+int se3_radius_count_hist_host(const float* q_points, int64_t nq, const float* s_points, int64_t ns, const int64_t* q_lengths,
+                               const int64_t* s_lengths, int batch, float radius, int hist_n, const int* slot_of_cloud, int num_slots,
+                               int32_t* hist, int32_t* dropped, int32_t* max_count);
 
 /* ---- round 4: the remaining library products of the inference forward as kernels --------------------------------------------------------
  * se3_patch_scores   experiments/se3ete.3dmatch/model.py:186-203 -- the fine-matching score matrices of all patch pairs with the two feature

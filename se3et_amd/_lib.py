@@ -32,6 +32,7 @@ SIGNATURES = {
     'se3_radius_neighbors_grid': (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _f32, _i32, _vp, _vp, _i32, _vp]),
     'se3_radius_neighbors_ties': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'se3_radius_neighbors_grid_ties': (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _f32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'se3_radius_count_hist': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     'se3_kdtree_max_bytes': (_sz, [_i64, _i32]),
     'se3_kdtree_build_host': (_i32, [_vp, _i64, _vp, _i32, _vp, _sz, _vp]),
     'se3_radius_tie_scratch_bytes': (_sz, [_i64, _i32]),
@@ -161,6 +162,7 @@ SIGNATURES = {
     'se3_grid_subsample_host': (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp]),
     'se3_neighbor_table_trim': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     'se3_radius_neighbors_host': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _i64, _vp, _vp]),
+    'se3_radius_count_hist_host': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _vp, _i32, _vp, _vp, _vp]),
     'se3_log_sinkhorn_fwd': (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     'se3_log_sinkhorn_bwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
 }

@@ -135,3 +135,144 @@ extern "C" int se3_radius_neighbors_host(const float* q_points, int64_t nq, cons
   *max_count = mc;
   return SE3_OK;
 }
+
+// ---- count-only search on host memory (neighbour-limit calibration; the device form: csrc/radius_neighbors.hip) --------------------------
+// Per query only the NUMBER of support points with d2 < r^2 is wanted, so no tree and no sort: the finite support points of a cloud are
+// binned into cells of edge > radius (counting sort) and a query tests the points of the 3 x 3 x 3 cells around it with the search's float
+// arithmetic.  A cell walk only ever skips points further than a cell edge away, so the counts equal the exhaustive scan's.  Points with a
+// non-finite coordinate are never within a radius of anything (their d2 is inf or NaN) and are left out of the cells.
+#include <stdlib.h>
+#include <thread>
+namespace {
+
+constexpr int kHostGridCap = 128;                  // cells per axis at most
+constexpr int kHostMaxHistBins = 4096;             // as the device entry
+
+struct CountCells {
+  double org[3], inv_cell;
+  int dim[3];
+  std::vector<int> start;                          // (cells + 1) offsets into xyz
+  std::vector<float> xyz;                          // the binned points, cell by cell
+
+  CountCells(const float* s, int64_t ns, float radius) {
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    int64_t kept = 0;
+    auto finite = [&](int64_t i) { return isfinite(s[3 * i]) && isfinite(s[3 * i + 1]) && isfinite(s[3 * i + 2]); };
+    for (int64_t i = 0; i < ns; i++) {
+      if (!finite(i)) continue;
+      for (int d = 0; d < 3; d++) {
+        const double v = s[3 * i + d];
+        if (kept == 0 || v < lo[d]) lo[d] = v;
+        if (kept == 0 || v > hi[d]) hi[d] = v;
+      }
+      kept++;
+    }
+    double ext = 0;
+    for (int d = 0; d < 3; d++) ext = std::max(ext, hi[d] - lo[d]);
+    const double cell = std::max(std::max((double)fabsf(radius), ext / (kHostGridCap - 1)), 1e-20) * 1.0001;
+    inv_cell = 1.0 / cell;
+    int cells = 1;
+    for (int d = 0; d < 3; d++) {
+      org[d] = lo[d];
+      dim[d] = std::min(kHostGridCap, std::max(1, (int)floor((hi[d] - lo[d]) * inv_cell) + 1));
+      cells *= dim[d];
+    }
+    start.assign((size_t)cells + 1, 0);
+    std::vector<int> cell_of((size_t)ns, -1);
+    for (int64_t i = 0; i < ns; i++) {
+      if (!finite(i)) continue;
+      int c[3];
+      for (int d = 0; d < 3; d++) c[d] = std::min(dim[d] - 1, std::max(0, (int)floor((s[3 * i + d] - org[d]) * inv_cell)));
+      cell_of[(size_t)i] = c[0] + dim[0] * (c[1] + dim[1] * c[2]);
+      start[(size_t)cell_of[(size_t)i] + 1]++;
+    }
+    for (int c = 0; c < cells; c++) start[(size_t)c + 1] += start[(size_t)c];
+    std::vector<int> fill(start.begin(), start.end() - 1);
+    xyz.resize((size_t)kept * 3);
+    for (int64_t i = 0; i < ns; i++) {
+      if (cell_of[(size_t)i] < 0) continue;
+      const size_t o = (size_t)fill[(size_t)cell_of[(size_t)i]]++;
+      for (int d = 0; d < 3; d++) xyz[3 * o + d] = s[3 * i + d];
+    }
+  }
+
+  int count(const float* q, float r2) const {
+    if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) return 0;
+    int c[3];
+    for (int d = 0; d < 3; d++) c[d] = (int)std::min((double)dim[d] + 1, std::max(-2.0, floor((q[d] - org[d]) * inv_cell)));
+    const int x0 = std::max(c[0] - 1, 0), x1 = std::min(c[0] + 1, dim[0] - 1);
+    if (x0 > x1) return 0;
+    int n = 0;
+    for (int z = std::max(c[2] - 1, 0); z <= std::min(c[2] + 1, dim[2] - 1); z++)
+      for (int y = std::max(c[1] - 1, 0); y <= std::min(c[1] + 1, dim[1] - 1); y++) {
+        const size_t row = (size_t)dim[0] * ((size_t)y + (size_t)dim[1] * (size_t)z);
+        for (int k = start[row + (size_t)x0]; k < start[row + (size_t)x1 + 1]; k++) {
+          // unfused float32 (this file is compiled with -ffp-contract=off), the association of the searches
+          const float dx = q[0] - xyz[3 * (size_t)k], dy = q[1] - xyz[3 * (size_t)k + 1], dz = q[2] - xyz[3 * (size_t)k + 2];
+          const float d2 = (dx * dx + dy * dy) + dz * dz;
+          n += d2 < r2 ? 1 : 0;
+        }
+      }
+    return n;
+  }
+};
+
+int host_threads() {                               // SE3_HOST_THREADS (default 1: DataLoader workers are processes of their own)
+  const char* e = getenv("SE3_HOST_THREADS");
+  const int n = e ? atoi(e) : 1;
+  return n < 1 ? 1 : (n > 64 ? 64 : n);
+}
+
+}  // namespace
+
+extern "C" int se3_radius_count_hist_host(const float* q_points, int64_t nq, const float* s_points, int64_t ns, const int64_t* q_lengths,
+                                          const int64_t* s_lengths, int batch, float radius, int hist_n, const int* slot_of_cloud,
+                                          int num_slots, int32_t* hist, int32_t* dropped, int32_t* max_count) {
+  SE3_REQUIRE(batch >= 1 && batch <= SE3_MAX_BATCH, SE3_ERR_INVALID_ARG, "radius_count_hist_host: batch %d not in [1,%d]", batch, SE3_MAX_BATCH);
+  SE3_REQUIRE(hist_n >= 1 && hist_n <= kHostMaxHistBins, SE3_ERR_UNSUPPORTED, "radius_count_hist_host: hist_n %d not in [1,%d]", hist_n,
+              kHostMaxHistBins);
+  SE3_REQUIRE(q_points && s_points && q_lengths && s_lengths && slot_of_cloud && hist && dropped && max_count, SE3_ERR_INVALID_ARG,
+              "radius_count_hist_host: null pointer");
+  SE3_REQUIRE(num_slots >= 1, SE3_ERR_INVALID_ARG, "radius_count_hist_host: num_slots %d", num_slots);
+  int64_t q0 = 0, s0 = 0;
+  for (int b = 0; b < batch; b++) {
+    SE3_REQUIRE(slot_of_cloud[b] >= 0 && slot_of_cloud[b] < num_slots, SE3_ERR_INVALID_ARG,
+                "radius_count_hist_host: slot %d of cloud %d not in [0,%d)", slot_of_cloud[b], b, num_slots);
+    SE3_REQUIRE(q_lengths[b] >= 0 && s_lengths[b] >= 0, SE3_ERR_INVALID_ARG, "radius_count_hist_host: negative length");
+    q0 += q_lengths[b];
+    s0 += s_lengths[b];
+  }
+  SE3_REQUIRE(q0 == nq && s0 == ns, SE3_ERR_INVALID_ARG, "radius_count_hist_host: lengths do not sum to the sizes");
+  const float r2 = radius * radius;
+  const int threads = host_threads();
+  q0 = s0 = 0;
+  for (int b = 0; b < batch; b++) {
+    const int64_t qn = q_lengths[b];
+    const CountCells cells(s_points + 3 * s0, s_lengths[b], radius);
+    const float* q = q_points + 3 * q0;
+    // every thread a contiguous share of the queries and a histogram of its own (hist_n bins, dropped, largest count), added up in order
+    const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(threads, qn / 256));
+    std::vector<std::vector<int32_t>> local((size_t)parts, std::vector<int32_t>((size_t)hist_n + 2, 0));
+    auto work = [&](int t) {
+      std::vector<int32_t>& h = local[(size_t)t];
+      for (int64_t i = qn * t / parts; i < qn * (t + 1) / parts; i++) {
+        const int c = r2 > 0.f ? cells.count(q + 3 * i, r2) : 0;
+        h[(size_t)(c < hist_n ? c : hist_n)]++;
+        if (c > h[(size_t)hist_n + 1]) h[(size_t)hist_n + 1] = c;
+      }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < parts; t++) pool.emplace_back(work, t);
+    work(0);
+    for (std::thread& t : pool) t.join();
+    int32_t* row = hist + (size_t)slot_of_cloud[b] * hist_n;
+    for (const std::vector<int32_t>& h : local) {
+      for (int i = 0; i < hist_n; i++) row[i] += h[(size_t)i];
+      dropped[slot_of_cloud[b]] += h[(size_t)hist_n];
+      max_count[b] = std::max(max_count[b], h[(size_t)hist_n + 1]);
+    }
+    q0 += qn;
+    s0 += s_lengths[b];
+  }
+  return SE3_OK;
+}

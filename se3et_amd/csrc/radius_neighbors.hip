@@ -574,3 +574,207 @@ extern "C" int se3_neighbor_table_trim(const int64_t* full, int64_t rows, int fu
   return SE3_OK;
 }
 
+
+// =====================================================================================================================
+// Count-only search (neighbour-limit calibration, geotransformer/utils/data.py:212-252).  The calibration needs, per query, only the
+// NUMBER of in-radius support points -- up to hist_n = 180 (3DMatch) or 607 (KITTI) of them, far beyond the one-entry-per-lane list of the
+// searches above -- and of those numbers only the histogram.  So the sorted list, the insertion loop, the tie flags and the (Nq, limit)
+// table all disappear: every lane adds up its own hits, one wave reduction per query gives the count, and the counts of a workgroup go into
+// an LDS histogram that is flushed once, with one integer atomicAdd per non-zero bin.  Distance arithmetic and the strict d2 < r2 test are
+// those of the search kernels; integer adds commute, so the result does not depend on the launch geometry, the run, or what else is stacked.
+// =====================================================================================================================
+namespace {
+
+constexpr int kCountQPW = 8;                        // queries per wave, exhaustive form (no list to keep: twice the search's)
+constexpr int kCountQPB = kWaves * kCountQPW;
+constexpr int kGridCountQPW = 8;                    // queries a wave handles one after the other, grid form
+constexpr int kGridCountQPB = 4 * kGridCountQPW;
+constexpr int kMaxHistBins = 4096;                  // 16 KB of LDS
+
+struct SlotTable {
+  int slot[SE3_MAX_BATCH];                          // histogram row of every cloud
+};
+
+// LDS layout of both kernels: hist_n bins, then the number of dropped queries (count >= hist_n), then the largest count
+__device__ __forceinline__ void count_note(int* lds, int hist_n, int count) {
+  atomicAdd(&lds[count < hist_n ? count : hist_n], 1);
+  atomicMax(&lds[hist_n + 1], count);
+}
+
+__device__ __forceinline__ void count_flush(const int* lds, int hist_n, int32_t* __restrict__ hist_row, int32_t* __restrict__ dropped,
+                                            int32_t* __restrict__ max_count) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < hist_n; i += blockDim.x) {
+    const int v = lds[i];
+    if (v != 0) atomicAdd(hist_row + i, v);
+  }
+  if (threadIdx.x == 0) {
+    if (lds[hist_n] != 0) atomicAdd(dropped, lds[hist_n]);
+    // (the running maximum is monotonic: a plain, possibly stale read filters almost every atomic, as in the search kernels)
+    if (lds[hist_n + 1] > __atomic_load_n(max_count, __ATOMIC_RELAXED)) atomicMax(max_count, lds[hist_n + 1]);
+  }
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__global__ __launch_bounds__(kWaves* SE3_WAVE) void radius_count_kernel(const float* __restrict__ q, const float* __restrict__ s, BatchTable bt,
+                                                                       SlotTable slots, float r2, int hist_n, int32_t* __restrict__ hist,
+                                                                       int32_t* __restrict__ dropped, int32_t* __restrict__ max_count) {
+  __shared__ float sx[kTile], sy[kTile], sz[kTile];
+  extern __shared__ int count_lds[];
+  const int b = blockIdx.y;
+  const int64_t qn = bt.q_count[b], sn = bt.s_count[b];
+  const int64_t q0 = bt.q_start[b], s0 = bt.s_start[b];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t qbase = (int64_t)blockIdx.x * kCountQPB + wave * kCountQPW;
+  if ((int64_t)blockIdx.x * kCountQPB >= qn) return;
+  for (int i = threadIdx.x; i < hist_n + 2; i += kWaves * SE3_WAVE) count_lds[i] = 0;
+
+  float qx[kCountQPW], qy[kCountQPW], qz[kCountQPW];
+  int count[kCountQPW];
+#pragma unroll
+  for (int j = 0; j < kCountQPW; j++) {
+    const int64_t qi = qbase + j;
+    const int64_t g = q0 + (qi < qn ? qi : 0);
+    qx[j] = q[3 * g + 0];
+    qy[j] = q[3 * g + 1];
+    qz[j] = q[3 * g + 2];
+    count[j] = 0;
+  }
+
+  for (int64_t t0 = 0; t0 < sn; t0 += kTile) {
+    const int tn = (int)((sn - t0) < kTile ? (sn - t0) : kTile);
+    __syncthreads();
+    for (int e = threadIdx.x; e < 3 * tn; e += kWaves * SE3_WAVE) {
+      float v = s[3 * (s0 + t0) + e];
+      int p = e / 3, c = e - 3 * p;
+      (c == 0 ? sx : (c == 1 ? sy : sz))[p] = v;
+    }
+    __syncthreads();
+    for (int base = 0; base < tn; base += SE3_WAVE) {
+      const int p = base + lane;
+      const bool valid = p < tn;
+      const float px = valid ? sx[p] : 0.f, py = valid ? sy[p] : 0.f, pz = valid ? sz[p] : 0.f;
+#pragma unroll
+      for (int j = 0; j < kCountQPW; j++) {
+        // unfused float32, nanoflann association order: ((dx*dx) + dy*dy) + dz*dz with d = query - support
+        const float dx = __fsub_rn(qx[j], px), dy = __fsub_rn(qy[j], py), dz = __fsub_rn(qz[j], pz);
+        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        count[j] += (valid && (d2 < r2)) ? 1 : 0;
+      }
+    }
+  }
+
+  __syncthreads();                                  // (the cleared histogram, also when the support is empty)
+#pragma unroll
+  for (int j = 0; j < kCountQPW; j++) {
+    const int c = wave_sum_int(count[j]);
+    if (lane == 0 && qbase + j < qn) count_note(count_lds, hist_n, c);
+  }
+  count_flush(count_lds, hist_n, hist + (size_t)slots.slot[b] * hist_n, dropped + slots.slot[b], max_count + b);
+}
+
+// cell coordinate of a QUERY: not clamped to the grid (a query outside the support box still has to see the boundary cells), but kept
+// within two cells of it so that a far-away, infinite or NaN coordinate stays an int (it sees no cell, or cells that hold no hit)
+__device__ __forceinline__ int query_cell(float v, float org, float inv_cell, int dim) {
+  return (int)fminf(fmaxf(floorf((v - org) * inv_cell), -2.f), (float)(dim + 1));
+}
+
+// the 27-cell walk of radius_grid_search_kernel, counting only; a wave takes kGridCountQPW queries one after the other
+__global__ __launch_bounds__(256) void radius_grid_count_kernel(const float* __restrict__ q, BatchTable bt, SlotTable slots, GridLayout G, float r2,
+                                                                int hist_n, int32_t* __restrict__ hist, int32_t* __restrict__ dropped,
+                                                                int32_t* __restrict__ max_count) {
+  extern __shared__ int count_lds[];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int64_t qn = bt.q_count[b];
+  const int64_t first = (int64_t)blockIdx.x * kGridCountQPB;
+  if (first >= qn) return;
+  for (int i = threadIdx.x; i < hist_n + 2; i += 256) count_lds[i] = 0;
+  __syncthreads();
+  const GridMeta m = G.meta[b];
+  const int* cs = G.cell_start + (size_t)b * (kCellCap + 1);
+  const float4* pts = G.sorted + bt.s_start[b];
+  for (int j = 0; j < kGridCountQPW; j++) {
+    const int64_t qi = first + (threadIdx.x >> 6) * kGridCountQPW + j;        // (the same for all lanes of the wave)
+    if (qi >= qn) break;
+    const int64_t gq = bt.q_start[b] + qi;
+    const float qx = q[3 * gq], qy = q[3 * gq + 1], qz = q[3 * gq + 2];
+    const int cx = query_cell(qx, m.org[0], m.inv_cell, m.dim[0]), cy = query_cell(qy, m.org[1], m.inv_cell, m.dim[1]),
+              cz = query_cell(qz, m.org[2], m.inv_cell, m.dim[2]);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, m.dim[0] - 1);
+    int beg = 0, len = 0;
+    if (lane < 9 && x0 <= x1) {
+      const int z = cz + lane / 3 - 1, y = cy + lane % 3 - 1;
+      if (z >= 0 && z < m.dim[2] && y >= 0 && y < m.dim[1]) {
+        const int rowc = m.dim[0] * (y + m.dim[1] * z);
+        beg = cs[rowc + x0];
+        len = cs[rowc + x1 + 1] - beg;
+      }
+    }
+    int rb[9], ro[9], total = 0;
+#pragma unroll
+    for (int r = 0; r < 9; r++) {
+      rb[r] = __builtin_amdgcn_readlane(beg, r);
+      ro[r] = total;                                       // exclusive offset of run r in the flat list
+      total += __builtin_amdgcn_readlane(len, r);
+    }
+    int count = 0;
+    for (int base = 0; base < total; base += 64) {
+      const int t = base + lane;
+      const bool valid = t < total;
+      int p = 0;
+#pragma unroll
+      for (int r = 0; r < 9; r++) p = (t >= ro[r]) ? rb[r] + (t - ro[r]) : p;
+      const float4 c = valid ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float dx = __fsub_rn(qx, c.x), dyv = __fsub_rn(qy, c.y), dzv = __fsub_rn(qz, c.z);
+      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dyv, dyv)), __fmul_rn(dzv, dzv));
+      count += (valid && (d2 < r2)) ? 1 : 0;
+    }
+    count = wave_sum_int(count);
+    if (lane == 0) count_note(count_lds, hist_n, count);
+  }
+  count_flush(count_lds, hist_n, hist + (size_t)slots.slot[b] * hist_n, dropped + slots.slot[b], max_count + b);
+}
+
+}  // namespace
+
+extern "C" int se3_radius_count_hist(const float* q_points, int64_t nq, const float* s_points, int64_t ns, const int64_t* q_lengths_host,
+                                     const int64_t* s_lengths_host, int batch, float radius, const void* grid_workspace, int hist_n,
+                                     const int* slot_of_cloud_host, int num_slots, int32_t* hist, int32_t* dropped, int32_t* max_count,
+                                     void* stream) {
+  SE3_REQUIRE(batch >= 1 && batch <= SE3_MAX_BATCH, SE3_ERR_INVALID_ARG, "radius_count_hist: batch %d not in [1,%d]", batch, SE3_MAX_BATCH);
+  SE3_REQUIRE(hist_n >= 1 && hist_n <= kMaxHistBins, SE3_ERR_UNSUPPORTED, "radius_count_hist: hist_n %d not in [1,%d]", hist_n, kMaxHistBins);
+  SE3_REQUIRE(q_points && s_points && q_lengths_host && s_lengths_host && slot_of_cloud_host && hist && dropped && max_count,
+              SE3_ERR_INVALID_ARG, "radius_count_hist: null pointer");
+  SE3_REQUIRE(num_slots >= 1, SE3_ERR_INVALID_ARG, "radius_count_hist: num_slots %d", num_slots);
+  SE3_REQUIRE(ns < (1ll << 31), SE3_ERR_UNSUPPORTED, "radius_count_hist: support size %lld too large", (long long)ns);
+  SlotTable slots{};
+  for (int b = 0; b < batch; b++) {
+    SE3_REQUIRE(slot_of_cloud_host[b] >= 0 && slot_of_cloud_host[b] < num_slots, SE3_ERR_INVALID_ARG,
+                "radius_count_hist: slot %d of cloud %d not in [0,%d)", slot_of_cloud_host[b], b, num_slots);
+    slots.slot[b] = slot_of_cloud_host[b];
+  }
+  BatchTable bt;
+  int64_t qmax, smax;
+  SE3_REQUIRE(fill_batch_table(&bt, q_lengths_host, s_lengths_host, batch, nq, ns, &qmax, &smax) == 0, SE3_ERR_INVALID_ARG,
+              "radius_count_hist: lengths do not sum to the sizes");
+  if (nq == 0) return SE3_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = sizeof(int) * (size_t)(hist_n + 2);
+  if (grid_workspace != nullptr) {
+    GridLayout G;
+    grid_carve(ns, batch, (char*)grid_workspace, &G);
+    dim3 grid((unsigned)se3_cdiv(qmax, kGridCountQPB), (unsigned)batch);
+    radius_grid_count_kernel<<<grid, 256, lds, st>>>(q_points, bt, slots, G, radius * radius, hist_n, hist, dropped, max_count);
+  } else {
+    dim3 grid((unsigned)se3_cdiv(qmax, kCountQPB), (unsigned)batch);
+    radius_count_kernel<<<grid, kWaves * SE3_WAVE, lds, st>>>(q_points, s_points, bt, slots, radius * radius, hist_n, hist, dropped, max_count);
+  }
+  SE3_CHECK_LAUNCH("radius_count_hist");
+  return SE3_OK;
+}
