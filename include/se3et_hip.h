@@ -45,18 +45,6 @@ extern "C" {
 /* Library / build identification. */
 const char* se3_version(void);
 const char* se3_last_error(void);   /* text of the last failure on the calling thread */
-/* Benchmark tuning / profiling hooks (process-global, defaults 0; every variant computes the same result): kernel variant + workgroups per
- * CU of the relative-position kernel (3 = exact f32 MFMAs instead of the f16 hi / lo split); variant of the attention kernel (5 = f16-split
- * flash loop, 6 / 7 two waves per workgroup, 8 / 10 one wave); variant 9 writes 32 clock64() stamps per wave to `stamps`. */
-void se3_debug_set_bias_variant(int variant, int split);
-void se3_debug_set_attention_variant(int variant);
-void se3_debug_set_attention_profile(long long* stamps);
-/* Variant bits of the fused KPConv kernel (se3_kpconv_so3_fused): 1 = consecutive 16-point tiles on ONE XCD (workgroup i runs on XCD i mod 8:
- * tile = start of that XCD's contiguous tile range + i / 8) instead of tile = workgroup index -- for row orders with spatial locality. */
-void se3_debug_set_kpconv_variant(int variant);
-/* Diagnostic bits of se3_kpconv_so3_union (timing only: results are wrong with any bit set): 1 producers skip the gather product, 2 the row loads,
- * 4 the A fragments; 8 consumers skip their MFMAs. */
-void se3_debug_set_kpconv_union_variant(int variant);
 /* se3_log_sinkhorn_fwd: 0 = the iteration in base 2 with the previous iteration's logsumexp as the shift (default), 1 = natural base with the exact
  * maximum in every pass (the reference's order of operations) -- A/B runs. */
 void se3_debug_set_sinkhorn_variant(int variant);
@@ -70,12 +58,11 @@ unsigned long long se3_debug_dense_saturated_rows(int reset);
  * (csrc/attention.hip: x6_split_kernel).  A non-zero count says the input already held NaN / Inf. */
 unsigned long long se3_debug_attention_saturated(int reset);
 /* Per-launch timing of the two RPE self-attention kernels (bench.py): while enabled every launch carries its own start / stop
- * HIP event pair (hipExtLaunchKernelGGL) on the launch stream; collect() waits for them, returns the count and fills the
- * durations (us) and tags (1 = relative-position logits kernel, 2 = attention kernel) in launch order. */
+ * HIP event pair (hipExtLaunchKernelGGL) on the launch stream; collect_ex() waits for them, returns the count and fills the
+ * durations (us) and tags (1 = relative-position logits kernel, 2 = attention kernel) in launch order, plus per record the algorithmic bytes
+ * of the call (negative = equivariant call) for the logits launches (tag 1) of se3_rpe_self_attention_stack*_fwd and 0 for every
+ * other launch. */
 void se3_debug_kernel_timing(int enable);
-int se3_debug_kernel_timing_collect(float* microseconds, int* tags, int capacity);
-/* The same, plus per record the algorithmic bytes of the call (negative = equivariant call) for the logits launches (tag 1) of
- * se3_rpe_self_attention_stack*_fwd and 0 for every other launch. */
 int se3_debug_kernel_timing_collect_ex(float* microseconds, int* tags, double* aux, int capacity);
 
 /* ---- A2: stack-mode radius neighbour search ---------------------------------------------------------------
@@ -279,8 +266,6 @@ int se3_linear_stream(const float* x, int64_t rows, int in_features, int64_t x_r
                       int out_features, int apply_relu, float* out, int64_t out_row_stride, void* stream);
 int se3_linear_stream_transposed(const float* x, int64_t rows, int in_features, int64_t x_row_stride, const void* weight_pieces,
                                  const float* bias, int out_features, int block_rows, float* out_t, int64_t ld, void* stream);
-/* Tuning hook (tools/micro): workgroups se3_dense_norm_fwd aims at (default 768 = 3 per compute unit, all resident at once). */
-void se3_dense_norm_set_target_chunks(int workgroups);
 
 /* ---- D6: LayerNorm(hidden + residual) ---------------------------------------------------------------------------
  * Replaces the residual + nn.LayerNorm tails of geotransformer/modules/transformer/rpe_transformer.py:163-164,

@@ -15,16 +15,10 @@ _vp, _i64, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctyp
 SIGNATURES = {
     'se3_version': (ctypes.c_char_p, []),
     'se3_last_error': (ctypes.c_char_p, []),
-    'se3_debug_set_bias_variant': (None, [_i32, _i32]),
-    'se3_debug_set_attention_variant': (None, [_i32]),
-    'se3_debug_set_kpconv_variant': (None, [_i32]),
-    'se3_debug_set_kpconv_union_variant': (None, [_i32]),
     'se3_debug_set_sinkhorn_variant': (None, [_i32]),
     'se3_debug_dense_saturated_rows': (ctypes.c_uint64, [_i32]),
     'se3_debug_attention_saturated': (ctypes.c_uint64, [_i32]),
-    'se3_debug_set_attention_profile': (None, [_vp]),
     'se3_debug_kernel_timing': (None, [_i32]),
-    'se3_debug_kernel_timing_collect': (_i32, [_vp, _vp, _i32]),
     'se3_debug_kernel_timing_collect_ex': (_i32, [_vp, _vp, _vp, _i32]),
     'se3_radius_neighbors': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp]),
     'se3_radius_grid_workspace_bytes': (_sz, [_i64, _i32]),
@@ -63,7 +57,6 @@ SIGNATURES = {
     'se3_transformer_workspace_bytes': (_sz, [_vp]),
     'se3_transformer_plan_layout': (None, [_vp]),
     'se3_transformer_forward': (_i32, [_vp, _vp, _vp, _vp, _sz, _vp]),
-    'se3_dense_norm_set_target_chunks': (None, [_i32]),
     'se3_linear_weight_pieces_bytes': (_sz, [_i32, _i32]),
     'se3_linear_split_weights_f16': (_i32, [_vp, _i32, _i32, _vp, _vp]),
     'se3_linear_f16': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

@@ -112,11 +112,12 @@ constexpr int kStageStride = 36;     // floats per staged logits row (32 keys + 
 // queries split once when they are staged in LDS, the embedding values in registers right behind their load -- three products
 // hi hi + hi lo + lo hi in f32 (2^-22 per term: 1e-6 on logits of magnitude 4).  A lane's two float4 of a 32-channel step are not
 // consecutive channels; the A fragments are staged with the same permutation of the K index.
-// TL (round 4, with HS): the embedding tile is REQUESTED with four adjacent lanes on one key's 64 contiguous bytes (lane l: key l >> 2,
+// Since round 4 the HS form REQUESTS the embedding tile with four adjacent lanes on one key's 64 contiguous bytes (lane l: key l >> 2,
 // 16-byte piece l & 3) instead of the MFMA operand's own order (key l & 15, piece l >> 4: the four lanes of a 64-byte segment 16 lanes apart,
-// every quarter-wave of a load touching 16 different cache lines), and brought into operand order through a wave-private LDS block right
-// before its use (ds_write_b128 / ds_read_b128 of one wave complete in order: no barrier).
-template <int CT, int RT, bool NEXT, bool EQ, bool UA, bool BF, bool HS = false, bool TL = false>
+// every quarter-wave of a load touching 16 different cache lines), and brings it into operand order through a wave-private LDS block right
+// before its use (ds_write_b128 / ds_read_b128 of one wave complete in order: no barrier).  (Requests in operand order, the round-3 form of HS, went
+// with the tuning variants.)
+template <int CT, int RT, bool NEXT, bool EQ, bool UA, bool BF, bool HS = false>
 __device__ __forceinline__ void bias_tile(float4 (&b)[BF ? CT / 2 : CT], const float4* afrag, const float4* qe_s, float* stage,
                                           int col0, const float* Erow, const float* eq_row, unsigned eq_anchor_stride, int tile,
                                           int next_tile, int M, int AH, int H, float4* tbuf = nullptr, float inv_qs = 1.f) {
@@ -126,7 +127,7 @@ __device__ __forceinline__ void bias_tile(float4 (&b)[BF ? CT / 2 : CT], const f
   const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
   asm volatile("" ::: "memory");        // keeps the LDS fragment reads inside the tile loop (otherwise hoisted and spilled)
   const int m = (tile << 4) + col;
-  const float* Enext = TL ? Erow + ((unsigned)min((next_tile << 4) + (lane >> 2), M - 1) * CE + 4 * (lane & 3))
+  const float* Enext = HS ? Erow + ((unsigned)min((next_tile << 4) + (lane >> 2), M - 1) * CE + 4 * (lane & 3))
                           : Erow + ((unsigned)min((next_tile << 4) + col, M - 1) * CE + 4 * kq);     // chunk t at +16 t (immediate)
   float4 e4[RT];
   if (EQ && UA) {
@@ -149,13 +150,11 @@ __device__ __forceinline__ void bias_tile(float4 (&b)[BF ? CT / 2 : CT], const f
         ah[rt] = afrag[(rt * KT + j) * 64 + lane];
         al[rt] = afrag[((RT + rt) * KT + j) * 64 + lane];
       }
-      float4 b0 = b[2 * j], b1 = b[2 * j + 1];
-      if (TL) {      // request order (key l >> 2, piece l & 3) -> operand order (key l & 15, piece l >> 4); rows 5 float4 apart (80 B)
-        tbuf[(lane >> 2) * 5 + (lane & 3)] = b0;
-        tbuf[80 + (lane >> 2) * 5 + (lane & 3)] = b1;
-        b0 = tbuf[col * 5 + kq];
-        b1 = tbuf[80 + col * 5 + kq];
-      }
+      // request order (key l >> 2, piece l & 3) -> operand order (key l & 15, piece l >> 4); rows 5 float4 apart (80 B)
+      tbuf[(lane >> 2) * 5 + (lane & 3)] = b[2 * j];
+      tbuf[80 + (lane >> 2) * 5 + (lane & 3)] = b[2 * j + 1];
+      const float4 b0 = tbuf[col * 5 + kq];
+      const float4 b1 = tbuf[80 + col * 5 + kq];
       uint2 h0, l0, h1, l1;
       split_f16x4(b0, h0, l0);
       split_f16x4(b1, h1, l1);
@@ -232,7 +231,7 @@ __device__ __forceinline__ void bias_tile(float4 (&b)[BF ? CT / 2 : CT], const f
 // range [w U / G, (w+1) U / G) and walks it row segment by row segment (the folded queries of the segment's row are staged
 // in LDS in MFMA-fragment order); inside a segment the 4 waves stride over the units.  A unit = two 16-key tiles whose
 // logits are collected in a wave-private LDS block and written out as full 128-byte row segments (float4 per lane).
-template <int CT, int RT, int MINW, bool EQ, bool UA, bool BF = false, bool HS = false, bool TL = false>
+template <int CT, int RT, int MINW, bool EQ, bool UA, bool BF = false, bool HS = false>
 __global__ __launch_bounds__(256, MINW) void rpe_bias_kernel(const float* __restrict__ qp, const float* __restrict__ qe,
                                                              int qp_rs, long long qp_sa, Stack S, int AH, int H,
                                                              float* __restrict__ bias) {
@@ -241,7 +240,7 @@ __global__ __launch_bounds__(256, MINW) void rpe_bias_kernel(const float* __rest
   __shared__ float4 afrag[RT * CT * 64];                    // bf16: hi fragments, then lo fragments (same size)
   __shared__ float4 qe_s[32];
   __shared__ __attribute__((aligned(16))) float stage_s[4 * RT * 16 * kStageStride];
-  __shared__ float4 tbuf_s[TL ? 4 * 160 : 1];                 // TL: per wave two 16-row blocks of 80 bytes per row
+  __shared__ float4 tbuf_s[HS ? 4 * 160 : 1];                 // HS: per wave two 16-row blocks of 80 bytes per row
   // Round 5, late (the logits kernel's half): the folded queries of a query point are scaled by ONE power of two
   // before their f16 / bf16 split -- the largest magnitude over the point's (anchor, head) rows goes to [2^6, 2^7) unless it already lies in
   // [2^-4, 2^7) (then nothing changes: bit-identical) -- and the logits are scaled back in the tile epilogue: no overflow to Inf above 65504,
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(256, MINW) void rpe_bias_kernel(const float* __rest
   int seg_parity = 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
   float* stage = stage_s + wave * (RT * 16 * kStageStride);
-  float4* tbuf = tbuf_s + (TL ? wave * 160 : 0);
+  float4* tbuf = tbuf_s + (HS ? wave * 160 : 0);
   int f = (int)((long long)blockIdx.x * S.total_units / gridDim.x);
   const int f_end = (int)((long long)(blockIdx.x + 1) * S.total_units / gridDim.x);
   while (f < f_end) {
@@ -290,7 +289,7 @@ __global__ __launch_bounds__(256, MINW) void rpe_bias_kernel(const float* __rest
     }
     float4 b[CTB];
     if (unit < u_hi) {
-      const float* E0 = TL ? Erow + ((unsigned)min((unit << 5) + (lane >> 2), cl.M - 1) * CE + 4 * (lane & 3))
+      const float* E0 = HS ? Erow + ((unsigned)min((unit << 5) + (lane >> 2), cl.M - 1) * CE + 4 * (lane & 3))
                            : Erow + ((unsigned)min((unit << 5) + col, cl.M - 1) * CE + 4 * kq);
 #pragma unroll
       for (int t = 0; t < CTB; t++) b[t] = ld4(E0 + 16 * t);
@@ -362,11 +361,11 @@ __global__ __launch_bounds__(256, MINW) void rpe_bias_kernel(const float* __rest
     const unsigned bias_ah = (unsigned)cl.N * cl.Mp;
     for (; unit < u_hi; unit += 4) {
       const int t0 = unit << 1;
-      bias_tile<CT, RT, true, EQ, UA, BF, HS, TL>(b, afrag, qe_s, stage, 0, Erow, eq_row, eq_sa, t0, t0 + 1, cl.M, AH, H, tbuf, inv_qs);
+      bias_tile<CT, RT, true, EQ, UA, BF, HS>(b, afrag, qe_s, stage, 0, Erow, eq_row, eq_sa, t0, t0 + 1, cl.M, AH, H, tbuf, inv_qs);
       if (unit + 4 < u_hi)
-        bias_tile<CT, RT, true, EQ, UA, BF, HS, TL>(b, afrag, qe_s, stage, 16, Erow, eq_row, eq_sa, t0 + 1, t0 + 8, cl.M, AH, H, tbuf, inv_qs);
+        bias_tile<CT, RT, true, EQ, UA, BF, HS>(b, afrag, qe_s, stage, 16, Erow, eq_row, eq_sa, t0 + 1, t0 + 8, cl.M, AH, H, tbuf, inv_qs);
       else
-        bias_tile<CT, RT, false, EQ, UA, BF, HS, TL>(b, afrag, qe_s, stage, 16, Erow, eq_row, eq_sa, t0 + 1, t0 + 1, cl.M, AH, H, tbuf, inv_qs);
+        bias_tile<CT, RT, false, EQ, UA, BF, HS>(b, afrag, qe_s, stage, 16, Erow, eq_row, eq_sa, t0 + 1, t0 + 1, cl.M, AH, H, tbuf, inv_qs);
       // the unit's (rows, 32 keys) block: 8 lanes cover one row's 128 bytes
       const int r8 = lane >> 3, m4 = (lane & 7) * 4;
 #pragma unroll
@@ -499,17 +498,10 @@ __device__ __forceinline__ void flash_tiles(FlashState<D>& st, const float* __re
 // float4 q[n0 + c32][8 u + 4 half ..], shared by the waves, conflict-free ds_read_b128); every operand of a key tile is requested
 // one phase or one tile ahead of its use, each into registers that have just been consumed (no second register set, no spills
 // at 3 workgroups = 12 waves per CU; a single scratch reload would cost a vmcnt(0) drain in the middle of the tile).
-#define SE3_STAMP(slot)                                                    \
-  if (PROF) {                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-    if (prof != nullptr && (threadIdx.x & 63) == 0) prof[slot] = clock64(); \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-  }
-template <int D, bool HAS_BIAS, bool PROF = false>
+template <int D, bool HAS_BIAS>
 __device__ __forceinline__ void flash_tiles_qlds(FlashState<D>& st, const float4* q_s, const float* __restrict__ k,
                                                  const float* __restrict__ v, const float* __restrict__ bias, int n0, int N, int M,
-                                                 int k_rs, int v_rs, int Mp, float scale, int tile_begin, int tile_step,
-                                                 long long* prof = nullptr) {
+                                                 int k_rs, int v_rs, int Mp, float scale, int tile_begin, int tile_step) {
   constexpr int DT = FlashState<D>::DT, KU = FlashState<D>::KU;
   const int lane = threadIdx.x & 63, half = lane >> 5, c32 = lane & 31;
   const int nq = min(n0 + c32, N - 1);
@@ -525,12 +517,10 @@ __device__ __forceinline__ void flash_tiles_qlds(FlashState<D>& st, const float4
     for (int g = 0; g < 4; g++)
       b4[g] = HAS_BIAS ? ld4(bias_row + (tile_begin << 5) + 8 * g + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  int pslot = 2;
   for (int tile = tile_begin; tile < tiles; tile += tile_step) {
     const int m0 = tile << 5;
     const int tn = min(tile + tile_step, tiles - 1);      // the last iteration re-requests its own tile: branch-free
     float vv[DT * 16];
-    SE3_STAMP(pslot)
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; r++) s[r] = 0.f;
@@ -593,7 +583,6 @@ __device__ __forceinline__ void flash_tiles_qlds(FlashState<D>& st, const float4
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    SE3_STAMP(pslot + 1)
     const float m_new = fmaxf(st.m, mx);
     const float alpha = __expf(st.m - m_new);        // st.m = -inf on the first tile -> 0
     float ps = 0.f;
@@ -605,144 +594,12 @@ __device__ __forceinline__ void flash_tiles_qlds(FlashState<D>& st, const float4
     ps += __shfl_xor(ps, 32);
     st.l = st.l * alpha + ps;
     st.m = m_new;
-    SE3_STAMP(pslot + 2)
 #pragma unroll
     for (int dt = 0; dt < DT; dt++) {
 #pragma unroll
       for (int r = 0; r < 16; r++) st.o[dt][r] *= alpha;
 #pragma unroll
       for (int r = 0; r < 16; r++) st.o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[dt * 16 + r], s[r], st.o[dt], 0, 0, 0);
-    }
-    SE3_STAMP(pslot + 3)
-    pslot += 4;
-  }
-}
-
-// f16-split form of flash_tiles_qlds (round 3; head dimensions that are multiples of 16): both products on v_mfma_f32_32x32x16_f16 with every
-// operand as f16 hi + lo pieces and three products hi hi + hi lo + lo hi accumulated in f32 (2^-22 per term) -- 24 MFMAs of 32 cycles per
-// (32 query, 32 key) tile where the f32 form issues 64 of 64 cycles (93 us of matrix time per equivariant call at the bench shape).  The
-// query tile is split once into LDS (q_h / q_l[(2 j + half) * 32 + c32] = 8 f16: channels 16 j + 4 half .. +3 and 16 j + 8 + 4 half .. +3, the
-// order in which a lane's two K float4 of MFMA j arrive); K, V^T and the softmax weights are split in registers.  The S^T accumulator
-// registers of a lane are keys {8 g + 4 half + j}: registers 0..7 / 8..15 are directly the B operand of the two K16 steps of P V, and the V^T
-// registers are loaded in the same key order.
-__device__ __forceinline__ void split_f16x8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    hi[i] = (_Float16)v[i];
-    lo[i] = (_Float16)(v[i] - (float)hi[i]);
-  }
-}
-template <int D, bool HAS_BIAS>
-__device__ __forceinline__ void flash_tiles_f16(FlashState<D>& st, const uint4* q_h, const uint4* q_l, const float* __restrict__ k,
-                                                const float* __restrict__ v, const float* __restrict__ bias, int n0, int N, int M,
-                                                int k_rs, int v_rs, int Mp, float scale, int tile_begin, int tile_step) {
-  constexpr int DT = FlashState<D>::DT, KU = FlashState<D>::KU, KJ = D / 16;
-  static_assert(D % 16 == 0, "f16 flash tiles need a head dimension that is a multiple of 16");
-  const int lane = threadIdx.x & 63, half = lane >> 5, c32 = lane & 31;
-  const int nq = min(n0 + c32, N - 1);
-  const float* bias_row = HAS_BIAS ? bias + (size_t)nq * Mp : nullptr;
-  const int tiles = (M + 31) >> 5;
-  if (tile_begin >= tiles) return;
-  float4 kf[KU], b4[4];
-  {
-    const float* kr = k + (size_t)min((tile_begin << 5) + c32, M - 1) * k_rs + 4 * half;
-#pragma unroll
-    for (int u = 0; u < KU; u++) kf[u] = ld4(kr + 8 * u);
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-      b4[g] = HAS_BIAS ? ld4(bias_row + (tile_begin << 5) + 8 * g + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  for (int tile = tile_begin; tile < tiles; tile += tile_step) {
-    const int m0 = tile << 5;
-    const int tn = min(tile + tile_step, tiles - 1);      // the last iteration re-requests its own tile: branch-free
-    float vv[DT * 16];
-    f32x16 s;
-#pragma unroll
-    for (int r = 0; r < 16; r++) s[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < KJ; j++) {
-      const f16x8 qh = __builtin_bit_cast(f16x8, q_h[(2 * j + half) * 32 + c32]);
-      const f16x8 ql = __builtin_bit_cast(f16x8, q_l[(2 * j + half) * 32 + c32]);
-      const float kv[8] = {kf[2 * j].x, kf[2 * j].y, kf[2 * j].z, kf[2 * j].w, kf[2 * j + 1].x, kf[2 * j + 1].y, kf[2 * j + 1].z, kf[2 * j + 1].w};
-      f16x8 kh, kl;
-      split_f16x8(kv, kh, kl);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh, s, 0, 0, 0);
-    }
-    // (1) V^T of this tile, (2) K fragment of the next tile -- into the registers the S phase just read (see flash_tiles_qlds)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++) {
-      const int dd = 32 * dt + c32;
-#pragma unroll
-      for (int g = 0; g < 4; g++) {          // keys m0 + 8 g + 4 half .. +3 are contiguous in the transposed values
-        const float4 t = dd < D ? ld4(v + (size_t)dd * v_rs + m0 + 8 * g + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
-        vv[dt * 16 + 4 * g + 0] = t.x;
-        vv[dt * 16 + 4 * g + 1] = t.y;
-        vv[dt * 16 + 4 * g + 2] = t.z;
-        vv[dt * 16 + 4 * g + 3] = t.w;
-      }
-    }
-    {
-      const float* kr = k + (size_t)min((tn << 5) + c32, M - 1) * k_rs + 4 * half;
-#pragma unroll
-      for (int u = 0; u < KU; u++) kf[u] = ld4(kr + 8 * u);
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int key = m0 + 8 * g + 4 * half + j;
-        float val = (s[4 * g + j] + f4get(b4[g], j)) * scale;
-        val = key < M ? val : -INFINITY;
-        s[4 * g + j] = val;
-        mx = fmaxf(mx, val);
-      }
-    }
-    // (3) the logits of the next tile, into the registers just consumed, requested last (in-order VMEM counter)
-    __builtin_amdgcn_sched_barrier(0);
-    if (HAS_BIAS) {
-#pragma unroll
-      for (int g = 0; g < 4; g++) b4[g] = ld4(bias_row + (tn << 5) + 8 * g + 4 * half);
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(st.m, mx);
-    const float alpha = __expf(st.m - m_new);        // st.m = -inf on the first tile -> 0
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      s[r] = __expf(s[r] - m_new);
-      ps += s[r];
-    }
-    ps += __shfl_xor(ps, 32);
-    st.l = st.l * alpha + ps;
-    st.m = m_new;
-    f16x8 ph[2], pl[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const float pv[8] = {s[8 * i], s[8 * i + 1], s[8 * i + 2], s[8 * i + 3], s[8 * i + 4], s[8 * i + 5], s[8 * i + 6], s[8 * i + 7]};
-      split_f16x8(pv, ph[i], pl[i]);
-    }
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) st.o[dt][r] *= alpha;
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const float vs[8] = {vv[dt * 16 + 8 * i], vv[dt * 16 + 8 * i + 1], vv[dt * 16 + 8 * i + 2], vv[dt * 16 + 8 * i + 3],
-                             vv[dt * 16 + 8 * i + 4], vv[dt * 16 + 8 * i + 5], vv[dt * 16 + 8 * i + 6], vv[dt * 16 + 8 * i + 7]};
-        f16x8 vh, vl;
-        split_f16x8(vs, vh, vl);
-        st.o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[i], st.o[dt], 0, 0, 0);
-        st.o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[i], st.o[dt], 0, 0, 0);
-        st.o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[i], st.o[dt], 0, 0, 0);
-      }
     }
   }
 }
@@ -755,44 +612,6 @@ __device__ __forceinline__ void flash_init(FlashState<D>& st) {
   for (int dt = 0; dt < FlashState<D>::DT; dt++)
 #pragma unroll
     for (int r = 0; r < 16; r++) st.o[dt][r] = 0.f;
-}
-
-// merge the states of the NW waves of a workgroup into wave 0 (through LDS); returns normalised output in st (wave 0 only)
-template <int D, int NW>
-__device__ __forceinline__ void flash_merge(FlashState<D>& st, float* sm, float* sl, float* so) {
-  constexpr int DT = FlashState<D>::DT;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  sm[wave * 64 + lane] = st.m;
-  sl[wave * 64 + lane] = st.l;
-#pragma unroll
-  for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) so[((wave * DT + dt) * 16 + r) * 64 + lane] = st.o[dt][r];
-  __syncthreads();
-  if (wave == 0) {
-    float mt = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < NW; w++) mt = fmaxf(mt, sm[w * 64 + lane]);
-    float lt = 0.f;
-    float f[NW];
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      f[w] = __expf(sm[w * 64 + lane] - mt);
-      lt += sl[w * 64 + lane] * f[w];
-    }
-    const float inv = 1.f / lt;
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        float acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; w++) acc += so[((w * DT + dt) * 16 + r) * 64 + lane] * f[w];
-        st.o[dt][r] = acc * inv;
-      }
-    st.m = mt;
-    st.l = lt;
-  }
 }
 
 // Merge the states of the NW waves through LDS and write the normalised output tile; every wave reduces and stores its own
@@ -871,17 +690,21 @@ struct AttnArgs {
   float scale;
   int QT;                             // 32-query tiles of the largest cloud
   int G;                              // groups = clouds * anchors * heads
-  long long* prof;                    // profiling hook (attention variant 9): 32 stamps per wave, else null
 };
 
-// One workgroup per (cloud, anchor, head, 32-query tile); its NW waves split the key tiles and merge through LDS.
+// One workgroup per (cloud, anchor, head, 32-query tile); its 4 waves split the key tiles and merge through LDS.
 // XCD-aware flat grid: workgroup i runs on XCD i % 8 (round-robin dispatch), so group g = (cloud, anchor, head) is pinned
 // to XCD g % 8 and the K / V^T of a group (re-read by all of its query tiles) stay in ONE L2.
-template <int D, int NW, int MINW, int MODE>      // MODE 0: loads at the tile top; 1: full double buffering; 2: Q in LDS + K prefetch
-__global__ __launch_bounds__(64 * NW, MINW) void attention_kernel(AttnArgs p) {
+// Measured in rounds 2 and 3 and removed with the tuning variants: K / V^T loads at the tile top or fully double buffered through flash_tiles
+// (slower than Q in LDS + requests into just-consumed registers), 6 waves (2 workgroups per CU), 2 and 1 waves per workgroup (no / smaller merge
+// through LDS: 160-171 us against 160 per equivariant call at the bench shape), and the f16 hi / lo split of every operand inside the loop
+// (171-183 us: the ~400 split instructions per tile cost what the matrix pipe saves -- attention_x6_kernel below splits K / V^T once per call).
+template <int D>
+__global__ __launch_bounds__(256, 3) void attention_kernel(AttnArgs p) {
+  constexpr int NW = 4;
   __shared__ float sm[64 * NW], sl[64 * NW];
   __shared__ float so[NW * FlashState<D>::DT * 16 * 64];
-  __shared__ float4 q_s[MODE >= 2 ? (D / 8) * 2 * 32 : 1];
+  __shared__ float4 q_s[(D / 8) * 2 * 32];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int gslot = j / p.QT, qt = j - gslot * p.QT;
   const int g = gslot * 8 + xcd;
@@ -899,52 +722,25 @@ __global__ __launch_bounds__(64 * NW, MINW) void attention_kernel(AttnArgs p) {
   const float* q = p.q + a * p.q_sa + (size_t)cl.q_start * p.q_rs + h * D;
   const float* k = p.k + a * p.k_sa + (size_t)cl.k_start * p.k_rs + h * D;
   const float* v = p.v + a * p.v_sa + (size_t)h * D * p.v_rs + cl.k_start;
-  long long* prof = nullptr;         // MODE 3 (profiling hook): 32 clock64() stamps per wave
-  if (MODE == 3 && p.prof != nullptr) {
-    prof = p.prof + ((size_t)blockIdx.x * NW + wave) * 32;
-    if ((threadIdx.x & 63) == 0) prof[0] = clock64();
+  for (int i = threadIdx.x; i < (D / 8) * 2 * 32; i += 64 * NW) {
+    const int c32 = i & 31, uh = i >> 5;
+    q_s[i] = ld4(q + (size_t)min(n0 + c32, cl.N - 1) * p.q_rs + 8 * (uh >> 1) + 4 * (uh & 1));
   }
-  if (MODE == 4) {
-    // the query tile as f16 hi / lo pieces: fragment (j, half)[c32] = channels 16 j + 4 half .. +3 | 16 j + 8 + 4 half .. +3; thread i stages
-    // one float4 = one 8-byte half of a fragment
-    if constexpr (D % 16 == 0) {
-      uint2* qh2 = reinterpret_cast<uint2*>(q_s);
-      uint2* ql2 = qh2 + (D / 16) * 2 * 32 * 2;
-      for (int i = threadIdx.x; i < (D / 8) * 2 * 32; i += 64 * NW) {
-        const int c32 = i & 31, uh = i >> 5, u = uh >> 1, hf = uh & 1;
-        const float4 qv = ld4(q + (size_t)min(n0 + c32, cl.N - 1) * p.q_rs + 8 * u + 4 * hf);
-        uint2 hi, lo;
-        split_f16x4(qv, hi, lo);
-        const int slot = ((((u >> 1) * 2 + hf) * 32 + c32) << 1) + (u & 1);
-        qh2[slot] = hi;
-        ql2[slot] = lo;
-      }
-      __syncthreads();
-      const uint4* q_h = reinterpret_cast<const uint4*>(q_s);
-      const uint4* q_l = q_h + (D / 16) * 2 * 32;
-      if (p.bias != nullptr)
-        flash_tiles_f16<D, true>(st, q_h, q_l, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW);
-      else
-        flash_tiles_f16<D, false>(st, q_h, q_l, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW);
-    }
-  } else if (MODE >= 2) {
-    for (int i = threadIdx.x; i < (D / 8) * 2 * 32; i += 64 * NW) {
-      const int c32 = i & 31, uh = i >> 5;
-      q_s[i] = ld4(q + (size_t)min(n0 + c32, cl.N - 1) * p.q_rs + 8 * (uh >> 1) + 4 * (uh & 1));
-    }
-    __syncthreads();
-    if (MODE == 3 && prof != nullptr && (threadIdx.x & 63) == 0) prof[1] = clock64();
-    if (p.bias != nullptr)
-      flash_tiles_qlds<D, true, MODE == 3>(st, q_s, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW, prof);
-    else
-      flash_tiles_qlds<D, false, MODE == 3>(st, q_s, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW, prof);
-    if (MODE == 3 && prof != nullptr && (threadIdx.x & 63) == 0) prof[29] = clock64();
-  } else {
-    flash_tiles<D, MODE == 1>(st, q, k, v, bias, n0, cl.N, cl.M, p.q_rs, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW);
-  }
-  if (MODE == 3 && prof != nullptr && (threadIdx.x & 63) == 0) prof[30] = clock64();
+  __syncthreads();
+  if (p.bias != nullptr)
+    flash_tiles_qlds<D, true>(st, q_s, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW);
+  else
+    flash_tiles_qlds<D, false>(st, q_s, k, v, bias, n0, cl.N, cl.M, p.k_rs, p.v_rs, cl.Mp, p.scale, wave, NW);
   flash_merge_store<D, NW>(st, sm, sl, so, p.out + a * p.o_sa + (size_t)cl.q_start * p.C + h * D, n0, cl.N, p.C);
-  if (MODE == 3 && prof != nullptr && (threadIdx.x & 63) == 0) prof[31] = clock64();
+}
+
+// Never called: a second caller of flash_tiles<32, true>, which cross_eq_apply_kernel<32> needs in this file.  The helpers have internal linkage,
+// so with cross_eq_apply_kernel as the only caller the compiler propagates its constant arguments (no logits, tile 0, step 1) into flash_tiles
+// BEFORE inlining, and the kernel comes out with 168 instead of 152 registers: 2 instead of 3 waves per SIMD.  (Until the tuning variants were
+// removed, attention_kernel's double-buffered form was that caller.  D = 8 / 16 / 64 move by 3 / 6 / 17 registers without crossing an
+// occupancy step and are left alone: profiles/variants_removed_kernels.txt.)
+__device__ __attribute__((used, noinline)) void flash_tiles_second_caller(FlashState<32>& st, const AttnArgs& p, int n0, int tile_begin, int tile_step) {
+  flash_tiles<32, true>(st, p.q, p.k, p.v, p.bias, n0, p.S.c[0].N, p.S.c[0].M, p.q_rs, p.k_rs, p.v_rs, p.S.c[0].Mp, p.scale, tile_begin, tile_step);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1678,27 +1474,10 @@ static void launch_kernel(int tag, K kernel, dim3 grid, dim3 block, hipStream_t 
 
 extern "C" void se3_debug_kernel_timing(int enable) { g_time_kernels = enable != 0; }
 
-// Waits for the recorded launches, writes their durations (microseconds) and tags in launch order, releases the events and
-// returns the number of launches recorded (entries beyond `capacity` are dropped).
-extern "C" int se3_debug_kernel_timing_collect(float* microseconds, int* tags, int capacity) {
-  std::lock_guard<std::recursive_mutex> lock(g_timed_mutex);
-  int n = 0;
-  for (const TimedLaunch& t : g_timed) {
-    float ms = 0.f;
-    if (hipEventSynchronize(t.stop) == hipSuccess && hipEventElapsedTime(&ms, t.start, t.stop) == hipSuccess && n < capacity) {
-      microseconds[n] = ms * 1e3f;
-      tags[n] = t.tag;
-      n++;
-    }
-    (void)hipEventDestroy(t.start);
-    (void)hipEventDestroy(t.stop);
-  }
-  g_timed.clear();
-  return n;
-}
-
-// The same with the algorithmic bytes recorded for the logits launches of the stack-mode self-attention calls (0 elsewhere): the caller
-// needs no record of its own of which call was which (the launches may come from se3_transformer_forward).
+// Waits for the recorded launches, writes their durations (microseconds), tags and -- for the logits launches of the stack-mode
+// self-attention calls, 0 elsewhere -- the call's algorithmic bytes in launch order (the caller needs no record of its own of which call was
+// which: the launches may come from se3_transformer_forward), releases the events and returns the number of launches recorded (entries beyond
+// `capacity` are dropped).
 extern "C" int se3_debug_kernel_timing_collect_ex(float* microseconds, int* tags, double* aux, int capacity) {
   std::lock_guard<std::recursive_mutex> lock(g_timed_mutex);
   int n = 0;
@@ -1716,15 +1495,6 @@ extern "C" int se3_debug_kernel_timing_collect_ex(float* microseconds, int* tags
   g_timed.clear();
   return n;
 }
-
-static int g_attn_variant = 0;
-static long long* g_attn_prof = nullptr;
-extern "C" void se3_debug_set_attention_variant(int variant) { g_attn_variant = variant; }
-extern "C" void se3_debug_set_attention_profile(long long* stamps) { g_attn_prof = stamps; }
-static int g_bias_variant = 0;
-static int g_bias_split = 0;
-// tuning hooks (benchmarks only): kernel variant / m-split override; 0 = default
-extern "C" void se3_debug_set_bias_variant(int variant, int split) { g_bias_variant = variant; g_bias_split = split; }
 
 static int device_cu_count() {
   static int cus = 0;
@@ -1751,15 +1521,12 @@ static int launch_rpe_bias(const float* qp, const float* qe, int row_stride, int
   }
   SE3_REQUIRE(total < (1ll << 31), SE3_ERR_UNSUPPORTED, "rpe_bias: too many (row, key tile) units");
   S.total_units = (int)total;
-  if (g_bias_variant == 9)      // diagnostic (tools/micro/rpe_eq_breakdown.py): every cloud writes its logits over the first cloud's block -- 1/16 of the bytes
-    for (int c = 1; c < S.n; c++) S.c[c].bias_off = S.c[0].bias_off;
   // one resident round, each workgroup with a balanced range of units: 3 workgroups of 4 waves per CU (LDS: fragments + staging) for the
   // f32 / bf16-embedding kernels, 2 for the f16-split kernel (the splits need ~190 registers; 8 waves x 16 KB stay in flight per CU)
-  const bool half_split = !emb_bf16 && g_bias_variant != 2 && g_bias_variant != 3 && (qe == nullptr || H % 4 == 0);
+  const bool half_split = !emb_bf16 && (qe == nullptr || H % 4 == 0);
   // (round 4: with the quad-contiguous requests the f16-split kernel of <= 16 folded-query rows takes 130 registers: three resident
   // workgroups per compute unit, 337 against 351 us per invariant call; the 24-row form takes 176: two)
-  int wgs = (half_split && !(AH <= 16 && g_bias_variant != 5) ? 2 : 3) * device_cu_count();
-  if (g_bias_split > 0) wgs = g_bias_split * device_cu_count();
+  int wgs = (half_split && AH > 16 ? 2 : 3) * device_cu_count();
   if (wgs > (total + 3) / 4) wgs = (int)((total + 3) / 4);
   if (wgs < 1) wgs = 1;
   dim3 grid((unsigned)wgs);
@@ -1770,15 +1537,9 @@ static int launch_rpe_bias(const float* qp, const float* qe, int row_stride, int
     else if (H % 4 == 0) launch_kernel(1, rpe_bias_kernel<CT, RT, 3, true, true, true>, grid, dim3(256), st, SE3_BIAS_ARGS);          \
     else launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);                         \
   } else if (qe == nullptr) {                                                                                               \
-    if (g_bias_variant == 2) launch_kernel(1, rpe_bias_kernel<CT, RT, 2, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);           \
-    else if (g_bias_variant == 3) launch_kernel(1, rpe_bias_kernel<CT, RT, 3, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);      \
-    else if (g_bias_variant == 5) launch_kernel(1, rpe_bias_kernel<CT, RT, 2, false, true, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);       \
-    else launch_kernel(1, rpe_bias_kernel<CT, RT, 2, false, true, false, true, true>, grid, dim3(256), st, SE3_BIAS_ARGS);            \
+    launch_kernel(1, rpe_bias_kernel<CT, RT, 2, false, true, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);                       \
   } else if (H % 4 == 0) {                                                                                           \
-    if (g_bias_variant == 2) launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, true>, grid, dim3(256), st, SE3_BIAS_ARGS);            \
-    else if (g_bias_variant == 3) launch_kernel(1, rpe_bias_kernel<CT, RT, 3, true, true>, grid, dim3(256), st, SE3_BIAS_ARGS);       \
-    else if (g_bias_variant == 5) launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, true, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);        \
-    else launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, true, false, true, true>, grid, dim3(256), st, SE3_BIAS_ARGS);             \
+    launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, true, false, true>, grid, dim3(256), st, SE3_BIAS_ARGS);                        \
   } else {                                                                                                           \
     launch_kernel(1, rpe_bias_kernel<CT, RT, 2, true, false>, grid, dim3(256), st, SE3_BIAS_ARGS);                                    \
   }
@@ -1866,7 +1627,7 @@ extern "C" int se3_rpe_bias_stack_bf16_fwd(const float* qp, const float* qe, int
 
 // ---- RPE / plain attention of a stack of clouds on the f16 matrix cores (head dimension 64) ---------------------------------------------
 // attention_kernel above multiplies on the f32 matrix cores (57 % of their peak at A = 6: 160 us per call) and its f16-split form
-// (MODE 4) splits every K and V^T tile again in every workgroup that reads it -- vector-ALU bound, no gain.  Here K and V^T are split ONCE
+// (round 3, removed) split every K and V^T tile again in every workgroup that read it -- vector-ALU bound, no gain.  Here K and V^T are split ONCE
 // per call (x6_split_kernel: the pieces have the byte size of the f32 tensors) and the kernel has the structure of
 // cross_eq_apply_stack_x6_kernel: 4 waves = 4 consecutive 32-query tiles of one (cloud, anchor, head), every 32-key K / V^T tile goes
 // global -> registers -> LDS THREE steps ahead and is read by the four waves from LDS, the logits tile of a wave (16 floats per lane, written
@@ -1878,10 +1639,9 @@ struct AttnPieces {
   int nblk;
 };
 
-template <bool HAS_BIAS, bool PROF = false>
+template <bool HAS_BIAS>
 __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(AttnArgs p, AttnPieces X, int64_t k_piece_sa, int64_t v_piece_sa) {
   constexpr int D = 64;
-  long long* prof = nullptr;                                // profiling hook (attention variant 12): 32 clock64() stamps per wave
   __shared__ uint4 ktile[2][2][32][kX6KRow];
   __shared__ uint4 vtile[2][2][64][kX6VRow];
   const int A = p.A, C = p.C;
@@ -1892,8 +1652,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, c32 = lane & 31;
   const int n0 = blockIdx.x * 128 + wave * 32;
   const bool active = n0 < cl.N;                            // (inactive waves still help with the tile copies)
-  if (PROF && p.prof != nullptr) prof = p.prof + ((((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + wave) * 32;
-  SE3_STAMP(0)
   const int nq = min(n0 + c32, cl.N - 1);
   h2x8_t qf[2][4];
   float q_unscale;              // logits = ((scaled q . scaled k) / (query scale x key-block scale) + bias) / sqrt(d): the lane's factor
@@ -1958,7 +1716,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
   request(1, rk[1], rv[1], rb[1], rs[1]);
   request(2, rk[2], rv[2], rb[2], rs[2]);
   __syncthreads();
-  SE3_STAMP(1)
   FlashState<D> st;
   flash_init(st);
   // one step; *_req: the register set that is free now (tile step + 3 goes there), *_pub: the set holding tile step + 1; bias: this step's
@@ -1970,7 +1727,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
     for (int g = 0; g < 4; g++) b4[g] = HAS_BIAS ? rb_req[g] : f32x4{0.f, 0.f, 0.f, 0.f};   // (this step's logits sit in the set about to be refilled)
     const float ks = rs_req;                                                                //  and so do its key-block scales
     request(step + 3, rk_req, rv_req, rb_req, rs_req);
-    if (PROF && step < 5) { SE3_STAMP(2 + 5 * step) }
     if (active) {
       f32x16 s, s2;
 #pragma unroll
@@ -2002,7 +1758,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
           mx = fmaxf(mx, val);
         }
       }
-      if (PROF && step < 5) { SE3_STAMP(3 + 5 * step) }
       mx = fmaxf(mx, other_half(mx));
       const float m_new = fmaxf(st.m, mx);
       const float alpha = __expf(st.m - m_new);
@@ -2024,7 +1779,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
         pb[0][j] = __builtin_bit_cast(h2x8_t, p1);
         pb[1][j] = __builtin_bit_cast(h2x8_t, p2);
       }
-      if (PROF && step < 5) { SE3_STAMP(4 + 5 * step) }
 #pragma unroll
       for (int dt = 0; dt < 2; dt++)
 #pragma unroll
@@ -2043,10 +1797,8 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
 #undef SE3_X6_PV
       }
     }
-    if (PROF && step < 5) { SE3_STAMP(5 + 5 * step) }
     publish(buf ^ 1, rk_pub, rv_pub);
     __syncthreads();
-    if (PROF && step < 5) { SE3_STAMP(6 + 5 * step) }
   };
   // The step count is padded to a multiple of 3 (the padding steps see only masked keys: exp(-inf) = 0, the running maximum is finite after
   // the first real tile): with `if (step + 1 < steps)` around the second and third step the paths into the loop's back edge carry different
@@ -2056,7 +1808,6 @@ __global__ __launch_bounds__(256, HAS_BIAS ? 2 : 3) void attention_x6_kernel(Att
     one_step(step + 1, rk[1], rv[1], rb[1], rs[1], rk[2], rv[2]);
     one_step(step + 2, rk[2], rv[2], rb[2], rs[2], rk[0], rv[0]);
   }
-  SE3_STAMP(30)
   if (!active) return;
   const int nrow = n0 + c32;
   if (nrow < cl.N) {
@@ -2083,7 +1834,7 @@ extern "C" size_t se3_attention_kv_pieces_bytes(int num_anchors, int64_t key_row
 }
 static bool launch_attention_x6(AttnArgs& p, void* ws, size_t ws_bytes, hipStream_t st) {
   // (the plain cross-attention calls -- no logits, one or six small value sets -- stay on the f32 kernel: 16 us against 20 + 10 for the split)
-  if (ws == nullptr || p.bias == nullptr || g_attn_variant == 11 || p.C / p.H != 64 || p.C % 8 || p.v_rs % 16 || p.q_rs % 4 || p.k_rs % 4 ||
+  if (ws == nullptr || p.bias == nullptr || p.C / p.H != 64 || p.C % 8 || p.v_rs % 16 || p.q_rs % 4 || p.k_rs % 4 ||
       (reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(p.q) & 15) || (reinterpret_cast<uintptr_t>(p.k) & 15) ||
       (reinterpret_cast<uintptr_t>(p.v) & 15) || (p.A > 1 && (p.k_sa == 0 || p.v_sa == 0)))
     return false;
@@ -2117,10 +1868,7 @@ static bool launch_attention_x6(AttnArgs& p, void* ws, size_t ws_bytes, hipStrea
   }
   X.kinv = kinv; X.vinv = vinv; X.nblk = (int)((R + 7) / 8);
   const dim3 grid((unsigned)((nmax + 127) / 128), (unsigned)p.H, (unsigned)(p.S.n * p.A));
-  if (g_attn_variant == 12 && p.bias != nullptr) {
-    p.prof = g_attn_prof;
-    launch_kernel(2, attention_x6_kernel<true, true>, grid, dim3(256), st, p, X, (int64_t)R * p.C, (int64_t)p.C * p.v_rs);
-  } else if (p.bias != nullptr) launch_kernel(2, attention_x6_kernel<true>, grid, dim3(256), st, p, X, (int64_t)R * p.C, (int64_t)p.C * p.v_rs);
+  if (p.bias != nullptr) launch_kernel(2, attention_x6_kernel<true>, grid, dim3(256), st, p, X, (int64_t)R * p.C, (int64_t)p.C * p.v_rs);
   else launch_kernel(2, attention_x6_kernel<false>, grid, dim3(256), st, p, X, (int64_t)R * p.C, (int64_t)p.C * p.v_rs);
   return true;
 }
@@ -2133,27 +1881,7 @@ static int launch_attention(AttnArgs& p, hipStream_t st) {
   dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * qt));
   int rc = dispatch_head_dim(p.C / p.H, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    switch (g_attn_variant) {      // tuning hook
-      case 1: launch_kernel(2, attention_kernel<D, 4, 2, 1>, grid, dim3(256), st, p); break;
-      case 2: launch_kernel(2, attention_kernel<D, 4, 3, 0>, grid, dim3(256), st, p); break;
-      case 3: launch_kernel(2, attention_kernel<D, 6, 2, 2>, grid, dim3(384), st, p); break;
-      case 9: p.prof = g_attn_prof; launch_kernel(2, attention_kernel<D, 4, 3, 3>, grid, dim3(256), st, p); break;
-      case 5:                                                                                     // f16 hi / lo split MFMAs (flash_tiles_f16)
-        if constexpr (D % 16 == 0) launch_kernel(2, attention_kernel<D, 4, 3, 4>, grid, dim3(256), st, p);
-        else launch_kernel(2, attention_kernel<D, 4, 3, 2>, grid, dim3(256), st, p);
-        break;
-      case 6: launch_kernel(2, attention_kernel<D, 2, 3, 2>, grid, dim3(128), st, p); break;
-      case 7:
-        if constexpr (D % 16 == 0) launch_kernel(2, attention_kernel<D, 2, 3, 4>, grid, dim3(128), st, p);
-        else launch_kernel(2, attention_kernel<D, 2, 3, 2>, grid, dim3(128), st, p);
-        break;
-      case 8: launch_kernel(2, attention_kernel<D, 1, 3, 2>, grid, dim3(64), st, p); break;
-      case 10:
-        if constexpr (D % 16 == 0) launch_kernel(2, attention_kernel<D, 1, 3, 4>, grid, dim3(64), st, p);
-        else launch_kernel(2, attention_kernel<D, 1, 3, 2>, grid, dim3(64), st, p);
-        break;
-      default: launch_kernel(2, attention_kernel<D, 4, 3, 2>, grid, dim3(256), st, p); break;
-    }
+    launch_kernel(2, attention_kernel<D>, grid, dim3(256), st, p);
   }, "attention");
   if (rc != SE3_OK) return rc;
   SE3_CHECK_LAUNCH("attention");

@@ -633,7 +633,7 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
   gn_finalize_groups(a.part, a.groups, cb0, cb1, blockIdx.y * gpb, gpb, cpg, a.xb, a.gw, a.gb, a.eps, a.affine + (size_t)seg * 2 * N, N);
 }
 
-int g_target_chunks = 768;                   // workgroups (row chunks x column blocks) aimed at: 3 per compute unit, all resident at once
+constexpr int kTargetChunks = 768;           // workgroups (row chunks x column blocks) aimed at: 3 per compute unit, all resident at once
 
 }  // namespace
 
@@ -649,8 +649,6 @@ extern "C" unsigned long long se3_debug_dense_saturated_rows(int reset) {
   return n;
 }
 
-extern "C" void se3_dense_norm_set_target_chunks(int workgroups) { g_target_chunks = workgroups > 0 ? workgroups : 768; }
-
 constexpr size_t kCounterB = kGNCounterB;
 
 // [arrival counters: zero before the first call, left zero by every call][partials: (chunk, group) x 3 floats]
@@ -659,7 +657,7 @@ extern "C" size_t se3_dense_norm_workspace_bytes(int groups) {
 }
 
 namespace {
-// row chunks: whole row tiles, about g_target_chunks workgroups in all, never across a segment boundary
+// row chunks: whole row tiles, about kTargetChunks workgroups in all, never across a segment boundary
 int dense_chunks(int64_t rows, int N, const int64_t* segment_row_offsets_host, int num_segments, SegTable& T, int& TR, int& BN, int& ncb,
                  bool given = false) {
   if (!given) {
@@ -676,7 +674,7 @@ int dense_chunks(int64_t rows, int N, const int64_t* segment_row_offsets_host, i
     if (!(b1 > b0 && b0 >= 0 && b1 <= rows)) return -1;
     tiles += se3_cdiv(b1 - b0, TR);
   }
-  int64_t want = g_target_chunks / ncb;
+  int64_t want = kTargetChunks / ncb;
   if (want > kGNMaxChunks - num_segments) want = kGNMaxChunks - num_segments;
   if (want < 1) want = 1;
   int64_t tiles_per_chunk = se3_cdiv(tiles, want);

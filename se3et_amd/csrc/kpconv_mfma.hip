@@ -30,8 +30,8 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // Diagnostic hooks, empty in the product: tools/micro/kpconv_stamps.hip defines them (wave time stamps, fixed weight fragments) before it
 // includes this file and builds a library of its own.
-#ifndef SE3_STAMP
-#define SE3_STAMP(step_, slot_)
+#ifndef SE3_KPCONV_STAMP
+#define SE3_KPCONV_STAMP(step_, slot_)
 #endif
 #ifndef SE3_DIAG_WEIGHT_STEP
 #define SE3_DIAG_WEIGHT_STEP(gs_, ksp_) (gs_)
@@ -422,7 +422,6 @@ __global__ __launch_bounds__(256) void kpconv_orbit_gather_kernel(const float* _
 }
 
 // ---- fused form: stages 2 and 3 in one kernel ------------------------------------------------------------------------------------------
-static int g_kpconv_variant = 0;
 // One 11- or 12-wave workgroup per compute unit and 16-point tile; three tile images in LDS (3 x 48.6 KB).
 // Schedule: step u = 0 .. chunks + 1, one barrier between steps.  CONSUMER waves multiply chunk u - 2 (image (u - 2) % 3) in step u >= 2.
 // A PRODUCER wave (8 of them) handles ONE point per step over a PAIR of chunks (16 channels): in step u = 2T its first point, in step 2T + 1 its
@@ -434,7 +433,7 @@ template <int NCW, int KS, int CT, bool EXT, bool BLK>      // consumer waves: N
 __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
     const float* __restrict__ x, const float* __restrict__ hwt, const int* __restrict__ nbr, const int* __restrict__ cnt, int NNp,
     const u32x4* __restrict__ Wf, const float* __restrict__ hdr, int64_t P, int Cin, int Cout, float* __restrict__ out,
-    float* __restrict__ split_part, int* __restrict__ split_count, int variant, const float* __restrict__ x_amax) {
+    float* __restrict__ split_part, int* __restrict__ split_count, const float* __restrict__ x_amax) {
   constexpr int NC = NCW * KS;                                         // consumer waves
   const float xs = x_split_scale(x_amax);                              // power-of-two scale of x before its f16 split (1 inside the plain range)
   constexpr int NPW = 8;                                               // producer waves: two points of the tile each
@@ -444,13 +443,9 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
   unsigned* tab = reinterpret_cast<unsigned*>(lds + 3 * kTileB);       // [K16-step][rsel][h]: three 8-bit run numbers (anchor pairs 0..2)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // variant bit 0: workgroup i runs on XCD i mod 8 -- give every XCD one contiguous range of tiles (its L2 then sees neighbouring tiles)
-  int64_t tile = blockIdx.x;
-  if (variant & 1) {
-    const int n = (int)gridDim.x, xcd = (int)blockIdx.x & 7, per = n >> 3, rem = n & 7;
-    tile = (int64_t)xcd * per + (xcd < rem ? xcd : rem) + ((int)blockIdx.x >> 3);
-  }
-  const int64_t p0 = tile * kTP;
+  // (workgroup i runs on XCD i mod 8; giving every XCD one contiguous range of tiles, so that its L2 sees neighbouring tiles, was measured
+  // in round 5 with Morton-ordered rows: no gain, removed)
+  const int64_t tile = blockIdx.x, p0 = tile * kTP;
   // gridDim.z > 1 (few tiles: one pair per forward): the input-channel chunks are split over gridDim.z workgroups, whose partial outputs
   // the last one to arrive adds up in a fixed order (see the epilogue)
   const int chunks = Cin / kCC / (int)gridDim.z, chunk0 = blockIdx.z * chunks, pairs = (chunks + 1) / 2;
@@ -495,7 +490,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
       gather_request_ops<EXT, BLK>(x, hwt + pc * NNp * 16, NNp, 0, g, c16, nbv, rowlen, col_of(0), Cin, __builtin_amdgcn_readfirstlane(nv_cur), ops);
     }
     for (int u = 0; u < steps_total; u++) {
-      SE3_STAMP(u, 0)
+      SE3_KPCONV_STAMP(u, 0)
       if (u < 2 * pairs) {
         const int T = u >> 1, second = u & 1;
         const int i = pw + NPW * second;                                  // point of the tile, uniform over the wave
@@ -516,14 +511,14 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
         int nbn[kGN + (EXT ? kGX : 0)];
         gather_request_rows<EXT>(nbr + pnc * NNp, 0, g, nbn);
         const int nv_next = (more && pn < P) ? cnt[pnc] : 0;
-        SE3_STAMP(u, 1)
+        SE3_KPCONV_STAMP(u, 1)
         f32x4 acc[kA];
 #pragma unroll
         for (int a = 0; a < kA; a++) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
         const int nv = __builtin_amdgcn_readfirstlane(nv_cur);
-        SE3_STAMP(u, 5)
+        SE3_KPCONV_STAMP(u, 5)
         if (nv > 0) gather_multiply<EXT>(ops, nv > 32, acc, xs);
-        SE3_STAMP(u, 6)
+        SE3_KPCONV_STAMP(u, 6)
         for (int rd = 1; S * rd < nv; rd++) {                             // more valid neighbours than a round holds: further rounds, requested on the spot
           int nbv[kGN + (EXT ? kGX : 0)];
           GatherOps<EXT> q;
@@ -531,12 +526,12 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
           gather_request_ops<EXT, BLK>(x, hwt + pc * NNp * 16, NNp, rd, g, c16, nbv, rowlen, col_of(u), Cin, nv, q);
           gather_multiply<EXT>(q, nv > S * rd + 32, acc, xs);
         }
-        SE3_STAMP(u, 7)
+        SE3_KPCONV_STAMP(u, 7)
         // the next step's operands leave now (their neighbour numbers have arrived behind the MFMAs)
         gather_request_ops<EXT, BLK>(x, hwt + pnc * NNp * 16, NNp, 0, g, c16, nbn, rowlen, col_of(more ? u + 1 : u), Cin,
                                 __builtin_amdgcn_readfirstlane(nv_next), ops);
         nv_cur = nv_next;
-        SE3_STAMP(u, 2)
+        SE3_KPCONV_STAMP(u, 2)
         unsigned word[kA][4];
         gather_split(acc, odd, word);
         unsigned char* dst = (half ? img_b : img_a) + i * kRowB + dst0;
@@ -551,9 +546,9 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
 #pragma unroll
           for (int r = 0; r < 4; r++) held[a][r] = word[a][r];
       }
-      SE3_STAMP(u, 3)
+      SE3_KPCONV_STAMP(u, 3)
       if (u + 1 < steps_total) __syncthreads();
-      SE3_STAMP(u, 4)
+      SE3_KPCONV_STAMP(u, 4)
     }
     if (KS > 1) {
       __syncthreads();
@@ -599,7 +594,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
   __syncthreads();
   for (int cc = 0; cc < chunks; cc++) {
     const unsigned char* img = lds + (cc % 3) * kTileB;
-    SE3_STAMP(cc + 2, 0)
+    SE3_KPCONV_STAMP(cc + 2, 0)
     // A fragments of the step after the one being multiplied are read while its MFMAs run (two register sets)
     f16x8 av[2][3][2];
     {
@@ -663,9 +658,9 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_fused_kernel(
         (void)kDummy;
       }
     }
-    SE3_STAMP(cc + 2, 3)
+    SE3_KPCONV_STAMP(cc + 2, 3)
     if (cc + 1 < chunks) __syncthreads();
-    SE3_STAMP(cc + 2, 4)
+    SE3_KPCONV_STAMP(cc + 2, 4)
   }
   if (KS > 1) {                                                          // merge the K split through LDS (the images are no longer needed)
     __syncthreads();
@@ -967,7 +962,7 @@ extern "C" int se3_kpconv_so3_fused_scaled(const float* x, const void* table, in
     }                                                                                                                                     \
     kpconv_fused_kernel<NCW_, KS_, CT_, EXT_, BLK_>                                                                                       \
         <<<dim3((unsigned)tiles, (unsigned)(NCT / (NCW_ * CT_)), (unsigned)splits), 64 * (NCW_ * KS_ + 8), lds, st>>>(                    \
-            x, t.hwt, t.nbr, t.cnt, t.NNp, Wf, hdr, num_queries, in_channels, out_channels, out, split_part, split_count, g_kpconv_variant, x_amax);                \
+            x, t.hwt, t.nbr, t.cnt, t.NNp, Wf, hdr, num_queries, in_channels, out_channels, out, split_part, split_count, x_amax);                \
   }
 #define SE3_FUSED(NCW_, KS_, CT_)                                  \
   {                                                                \
@@ -989,5 +984,3 @@ extern "C" int se3_kpconv_so3_fused_scaled(const float* x, const void* table, in
   SE3_CHECK_LAUNCH("kpconv_so3_fused");
   return SE3_OK;
 }
-
-extern "C" void se3_debug_set_kpconv_variant(int variant) { g_kpconv_variant = variant; }

@@ -338,8 +338,6 @@ struct UnionArgs {
   float* split_part;
   int* split_count;
   const float* x_amax;       // largest |x| of the tensor (se3_group_norm_apply_amax) or null: kpsum::x_split_scale
-  int variant;               // diagnostic bits (se3_debug_set_kpconv_union_variant; results are wrong with any of them set): 1 producers skip the gather
-                             // product and the image stores, 2 skip the row loads and the B image, 4 skip the A fragments, 8 consumers skip their MFMAs
 };
 
 // PERSISTENT workgroups: workgroup b walks the groups b, b + gridDim.x, ...; an ITEM is one pass (sub-tile) of a group over the workgroup's C
@@ -385,7 +383,6 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
     const int pw = wave - NC;
     const int g = lane >> 4, col = lane & 15, odd = col & 1, half = col >> 3, cpair = (col & 7) >> 1;
     const unsigned rowlen = (unsigned)(kA * Cin);
-    const bool v_gather = !(a.variant & 1), v_load = !(a.variant & 2), v_abuild = !(a.variant & 4);
     const float xs = x_split_scale(a.x_amax);
     // loader task of this lane: rows 8 oct + 4 jh .. + 3 of the union, 16-byte part q of a row's 192-byte chunk (60 lanes per wave)
     const int task = pw * 60 + lane, oh = task / 12, q = task - oh * 12, oct = oh >> 1, jh = oh & 1;
@@ -453,7 +450,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
     meta2 = stage_b(grp, meta, roff);
     {
       const int ucount0 = __builtin_amdgcn_readlane(meta, 19);
-      if (v_load) request(0, lane < 60 && oct < 4 * ((ucount0 + 31) >> 5), roff);
+      request(0, lane < 60 && oct < 4 * ((ucount0 + 31) >> 5), roff);
     }
     for (;;) {
       // ---------------- P(-1) ----------------
@@ -470,7 +467,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
         const int i = pw + NPW * pt;
         const int pid = __builtin_amdgcn_readlane(meta, pw + NPW * pt);
         const int c = __builtin_amdgcn_readlane(meta2, pt);
-        const bool active = pid >= 0 && i >= lo && i < lo + np && v_abuild;
+        const bool active = pid >= 0 && i >= lo && i < lo + np;
         const bool slot = active && lane < c;
         const int lcv = slot ? (int)a.loc[(grp * 16 + i) * NNp + lane] : 0;
         float hwv[16];
@@ -497,8 +494,8 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
           }
         }
       }
-      if (v_load) convert(0, ltask);
-      if (chunks > 1 && v_load) request(1, ltask, roff);
+      convert(0, ltask);
+      if (chunks > 1) request(1, ltask, roff);
       __syncthreads();
       if (kIdle) __syncthreads();
       // the item after this one
@@ -508,11 +505,11 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
       const bool has_next = ngrp < G;
       int meta_n = 0, meta2_n = 0;
       for (int u = 0; u < chunks; u++) {
-        if (u + 1 < chunks && v_load) convert(u + 1, ltask);
-        if (u + 2 < chunks && v_load) request(u + 2, ltask, roff);
+        if (u + 1 < chunks) convert(u + 1, ltask);
+        if (u + 2 < chunks) request(u + 2, ltask, roff);
         if (u == 0 && has_next) meta_n = meta_load(ngrp, nsubi);
         if (u == (chunks >= 2 ? chunks - 2 : 0) && has_next) meta2_n = stage_b(ngrp, meta_n, roff_n);
-        if (v_gather) {
+        {
           const unsigned char* bsrc = bimg0 + (u & 1) * kBImgB + g * 256;
           unsigned char* img = lds + (u & 1) * kTileB;
           f32x4 acc[2][3];
@@ -555,7 +552,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
               }
           }
         }
-        if (u == chunks - 1 && has_next && v_load) {
+        if (u == chunks - 1 && has_next) {
           const int ucn = __builtin_amdgcn_readlane(meta_n, 19);
           request(0, lane < 60 && oct < 4 * ((ucn + 31) >> 5), roff_n);
         }
@@ -605,7 +602,6 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
     }
   }
   constexpr int kAgent = 16;
-  const bool v_mfma = !(a.variant & 8);
   auto contract = [&](int cc) {
     const unsigned char* img = lds + (cc & 1) * kTileB;
     f16x8 av[2][3][2];
@@ -619,7 +615,7 @@ __global__ __launch_bounds__(64 * (NCW * KS + 8)) void kpconv_union_kernel(const
       }
     }
 #pragma unroll 1
-    for (int q0 = v_mfma ? 0 : kSPW; q0 < kSPW; q0 += U) {
+    for (int q0 = 0; q0 < kSPW; q0 += U) {
 #pragma unroll
       for (int j = 0; j < U; j++) {
         const int ja = j & 1, jb = j % BD;
@@ -828,16 +824,8 @@ int union_colblocks(int out_channels) {
   return NCT % 4 == 0 ? NCT / 4 : NCT % 2 == 0 ? NCT / 2 : NCT;
 }
 constexpr size_t kSplitCounterB = 64 * 1024;
-int g_union_variant = 0;
-int g_union_wgs = 0;              // workgroups per launch; 0: 256 (one per compute unit, each walking ~G / 256 groups) for layers up to 64 wide, 1024 beyond
-                                  // (fewer groups per workgroup: the hardware's dispatch balances the uneven ones); se3_debug_set_kpconv_union_variant(v | wgs << 8) overrides
 
 }  // namespace
-
-extern "C" void se3_debug_set_kpconv_union_variant(int variant) {
-  g_union_variant = variant & 0xff;
-  g_union_wgs = variant >> 8;
-}
 
 extern "C" int64_t se3_point_order_groups(const int64_t* cloud_lengths_host, int num_clouds) {
   int64_t g = 0;
@@ -989,7 +977,6 @@ extern "C" int se3_kpconv_so3_union(const float* x, const void* table, const voi
   a.out = out;
   a.split_part = nullptr;
   a.split_count = nullptr;
-  a.variant = g_union_variant;
   a.x_amax = x_amax;
   const size_t lds = (size_t)2 * kTileB + 2 * kBImgB + kSteps * 4 * sizeof(unsigned) + 32 * sizeof(int);
   int splits = 1;
@@ -1004,7 +991,9 @@ extern "C" int se3_kpconv_so3_union(const float* x, const void* table, const voi
   }
   // persistent workgroups: one per compute unit (160 KB of LDS each), dealt over (column blocks, channel splits, groups)
   auto wgx = [&](int colblocks) {
-    const int wgs = g_union_wgs > 0 ? g_union_wgs : (out_channels <= 64 ? 256 : 1024);
+    // 256 workgroups (one per compute unit, each walking ~G / 256 groups) for layers up to 64 wide, 1024 beyond (fewer groups per workgroup: the
+    // hardware's dispatch balances the uneven ones; one workgroup per compute unit loses 10-15 % on the wide layers, measured in round 5)
+    const int wgs = out_channels <= 64 ? 256 : 1024;
     int64_t per = wgs / ((int64_t)colblocks * splits);
     per = per < 1 ? 1 : per;
     return per < num_groups ? per : num_groups;

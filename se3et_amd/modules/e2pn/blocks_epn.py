@@ -187,7 +187,7 @@ class ResnetBottleneckBlockEPN(nn.Module):
         y = self.norm.pending(y, 0.1)                                         # norm of the activated norm: a second statistics pass
         if 'strided' in self.block_name:
             skip = SF.neighbor_max_pool(skip, neighb_inds)
-        if SF.RECOMPUTE_TAIL and self.unary2.no_relu and self._recompute_pays(y.raw.numel() // y.raw.shape[-1]) and (
+        if self.unary2.no_relu and self._recompute_pays(y.raw.numel() // y.raw.shape[-1]) and (
                 isinstance(self.skip_conv, nn.Identity) or (self.skip_conv.no_relu and SF._ops.norm_weight_nonzero(self.skip_conv.norm.norm.weight))):
             # unary2 (mid -> 4 mid channels) and skip_conv as statistics-only GEMMs, then ONE kernel that runs both products again and writes
             # lrelu(norm(unary2) + shortcut): nothing of the output's width exists but the output (csrc/dense_norm.hip, round 4)

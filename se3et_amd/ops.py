@@ -42,10 +42,9 @@ def mm(a, b):
 
 
 # ---- dense layers on the f16 matrix cores (csrc/linear_f16.hip) --------------------------------------------------------------
-# 'auto': the hand-written f16 hi / lo split kernel for the inference GEMMs it wins on MI355X (tools/micro/linear_shapes.py, gpurun_out ->
+# The hand-written f16 hi / lo split kernel for the inference GEMMs it wins on MI355X (tools/micro/linear_shapes.py ->
 # profiles/r03_linear_shapes.txt: in_features >= 256 and >= 20 000 rows: 1.1-1.55x the library's f32-MFMA-bound kernels; the short-K layers
-# are HBM bound and stay on the library, which streams them better), the library otherwise; SE3_LINEAR=library forces the library everywhere.
-LINEAR_F16 = os.environ.get('SE3_LINEAR', 'auto') != 'library'
+# are HBM bound and stay on the library, which streams them better), the library otherwise.
 LINEAR_F16_MIN_ROWS, LINEAR_F16_MIN_K = 20000, 256
 _linear_pieces = Derived(512, weights=True)          # (data_ptr, N, K, row stride, device) -> f16 pieces
 
@@ -85,7 +84,7 @@ def stacked_weight(weight, groups):
 
 def linear_f16_ok(x, weight):
     """True when linear_f16 applies: inference, f32 GPU tensors, unit-stride rows aligned to 16 bytes, enough rows to fill the chip."""
-    if not LINEAR_F16 or torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
         return False
     if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2 and weight.is_contiguous()):
         return False
@@ -751,7 +750,6 @@ class BlockedFeatures:
         return self.data.view(n, c // 16, a // 2, 16, 2).permute(0, 2, 4, 1, 3).reshape(n, a, c)
 
 
-KPCONV_BLOCKED = True          # False: the KPConv input in the plain layout (A/B runs)
 # The union-staged fused KPConv (csrc/kpconv_union.hip), wherever a spatial order of the query points is registered (se3et_amd/data.py):
 # SE3_KPCONV_UNION = 0 never; 1 (default) where it measured faster than the per-lane-gather kernel alone on the GPU (output widths <= 64 of the
 # stride-1 layers and the first strided one: profiles/r05_kpconv_union_check.txt: 18-26 % on those layers with the 128-row cap); all: every
@@ -760,12 +758,7 @@ KPCONV_BLOCKED = True          # False: the KPConv input in the plain layout (A/
 _KPCONV_UNION_ENV = os.environ.get('SE3_KPCONV_UNION', '1')
 KPCONV_UNION = _KPCONV_UNION_ENV != '0'
 KPCONV_UNION_ALL = _KPCONV_UNION_ENV == 'all'
-KPCONV_UNION_BIG = os.environ.get('SE3_KPCONV_UNION_BIG', '0') == '1'      # A/B: the policy's layers also for clouds beyond 8192 points (order through torch.sort)
 KPCONV_UNION_MIN_POINTS = 24000           # stage-0 points of a pyramid from which the pyramid builder registers orders (single pairs stay on the gather kernel)
-
-
-if os.environ.get('SE3_KPCONV_UNION_WGS'):        # A/B runs: workgroups per launch of the union-staged kernel (default: 256 up to 64 output channels, 1024 beyond)
-    lib().se3_debug_set_kpconv_union_variant(int(os.environ['SE3_KPCONV_UNION_WGS']) << 8)
 
 
 _amax_rings = {}
@@ -1161,8 +1154,8 @@ def register_point_orders(points_list, lengths_list, cells):
     if not ok:
         # (clouds beyond 8192 points -- the KITTI configuration -- would take the keys + torch.sort + placement form, whose launches cost more
         # than the four narrow layers gain there: 142 against 141 pairs/s at C3 with the 160-row cap, 138.6 against 140.4 with the 128-row cap
-        # and NN = 38 -- SE3_KPCONV_UNION_BIG=1; only on request)
-        return [register_point_order(p, l, c) for p, l, c in zip(points_list, lengths_list, cells)] if (KPCONV_UNION_ALL or KPCONV_UNION_BIG) else [None] * len(points_list)
+        # and NN = 38; only with SE3_KPCONV_UNION=all)
+        return [register_point_order(p, l, c) for p, l, c in zip(points_list, lengths_list, cells)] if KPCONV_UNION_ALL else [None] * len(points_list)
     S = len(points_list)
     las = [_i64_array(l) for l in lens]
     Gs = [int(lib().se3_point_order_groups(la, len(l))) for la, l in zip(las, lens)]
@@ -1545,13 +1538,8 @@ def rpe_self_attention_stack(proj, offs, vt, embs, eq_embs, starts, lengths, num
     return out
 
 
-ATTENTION_F16 = True          # False: q.k and P.v on the f32 matrix cores (A/B runs; the f16 hi / lo form has the error of an f32 product)
-
-
 def _attention_pieces(A, k_starts, k_lengths, C, v_row_stride, device):
     """(workspace pointer, bytes) for the f16 hi / lo pieces of K and V^T of one stack-mode attention call: one buffer per stream."""
-    if not ATTENTION_F16:
-        return None, 0
     rows = max(int(s) + int(n) for s, n in zip(k_starts, k_lengths))
     nbytes = lib().se3_attention_kv_pieces_bytes(int(A), rows, int(C), int(v_row_stride))
     if nbytes == 0:
@@ -1640,9 +1628,6 @@ def cross_eq_groups(A, q_lengths, num_heads, C, k_starts, vt):
     if not CROSS_EQ_BF16X6 or C // H != 64 or C % H or A > 6 or vt.stride(1) % 16 or vt.stride(2) != 1 or any(int(s) % 16 for s in k_starts):
         return 1
     wgs = sum((int(n) + 127) // 128 for n in q_lengths) * H * A
-    forced = int(os.environ.get('SE3_EQ_GROUPS', '0'))          # A/B runs: 2 or 3
-    if forced in (2, 3) and A % forced == 0:
-        return forced
     for G in (3, 2):
         if A % G == 0 and wgs * G <= 320:
             return G

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of bench.py variants on ONE box, alternating runs: tools/ab_bench.sh <reps> "<env A>" "<env B>" [extra bench args]
-# e.g. tools/ab_bench.sh 3 "SE3_LINEAR_STREAM=1" "SE3_LINEAR_STREAM=0"
+# e.g. tools/ab_bench.sh 3 "SE3_KPCONV_UNION=1" "SE3_KPCONV_UNION=0"
 reps=$1; A=$2; B=$3; shift 3
 mkdir -p gpurun_out/ab
 for i in $(seq 1 $reps); do

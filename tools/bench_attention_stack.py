@@ -3,7 +3,6 @@ import sys; sys.path.insert(0, '.')
 import random, time
 import torch
 from se3et_amd import ops
-from se3et_amd._lib import lib
 
 C, H = 256, 4
 
@@ -46,16 +45,14 @@ def reference(proj, vt, embs, eqs, starts, lengths):
     return outs
 
 
-def run(A, lengths, eq, bias_variant, split, attn_variant, iters=40, check=False):
+def run(A, lengths, eq, iters=40, check=False):
     proj, vt, embs, eqs, starts = setup(A, lengths, eq)
     out = torch.zeros(A, proj.shape[1], C, device='cuda')
-    lib().se3_debug_set_bias_variant(bias_variant, split)
-    lib().se3_debug_set_attention_variant(attn_variant)
     for _ in range(3): call(proj, vt, embs, eqs, starts, lengths, out)
     if check:
         ref = reference(proj, vt, embs, eqs, starts, lengths)
         err = max(((out[:, s:s + n] - r).abs().max() / r.abs().max()).item() for s, n, r in zip(starts, lengths, ref))
-        print('   check A=%d %s eq=%d bias_variant=%d split=%d attn_variant=%d: rel err %.2e' % (A, lengths, eq, bias_variant, split, attn_variant, err))
+        print('   check A=%d %s eq=%d: rel err %.2e' % (A, lengths, eq, err))
     ops.KERNEL_TIMINGS = {}
     for _ in range(iters): call(proj, vt, embs, eqs, starts, lengths, out)
     torch.cuda.synchronize()
@@ -71,30 +68,20 @@ if __name__ == '__main__':
     torch.cuda.synchronize()
     shapes = [(6, (382, 350), True), (1, (382, 350), False), (6, (382,), True)]
     for A, lengths, eq in shapes:
-        for bv, sp, av in ((0, 0, 0), (2, 2, 1), (0, 8, 2), (0, 1, 3), (2, 0, 4)):
-            run(A, lengths, eq, bv, sp, av, iters=1, check=True)
-    bias_cfgs = [(0, 0), (0, 2), (0, 6), (2, 2), (0, 3)]
-    attn_cfgs = [0, 1, 2, 3, 4]
+        run(A, lengths, eq, iters=1, check=True)
     res = {}
     for rep in range(3):
-        order = [(s, b) for s in range(len(shapes)) for b in range(len(bias_cfgs))]
+        order = list(range(len(shapes)))
         random.shuffle(order)
-        for si, bi in order:
+        for si in order:
             A, lengths, eq = shapes[si]
-            av = attn_cfgs[bi % len(attn_cfgs)]
-            tb, ta, nb = run(A, lengths, eq, bias_cfgs[bi][0], bias_cfgs[bi][1], av)
-            res.setdefault(('bias', si, bias_cfgs[bi]), []).append(tb)
-            res.setdefault(('attn', si, av), []).append(ta)
+            tb, ta, nb = run(A, lengths, eq)
+            res.setdefault(('bias', si), []).append(tb)
+            res.setdefault(('attn', si), []).append(ta)
             res[('bytes', si)] = nb
     for si, (A, lengths, eq) in enumerate(shapes):
         nb = res[('bytes', si)]
+        tb, ta = min(res[('bias', si)]), min(res[('attn', si)])
         print('A=%d lengths=%s eq=%d  algorithmic %.1f MB' % (A, lengths, eq, nb / 1e6))
-        for b in bias_cfgs:
-            t = min(res[('bias', si, b)])
-            print('   bias variant %d split %2d : %6.1f us' % (b[0], b[1], t))
-        for av in attn_cfgs:
-            t = min(res[('attn', si, av)])
-            print('   attention variant %d    : %6.1f us' % (av, t))
-        tb = min(min(res[('bias', si, b)]) for b in bias_cfgs); ta = min(min(res[('attn', si, av)]) for av in attn_cfgs)
-        print('   best total %.1f us -> %.0f GB/s (%.1f%% of 8 TB/s)' % (tb + ta, nb / (tb + ta) / 1e3, nb / (tb + ta) / 1e3 / 80))
-    lib().se3_debug_set_bias_variant(0, 0); lib().se3_debug_set_attention_variant(0)
+        print('   logits kernel %6.1f us  attention kernel %6.1f us' % (tb, ta))
+        print('   total %.1f us -> %.0f GB/s (%.1f%% of 8 TB/s)' % (tb + ta, nb / (tb + ta) / 1e3, nb / (tb + ta) / 1e3 / 80))

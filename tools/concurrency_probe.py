@@ -21,7 +21,7 @@ def main():
     from se3et_amd.synthetic import make_pair
     cfg = make_cfg('se3ete')
     b = cfg.backbone
-    for item in filter(None, os.environ.get('PROBE_FLAGS', '').split(',')):      # e.g. PROBE_FLAGS=GRAM_KERNEL=0,ATTENTION_F16=0 (se3et_amd.ops switches)
+    for item in filter(None, os.environ.get('PROBE_FLAGS', '').split(',')):      # e.g. PROBE_FLAGS=GRAM_KERNEL=0,CROSS_EQ_BF16X6=0 (se3et_amd.ops switches)
         name, val = item.split('=')
         from se3et_amd import functional as _SF
         mod = ops if hasattr(ops, name) else _SF

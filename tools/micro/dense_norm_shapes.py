@@ -1,5 +1,5 @@
 """The unary layers of the bench pyramid (8 pairs stacked): dense layer + GroupNorm as today (GEMM, then three GroupNorm launches) against the
-fused kernel (csrc/dense_norm.hip: statistics in the epilogue) + the apply pass.  python tools/micro/dense_norm_shapes.py [target_chunks]"""
+fused kernel (csrc/dense_norm.hip: statistics in the epilogue) + the apply pass.  python tools/micro/dense_norm_shapes.py"""
 import os
 import sys
 
@@ -8,7 +8,6 @@ import torch
 
 from se3et_amd import functional as SF
 from se3et_amd import ops
-from se3et_amd._lib import lib
 
 SHAPES = [(480000, 64, 32), (480000, 32, 128), (480000, 64, 128), (480000, 128, 32), (310452, 32, 128), (310452, 128, 64), (310452, 64, 256),
           (310452, 128, 256), (310452, 256, 64), (128466, 64, 256), (128466, 256, 128), (128466, 128, 512), (128466, 256, 512),
@@ -29,8 +28,6 @@ def timed(fn, n=20):
 
 
 def main():
-    if len(sys.argv) > 1:
-        lib().se3_dense_norm_set_target_chunks(int(sys.argv[1]))
     torch.manual_seed(0)
     tot = [0.0, 0.0, 0.0]
     for rows, K, N in SHAPES:
