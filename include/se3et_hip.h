@@ -884,6 +884,45 @@ int se3_transformer_forward(const se3_transformer_plan_t* plan, const float* x_i
 int se3_linear_stream_segments(const float* x, int64_t rows, int in_features, int seg_channels, int64_t seg_stride, const void* weight_pieces,
                                const float* bias, int out_features, int apply_relu, float* out, int64_t out_row_stride, void* stream);
 
+/* ---- pair ground truth: nearest neighbour, overlap, correspondences, gt.info covariance (csrc/pair_geometry.hip, csrc/pair_grid.h) ------------
+ * The reference's get_nearest_neighbor (utils/pointcloud.py:11-22), compute_overlap / get_correspondences (utils/registration.py:149-173) and
+ * calibrate_ground_truth (threedmatch/utils.py:197-228) for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64; the arithmetic
+ * contract is the header comment of csrc/pair_geometry.hip.  Points are (rows, 3) on the device, float32 (elem 0) or float64 (elem 1), promoted
+ * on load; pair p owns rows [offsets_host[p], offsets_host[p + 1]) of a stacked array (HOST int64, num_pairs + 1 entries from 0);
+ * transforms_host is (num_pairs, 4, 4) float64 on the HOST (checked finite), applied to the SUPPORT cloud.  Indices are pair-local.
+ *   se3_pair_grid_build     the float64 cell grid over each pair's transformed support.  cell_hint > 0: the cell size (the ball radius);
+ *                           0: from the point density (nearest neighbour).  The workspace then serves any number of searches.
+ *   se3_pair_nearest_neighbor_stack   distances (nq) float64 and indices (nq) int64 of the exact nearest support point of every query row;
+ *                           the lowest index among equal distances; inf / -1 for an empty support.
+ *   se3_pair_ball_count_stack   row_offsets (nq + 1) int64 on the device: the exclusive scan of the per-row hit counts, the total last.
+ *   se3_pair_ball_fill_stack    out (total, 2) int64: (i, j) of every hit, rows ascending in i, j ascending within a row; row_offsets and
+ *                           total as the count call left them (the same grid, points and radius).
+ *   se3_pair_overlap_stack  out (num_pairs) float64 = count(d * d < radius * radius) / rows of the pair's nearest-neighbour distances (NaN
+ *                           for a pair without rows).
+ *   se3_pair_info_covariance_stack   out (num_pairs, 6, 6) float64 = sum G^T G, G = [I3 | -[p]x], over the transformed src points
+ *                           src[selected[k]] of each pair (selected: pair-local int64 on the device, pair p's on
+ *                           [selected_offsets_host[p], selected_offsets_host[p + 1])); the zero matrix without a point.
+ *   se3_debug_pair_*_host   the same search core (pair_grid.h) on HOST memory for one pair: every pointer a host pointer.  ball: counts (nq)
+ *                           always; out (capacity, 2) may be NULL; *total may exceed capacity (rows that do not fit are not written). */
+#define SE3_PAIR_MAX_PAIRS 32
+size_t se3_pair_grid_workspace_bytes(int64_t ns_total, int num_pairs);
+int se3_pair_grid_build(const void* s_points, int elem, const int64_t* s_offsets_host, int num_pairs, const double* transforms_host,
+                        double cell_hint, void* workspace, size_t workspace_bytes, void* stream);
+int se3_pair_nearest_neighbor_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                    const int64_t* q_offsets_host, int num_pairs, double* distances, int64_t* indices, void* stream);
+int se3_pair_ball_count_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                              const int64_t* q_offsets_host, int num_pairs, double radius, int64_t* row_offsets, void* stream);
+int se3_pair_ball_fill_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                             const int64_t* q_offsets_host, int num_pairs, double radius, const int64_t* row_offsets, int64_t total,
+                             int64_t* out, void* stream);
+int se3_pair_overlap_stack(const double* nn_distances, const int64_t* q_offsets_host, int num_pairs, double radius, double* out, void* stream);
+int se3_pair_info_covariance_stack(const void* src_points, int elem, const int64_t* s_offsets_host, const double* transforms_host,
+                                   const int64_t* selected, const int64_t* selected_offsets_host, int num_pairs, double* out, void* stream);
+int se3_debug_pair_nearest_neighbor_host(const void* q_points, int64_t nq, const void* s_points, int64_t ns, int elem, const double* transform,
+                                         double* distances, int64_t* indices);
+int se3_debug_pair_ball_host(const void* q_points, int64_t nq, const void* s_points, int64_t ns, int elem, const double* transform,
+                             double radius, int64_t* counts, int64_t* out, int64_t capacity, int64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,391 @@
+// Uniform float64 grid over the TRANSFORMED support cloud of each pair of a stacked call, and the search core of csrc/pair_geometry.hip.
+//
+// The grid is only an accelerator: every answer is defined by the arithmetic contract in pair_geometry.hip (transform by the documented fma
+// chain, d^2 = (dx dx + dy dy) + dz dz unfused, strict tests, the lowest index among equal distances), and the walks below visit every
+// cell that can hold a point passing the test.
+//
+// The cell walk, the shell termination rule and the candidate test are __host__ __device__: the kernels run them with one wave per query
+// row (nearest neighbour: `lane` of 64) or one thread per row (ball query), and se3_debug_pair_nearest_neighbor_host /
+// se3_debug_pair_ball_host run the same text on host memory over a grid built by pg_build_host (tests/test_pair_geometry_cpu.py).
+//
+// Layout of a grid workspace (pg_carve): meta[P], cells[P][kPairCellCap + 1] (cells[c] .. cells[c + 1] is cell c's run of `sorted`),
+// moved (3 float64 per support point, in input order: the transformed cloud), sorted (3 float64 per point, cell by cell), sorted_idx (the
+// pair-local index of each sorted point).  The order of the points INSIDE a cell follows the arrival of the scatter's integer atomics; no
+// result depends on it: the nearest neighbour reduces on (d^2, index), the ball query sorts each row, counts are integers.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include <vector>
+
+#define PG_HD __host__ __device__ __forceinline__
+
+constexpr int kPairGridCap = 64;                                       // cells per axis at most (kGridCap of radius_neighbors.hip)
+constexpr int kPairCellCap = kPairGridCap * kPairGridCap * kPairGridCap;
+constexpr int kPairMaxPairs = 32;                                      // pairs per stacked call (SE3_PAIR_MAX_PAIRS)
+constexpr double kPairSlack = 1e-14;                                   // relative safety of every pruning bound: ~90 float64 roundings
+
+struct PairGridMeta {
+  double T[12];          // rows of [R | t]
+  double org[3], top[3];  // exact bounding box of the transformed support
+  double cell, inv_cell;
+  int dim[3], ncells;
+  int64_t s_start, ns;   // rows of this pair in the stacked support
+};
+
+struct PairGridView {
+  const PairGridMeta* meta;     // [P]
+  const int* cells;             // [P][kPairCellCap + 1]
+  const double* sorted;         // [ns_total][3]
+  const int* sorted_idx;        // [ns_total]
+};
+
+// pair p's rows [start[p], start[p + 1]) of a stacked array; passed to kernels by value
+struct PairRows {
+  int64_t start[kPairMaxPairs + 1];
+  int n;
+};
+
+PG_HD double pg_load(const void* p, int elem, int64_t i) { return elem ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
+
+// (fma(R[k][2], z, fma(R[k][1], y, R[k][0] * x)) + t[k])_k
+PG_HD void pg_transform(const double* T, double x, double y, double z, double* out) {
+#pragma clang fp contract(off)
+  for (int k = 0; k < 3; k++) {
+    const double a = T[4 * k] * x;
+    const double b = __builtin_fma(T[4 * k + 1], y, a);
+    const double c = __builtin_fma(T[4 * k + 2], z, b);
+    out[k] = c + T[4 * k + 3];
+  }
+}
+
+// the candidate test's distance: (dx dx + dy dy) + dz dz, every product and sum rounded on its own
+PG_HD double pg_dist2(const double* q, const double* s) {
+#pragma clang fp contract(off)
+  const double dx = q[0] - s[0], dy = q[1] - s[1], dz = q[2] - s[2];
+  const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  const double a = xx + yy;
+  return a + zz;
+}
+
+// floor((v - org) / cell) kept inside [-1, dim] (a NaN gives -1); monotone in v
+PG_HD int pg_cell_floor(double v, double org, double inv_cell, int dim) {
+  const double f = floor((v - org) * inv_cell);
+  if (!(f >= 0.0)) return -1;
+  return f >= (double)dim ? dim : (int)f;
+}
+// the cell a point is filed under: the same value clamped into the grid (the last cell also holds what the axis cap cut off)
+PG_HD int pg_cell_coord(double v, double org, double inv_cell, int dim) {
+  const int c = pg_cell_floor(v, org, inv_cell, dim);
+  return c < 0 ? 0 : (c >= dim ? dim - 1 : c);
+}
+PG_HD int pg_cell_of(const PairGridMeta& m, const double* p) {
+  const int cx = pg_cell_coord(p[0], m.org[0], m.inv_cell, m.dim[0]);
+  const int cy = pg_cell_coord(p[1], m.org[1], m.inv_cell, m.dim[1]);
+  const int cz = pg_cell_coord(p[2], m.org[2], m.inv_cell, m.dim[2]);
+  return cx + m.dim[0] * (cy + m.dim[1] * cz);
+}
+
+// Grid of n points inside [mn, mx].  cell_hint > 0 (ball query: the radius) is the cell size; otherwise it comes from the density, the
+// box volume over n (one point per cell if the cloud filled its box).  Either is raised until no axis needs more than kPairGridCap cells.
+PG_HD void pg_make_grid(const double* mn, const double* mx, int64_t n, double cell_hint, PairGridMeta* m) {
+  double ext[3], big = 0.0;
+  for (int d = 0; d < 3; d++) {
+    ext[d] = n > 0 ? mx[d] - mn[d] : 0.0;
+    if (!(ext[d] >= 0.0) || ext[d] > 1.7e308) ext[d] = 0.0;          // (non-finite points: any grid is safe, no walk leaves it)
+    big = fmax(big, ext[d]);
+  }
+  double cell = cell_hint;
+  if (!(cell > 0.0)) {
+    double vol = 1.0;
+    for (int d = 0; d < 3; d++) vol *= fmax(ext[d], 1e-3 * big);
+    cell = n > 0 ? cbrt(vol / (double)n) : 0.0;
+  }
+  cell = fmax(cell, big / (double)(kPairGridCap - 1));
+  if (!(cell > 0.0) || cell > 1.7e308) cell = 1.0;                     // one point, or all points equal
+  m->cell = cell;
+  m->inv_cell = 1.0 / cell;
+  m->ncells = 1;
+  for (int d = 0; d < 3; d++) {
+    m->org[d] = n > 0 ? mn[d] : 0.0;
+    m->top[d] = n > 0 ? mx[d] : 0.0;
+    const int dim = pg_cell_coord(m->top[d], m->org[d], m->inv_cell, kPairGridCap) + 1;
+    m->dim[d] = dim;
+    m->ncells *= dim;
+  }
+}
+
+// ---- nearest neighbour ----------------------------------------------------------------------------------------------------------------
+// The cells of Chebyshev ring k around cell c, clipped to the grid, as runs of consecutive cells [a, b] (cells are linear in x).
+template <class Run>
+PG_HD void pg_ring_runs(const PairGridMeta& m, const int* c, int k, Run&& run) {
+  const int x0 = c[0] - k < 0 ? 0 : c[0] - k, x1 = c[0] + k >= m.dim[0] ? m.dim[0] - 1 : c[0] + k;
+  const int y0 = c[1] - k < 0 ? 0 : c[1] - k, y1 = c[1] + k >= m.dim[1] ? m.dim[1] - 1 : c[1] + k;
+  const int z0 = c[2] - k < 0 ? 0 : c[2] - k, z1 = c[2] + k >= m.dim[2] ? m.dim[2] - 1 : c[2] + k;
+  for (int z = z0; z <= z1; z++)
+    for (int y = y0; y <= y1; y++) {
+      const int row = m.dim[0] * (y + m.dim[1] * z);
+      if (z - c[2] == k || c[2] - z == k || y - c[1] == k || c[1] - y == k) {
+        run(row + x0, row + x1);                                       // a face row of the ring: all of its x
+      } else {
+        if (c[0] - k >= 0) run(row + c[0] - k, row + c[0] - k);        // an inner row: its two end cells
+        if (c[0] + k < m.dim[0]) run(row + c[0] + k, row + c[0] + k);
+      }
+    }
+}
+
+// Shell termination rule: a lower bound of d^2 from q to every support point filed outside rings 0 .. k around c, +inf when those rings
+// cover the grid.  A cell outside lies beyond ring k on at least one axis and side; on that axis its points are at least `gap` from q (the
+// face of the ring, less kPairSlack for the roundings of the filing), on the other axes at least q's distance to the exact bounding box.
+PG_HD double pg_shell_bound2(const PairGridMeta& m, const double* q, const int* c, int k) {
+  double box2[3];
+  for (int d = 0; d < 3; d++) {
+    const double o = fmax(fmax(m.org[d] - q[d], q[d] - m.top[d]), 0.0);
+    box2[d] = o * o;
+  }
+  double best = INFINITY;
+  for (int a = 0; a < 3; a++) {
+    const double others = box2[(a + 1) % 3] + box2[(a + 2) % 3];
+    for (int side = 0; side < 2; side++) {
+      if (side == 0 ? c[a] - k - 1 < 0 : c[a] + k + 1 > m.dim[a] - 1) continue;   // no cell left on this side
+      const double face = m.org[a] + (double)(side == 0 ? c[a] - k : c[a] + k + 1) * m.cell;
+      double gap = side == 0 ? q[a] - face : face - q[a];
+      gap = fmax(gap - kPairSlack * (fabs(m.org[a]) + fabs(face) + fabs(q[a])), 0.0);
+      best = fmin(best, gap * gap + others);
+    }
+  }
+  return best * (1.0 - kPairSlack);
+}
+
+// Candidate test of the nearest neighbour: smaller d^2 wins, the lower index among equal d^2.
+PG_HD void pg_nearest_update(double d2, int j, double* best_d2, int* best_j) {
+  if (d2 < *best_d2 || (d2 == *best_d2 && j < *best_j)) *best_d2 = d2, *best_j = j;
+}
+
+// Exact nearest neighbour of q among pair `m`'s support.  Lanes lane, lane + nlanes, .. take the points of each run of a ring; `reduce`
+// makes (d^2, index) the minimum over the lanes after every ring (the host calls it with one lane and a no-op).  The rings widen until the
+// best d^2 found is no larger than the bound of everything outside them.  Empty support: d^2 = +inf, index -1.
+template <class Reduce>
+PG_HD void pg_nearest(const PairGridView& g, int p, const double* q, int lane, int nlanes, Reduce&& reduce, double* out_d2, int* out_j) {
+  const PairGridMeta& m = g.meta[p];
+  const int* cells = g.cells + (size_t)p * (kPairCellCap + 1);
+  const double* pts = g.sorted + 3 * m.s_start;
+  const int* idx = g.sorted_idx + m.s_start;
+  int c[3];
+  for (int d = 0; d < 3; d++) c[d] = pg_cell_coord(q[d], m.org[d], m.inv_cell, m.dim[d]);
+  double best = INFINITY;
+  int best_j = -1;
+  for (int k = 0; k < kPairGridCap; k++) {
+    pg_ring_runs(m, c, k, [&](int a, int b) {
+      const int end = cells[b + 1];
+      for (int t = cells[a] + lane; t < end; t += nlanes) pg_nearest_update(pg_dist2(q, pts + 3 * (size_t)t), idx[t], &best, &best_j);
+    });
+    reduce(&best, &best_j);
+    if (best <= pg_shell_bound2(m, q, c, k)) break;
+  }
+  *out_d2 = best;
+  *out_j = best_j;
+}
+
+// ---- ball query -------------------------------------------------------------------------------------------------------------------------
+// hit(j) for every support point of pair `m` with d^2 < r2, in cell order.  The block of cells comes from q -+ r widened by kPairSlack, so
+// a point whose rounded d^2 passes while its true distance is a rounding beyond r is still visited.
+template <class Hit>
+PG_HD void pg_ball_walk(const PairGridView& g, int p, const double* q, double r, double r2, Hit&& hit) {
+  const PairGridMeta& m = g.meta[p];
+  if (m.ns <= 0) return;
+  const int* cells = g.cells + (size_t)p * (kPairCellCap + 1);
+  const double* pts = g.sorted + 3 * m.s_start;
+  const int* idx = g.sorted_idx + m.s_start;
+  int lo[3], hi[3];
+  for (int d = 0; d < 3; d++) {
+    const double rr = r + kPairSlack * (r + fabs(q[d]) + fabs(m.org[d]));
+    lo[d] = pg_cell_coord(q[d] - rr, m.org[d], m.inv_cell, m.dim[d]);
+    hi[d] = pg_cell_floor(q[d] + rr, m.org[d], m.inv_cell, m.dim[d]);
+    if (hi[d] < 0) return;                                             // the ball ends below the box (or q is NaN)
+    if (hi[d] > m.dim[d] - 1) hi[d] = m.dim[d] - 1;
+  }
+  for (int z = lo[2]; z <= hi[2]; z++)
+    for (int y = lo[1]; y <= hi[1]; y++) {
+      const int row = m.dim[0] * (y + m.dim[1] * z);
+      const int end = cells[row + hi[0] + 1];
+      for (int t = cells[row + lo[0]]; t < end; t++)
+        if (pg_dist2(q, pts + 3 * (size_t)t) < r2) hit(idx[t]);
+    }
+}
+
+PG_HD int64_t pg_ball_count(const PairGridView& g, int p, const double* q, double r, double r2) {
+  int64_t n = 0;
+  pg_ball_walk(g, p, q, r, r2, [&](int) { n++; });
+  return n;
+}
+
+// Writes row i's hits as (i, j) pairs, j ascending, to out[0, 2 * capacity): each hit is inserted into the sorted part written so far
+// (rows are short).  Returns the number of hits met; never writes past capacity.
+PG_HD int64_t pg_ball_fill(const PairGridView& g, int p, const double* q, double r, double r2, int64_t i, int64_t* out, int64_t capacity) {
+  int64_t n = 0;
+  pg_ball_walk(g, p, q, r, r2, [&](int j) {
+    if (n < capacity) {
+      int64_t k = n;
+      for (; k > 0 && out[2 * (k - 1) + 1] > j; k--) out[2 * k + 1] = out[2 * (k - 1) + 1];
+      out[2 * k + 1] = j;
+      out[2 * n] = i;
+    }
+    n++;
+  });
+  return n;
+}
+
+// ---- workspace ----------------------------------------------------------------------------------------------------------------------------
+struct PairGridLayout {
+  PairGridMeta* meta;
+  int* cells;
+  double* moved;
+  double* sorted;
+  int* sorted_idx;
+  PairGridView view() const { return PairGridView{meta, cells, sorted, sorted_idx}; }
+};
+
+inline size_t pg_carve(int64_t ns_total, int num_pairs, char* base, PairGridLayout* L) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    off = (off + 255) & ~(size_t)255;
+    char* p = base ? base + off : nullptr;
+    off += bytes;
+    return p;
+  };
+  const size_t n = (size_t)(ns_total > 0 ? ns_total : 1), P = (size_t)(num_pairs > 0 ? num_pairs : 1);
+  PairGridLayout l;
+  l.meta = (PairGridMeta*)take(sizeof(PairGridMeta) * P);
+  l.cells = (int*)take(sizeof(int) * P * (kPairCellCap + 1));
+  l.moved = (double*)take(sizeof(double) * 3 * n);
+  l.sorted = (double*)take(sizeof(double) * 3 * n);
+  l.sorted_idx = (int*)take(sizeof(int) * n);
+  if (L) *L = l;
+  return (off + 255) & ~(size_t)255;
+}
+
+// The grid build on host memory, serial, over a workspace laid out by pg_carve in `base` (the debug entries).
+inline void pg_build_host(const void* s_points, int elem, const PairRows& rows, const double* transforms, double cell_hint, PairGridLayout& G) {
+  for (int p = 0; p < rows.n; p++) {
+    PairGridMeta& m = G.meta[p];
+    const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
+    for (int k = 0; k < 12; k++) m.T[k] = transforms[16 * p + k];
+    m.s_start = s0, m.ns = n;
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = s0; i < s0 + n; i++) {
+      pg_transform(m.T, pg_load(s_points, elem, 3 * i), pg_load(s_points, elem, 3 * i + 1), pg_load(s_points, elem, 3 * i + 2), G.moved + 3 * i);
+      for (int d = 0; d < 3; d++) mn[d] = fmin(mn[d], G.moved[3 * i + d]), mx[d] = fmax(mx[d], G.moved[3 * i + d]);
+    }
+    pg_make_grid(mn, mx, n, cell_hint, &m);
+    int* cells = G.cells + (size_t)p * (kPairCellCap + 1);
+    for (int c = 0; c <= m.ncells; c++) cells[c] = 0;
+    for (int64_t i = s0; i < s0 + n; i++) cells[pg_cell_of(m, G.moved + 3 * i)]++;
+    int run = 0;
+    for (int c = 0; c <= m.ncells; c++) {
+      const int v = cells[c];
+      cells[c] = run;
+      run += v;
+    }
+    std::vector<int> cursor(cells, cells + m.ncells);
+    for (int64_t i = s0; i < s0 + n; i++) {
+      const int pos = cursor[(size_t)pg_cell_of(m, G.moved + 3 * i)]++;
+      for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
+      G.sorted_idx[s0 + pos] = (int)(i - s0);
+    }
+  }
+}
+
+#ifdef __HIPCC__
+// ---- the build as kernels, batched over pairs --------------------------------------------------------------------------------------------
+struct PairTransforms {
+  double T[kPairMaxPairs][12];
+};
+
+constexpr int kPairBoundsThreads = 256;
+
+// one workgroup per pair: transform the support into `moved`, exact bounding box, grid geometry
+__global__ __launch_bounds__(kPairBoundsThreads) void pair_grid_bounds_kernel(const void* __restrict__ s, int elem, PairRows rows, PairTransforms tf,
+                                                                double cell_hint, PairGridLayout G) {
+  __shared__ double sh[kPairBoundsThreads / 64];
+  const int p = blockIdx.x;
+  const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
+  double T[12];
+  for (int k = 0; k < 12; k++) T[k] = tf.T[p][k];
+  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int64_t i = s0 + threadIdx.x; i < s0 + n; i += kPairBoundsThreads) {
+    double w[3];
+    pg_transform(T, pg_load(s, elem, 3 * i), pg_load(s, elem, 3 * i + 1), pg_load(s, elem, 3 * i + 2), w);
+    for (int d = 0; d < 3; d++) {
+      G.moved[3 * i + d] = w[d];
+      mn[d] = fmin(mn[d], w[d]);
+      mx[d] = fmax(mx[d], w[d]);
+    }
+  }
+  double r[6];
+#pragma unroll
+  for (int d = 0; d < 6; d++) {
+    double v = d < 3 ? mn[d] : -mx[d - 3];
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = sh[0];
+    for (int w = 1; w < kPairBoundsThreads / 64; w++) t = fmin(t, sh[w]);
+    r[d] = t;
+  }
+  if (threadIdx.x == 0) {
+    PairGridMeta* m = G.meta + p;
+    for (int k = 0; k < 12; k++) m->T[k] = T[k];
+    m->s_start = s0, m->ns = n;
+    const double lo[3] = {r[0], r[1], r[2]}, hi[3] = {-r[3], -r[4], -r[5]};
+    pg_make_grid(lo, hi, n, cell_hint, m);
+  }
+}
+
+// cell histogram (the only atomics of the build: integer adds, order-free)
+__global__ __launch_bounds__(256) void pair_grid_count_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ns_total) return;
+  int p = 0;
+  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  atomicAdd(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1);
+}
+
+// one workgroup per pair: counts -> INCLUSIVE ends (the scatter counts each end down to its cell's start); cells[ncells] = ns
+__global__ __launch_bounds__(1024) void pair_grid_scan_kernel(PairGridLayout G) {
+  __shared__ int sh[1024];
+  const int p = blockIdx.x, t = threadIdx.x;
+  const int n = G.meta[p].ncells;
+  int* a = G.cells + (size_t)p * (kPairCellCap + 1);
+  const int chunk = (n + 1023) / 1024;
+  const int lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+  int sum = 0;
+  for (int i = lo; i < hi; i++) sum += a[i];
+  sh[t] = sum;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int v = t >= off ? sh[t - off] : 0;
+    __syncthreads();
+    sh[t] += v;
+    __syncthreads();
+  }
+  int run = sh[t] - sum;
+  for (int i = lo; i < hi; i++) {
+    run += a[i];
+    a[i] = run;
+  }
+  if (t == 1023) a[n] = sh[1023];
+}
+
+__global__ __launch_bounds__(256) void pair_grid_scatter_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ns_total) return;
+  int p = 0;
+  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  const int64_t s0 = rows.start[p];
+  const int pos = atomicSub(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1) - 1;
+  for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
+  G.sorted_idx[s0 + pos] = (int)(i - s0);
+}
+#endif  // __HIPCC__

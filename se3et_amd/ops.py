@@ -2210,3 +2210,141 @@ def benchmark_summary(rows, is_gt, group_lengths, kitti, inlier_ratio_threshold,
                                       float(inlier_ratio_threshold), float(rmse_threshold), float(rre_threshold), float(rte_threshold),
                                       groups.data_ptr(), overall.data_ptr(), _stream()), 'se3_benchmark_summary')
     return groups[:G], overall
+
+
+# ---- pair ground truth: nearest neighbour, overlap, correspondences, gt.info covariance (csrc/pair_geometry.hip) ---------------------------
+PAIR_MAX_PAIRS = 32          # SE3_PAIR_MAX_PAIRS: pairs per stacked call (se3et_amd/pair_geometry.py chunks longer lists)
+_ws_pair_grid = Workspace(1 << 22)          # the cell grid of the call in flight on a stream
+
+
+def _pair_points(t, name):
+    """(rows, 3) float32 or float64 on the device, as it is (the kernels promote on load); returns (tensor, elem flag)."""
+    if torch.is_tensor(t) and t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError('%s must be float32 or float64, got %s' % (name, t.dtype))
+    t = _req(t, t.dtype if torch.is_tensor(t) else torch.float32, name, 2)
+    if t.shape[1] != 3:
+        raise RuntimeError('%s must be (rows, 3)' % name)
+    return t, 1 if t.dtype == torch.float64 else 0
+
+
+def _pair_offsets(lengths, rows, what):
+    lengths = [int(n) for n in lengths]
+    if len(lengths) > PAIR_MAX_PAIRS or any(n < 0 for n in lengths) or sum(lengths) != rows:
+        raise RuntimeError('%s: at most %d pairs per call, with lengths that sum to the %d rows given' % (what, PAIR_MAX_PAIRS, rows))
+    offsets = [0]
+    for n in lengths:
+        offsets.append(offsets[-1] + n)
+    return _i64_array(offsets)
+
+
+def _pair_transforms(transforms, P, what):
+    """(P, 4, 4) float64 on the HOST (the library checks it and passes it to the kernels by value)."""
+    t = transforms.detach().to(device='cpu', dtype=torch.float64).contiguous()
+    if tuple(t.shape) != (P, 4, 4):
+        raise RuntimeError('%s: transforms must be (%d, 4, 4)' % (what, P))
+    return t
+
+
+_pair_dummy = {}
+
+
+def _dp(t):
+    """data_ptr of a tensor, or of a small per-device buffer for an empty one (the library refuses null pointers; nothing is read or written
+    through the pointer of an array without rows)."""
+    if t.numel():
+        return t.data_ptr()
+    d = _pair_dummy.get(t.device)
+    if d is None:
+        d = _pair_dummy[t.device] = torch.zeros((64,), dtype=torch.uint8, device=t.device)
+    return d.data_ptr()
+
+
+class PairGrid:
+    """The cell grid of a stacked support (pair_grid_build), valid until the next build on the same stream."""
+    __slots__ = ('ws', 'nbytes', 'ns_total', 'num_pairs', 'device')
+
+    def __init__(self, ws, nbytes, ns_total, num_pairs):
+        self.ws, self.nbytes, self.ns_total, self.num_pairs, self.device = ws, nbytes, ns_total, num_pairs, ws.device
+
+
+def pair_grid_build(s_points, s_lengths, transforms, cell_hint=0.0):
+    """HIP: the float64 cell grid over the transformed support of each pair.  s_points (total, 3) float32 / float64 on the device, pair p on
+    the next s_lengths[p] rows (host ints); transforms (P, 4, 4), moved to the host as float64; cell_hint: the ball radius, or 0 for the
+    nearest-neighbour grid.  Returns a PairGrid for pair_nearest_neighbor_stack / pair_ball_*_stack."""
+    s, elem = _pair_points(s_points, 's_points')
+    P = len(s_lengths)
+    offsets = _pair_offsets(s_lengths, s.shape[0], 'pair_grid_build')
+    T = _pair_transforms(transforms, P, 'pair_grid_build')
+    nbytes = lib().se3_pair_grid_workspace_bytes(s.shape[0], P)
+    stream = _stream()
+    ws = _ws_pair_grid.get(s.device, stream.value, nbytes)
+    check(lib().se3_pair_grid_build(_dp(s), elem, offsets, P, T.data_ptr(), float(cell_hint), ws.data_ptr(), nbytes, stream),
+          'se3_pair_grid_build')
+    return PairGrid(ws, nbytes, s.shape[0], P)
+
+
+def _pair_query(grid, q_points, q_lengths, what):
+    q, elem = _pair_points(q_points, 'q_points')
+    if q.device != grid.device or len(q_lengths) != grid.num_pairs:
+        raise RuntimeError('%s: %d pairs on %s expected' % (what, grid.num_pairs, grid.device))
+    return q, elem, _pair_offsets(q_lengths, q.shape[0], what)
+
+
+def pair_nearest_neighbor_stack(grid, q_points, q_lengths):
+    """HIP: exact nearest support point of every query row in its own pair's transformed support.  Returns (distances (nq,) float64,
+    indices (nq,) int64 pair-local; inf / -1 for an empty support)."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'pair_nearest_neighbor_stack')
+    dist = torch.empty((q.shape[0],), dtype=torch.float64, device=q.device)
+    idx = torch.empty((q.shape[0],), dtype=torch.int64, device=q.device)
+    check(lib().se3_pair_nearest_neighbor_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
+                                                _dp(dist), _dp(idx), _stream()), 'se3_pair_nearest_neighbor_stack')
+    return dist, idx
+
+
+def pair_ball_count_stack(grid, q_points, q_lengths, radius):
+    """HIP: pass 1 of the ball query.  Returns row_offsets (nq + 1,) int64 on the device: the exclusive scan of the hits per query row."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'pair_ball_count_stack')
+    row_offsets = torch.empty((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
+    check(lib().se3_pair_ball_count_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
+                                          float(radius), row_offsets.data_ptr(), _stream()), 'se3_pair_ball_count_stack')
+    return row_offsets
+
+
+def pair_ball_fill_stack(grid, q_points, q_lengths, radius, row_offsets, total):
+    """HIP: pass 2.  Returns (total, 2) int64: (i, j) pair-local, rows ascending in i, j ascending within a row."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'pair_ball_fill_stack')
+    row_offsets = _req(row_offsets, torch.int64, 'row_offsets', 1)
+    if row_offsets.shape[0] != q.shape[0] + 1 or row_offsets.device != q.device:
+        raise RuntimeError('pair_ball_fill_stack: row_offsets of pair_ball_count_stack expected')
+    out = torch.empty((int(total), 2), dtype=torch.int64, device=q.device)
+    check(lib().se3_pair_ball_fill_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
+                                         float(radius), row_offsets.data_ptr(), int(total), _dp(out), _stream()),
+          'se3_pair_ball_fill_stack')
+    return out
+
+
+def pair_overlap_stack(nn_distances, q_lengths, radius):
+    """HIP: count(d d < r r) / rows per pair of stacked nearest-neighbour distances (float64).  Returns (P,) float64; NaN without rows."""
+    d = _req(nn_distances, torch.float64, 'nn_distances', 1)
+    P = len(q_lengths)
+    offsets = _pair_offsets(q_lengths, d.shape[0], 'pair_overlap_stack')
+    out = torch.empty((P,), dtype=torch.float64, device=d.device)
+    check(lib().se3_pair_overlap_stack(_dp(d), offsets, P, float(radius), _dp(out), _stream()), 'se3_pair_overlap_stack')
+    return out
+
+
+def pair_info_covariance_stack(src_points, s_lengths, transforms, selected, selected_lengths):
+    """HIP: the gt.info covariance sum G^T G over the transformed src points src[selected] of each pair (selected: pair-local int64 on the
+    device, pair p's the next selected_lengths[p] entries).  Returns (P, 6, 6) float64."""
+    s, elem = _pair_points(src_points, 'src_points')
+    sel = _req(selected, torch.int64, 'selected', 1)
+    P = len(s_lengths)
+    if len(selected_lengths) != P or sel.device != s.device:
+        raise RuntimeError('pair_info_covariance_stack: one selection per pair, on %s' % s.device)
+    s_off = _pair_offsets(s_lengths, s.shape[0], 'pair_info_covariance_stack')
+    k_off = _pair_offsets(selected_lengths, sel.shape[0], 'pair_info_covariance_stack')
+    T = _pair_transforms(transforms, P, 'pair_info_covariance_stack')
+    out = torch.empty((P, 6, 6), dtype=torch.float64, device=s.device)
+    check(lib().se3_pair_info_covariance_stack(_dp(s), elem, s_off, T.data_ptr(), _dp(sel), k_off, P, _dp(out), _stream()),
+          'se3_pair_info_covariance_stack')
+    return out
