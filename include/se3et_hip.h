@@ -703,6 +703,48 @@ int se3_ransac_correspondences_stack(const float* src_points, const float* ref_p
                                      const int32_t* hypothesis_indices, void* workspace, size_t workspace_bytes, float* transforms,
                                      float* fitness, float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts, float* err_sums,
                                      void* stream);
+/* The same with Open3D's correspondence checkers (registration_with_ransac_from_feats, geotransformer/utils/open3d.py:133-166); the kernels
+ * are shared.  edge_length_similarity t in (0, 1] (0: off): before the fit, a hypothesis is rejected if two of its sampled correspondences
+ * a, b have |s_a - s_b| < t |r_a - r_b| or |r_a - r_b| < t |s_a - s_b| (float64).  check_distance != 0: after the fit, it is rejected if a
+ * sampled correspondence has d^2 > distance_threshold^2 in the scoring arithmetic.  A rejected hypothesis scores 0 inliers.  passed
+ * (num_pairs, H) uint8 or NULL: 1 for a hypothesis with a valid sample that no checker rejected.  With t = 0 and check_distance = 0 every
+ * output is bit-identical to se3_ransac_correspondences_stack.  Workspace as above. */
+int se3_ransac_correspondences_checked_stack(const float* src_points, const float* ref_points, const int64_t* offsets, int num_pairs,
+                                             float distance_threshold, int ransac_n, int num_iterations, uint64_t seed,
+                                             const int32_t* hypothesis_indices, double edge_length_similarity, int check_distance,
+                                             void* workspace, size_t workspace_bytes, float* transforms, float* fitness,
+                                             float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts, float* err_sums, uint8_t* passed,
+                                             void* stream);
+
+/* ---- feature-space matching for stacked pairs (csrc/feature_nn.hip) ---------------------------------------------------------------------
+ * The nearest neighbour in descriptor space of every row in the other cloud of its pair, both directions in one call, without an (N, M)
+ * array: extract_correspondences_from_feats (geotransformer/modules/registration/matching.py:135-170) and extract_corr_indices_from_feats
+ * (utils/registration.py:179-212).  ref_feats (num_ref_rows, channels) / src_feats (num_src_rows, channels) float32; pair p owns rows
+ * [ref_offsets[p], ref_offsets[p+1]) and [src_offsets[p], src_offsets[p+1]) (int64, DEVICE, num_pairs + 1 entries from 0 to the row count).
+ * Candidates are ranked by v = (|x|^2 - 2 x.y) + |y|^2 with float32 MFMA products (x the query row); among equal v the lowest index wins; a
+ * NaN or infinite v is never chosen.  Outputs per ref row: nn_src_indices (pair-local int64, -1 without a candidate) and
+ * nn_src_sq_distances (float32, sum_k (x_k - y_k)^2 recomputed for the winner, +inf for -1); the same per src row in nn_ref_*.  Results are
+ * bit-identical from run to run and for a pair alone or in any batch.  workspace: se3_feature_nn_workspace_bytes bytes (O(rows)).  Three
+ * launches, no host synchronisation.
+ *   se3_feature_corr_count_stack   entry_offsets (num_ref_rows + num_src_rows + 1) int64: the exclusive scan of the entries each element of
+ *       the pair-major sequence [ref rows of pair 0, src rows of pair 0, ref rows of pair 1, ...] contributes, the total last; pair p's
+ *       entries are [entry_offsets[ref_offsets[p] + src_offsets[p]], entry_offsets[ref_offsets[p+1] + src_offsets[p+1]]).
+ *       mode 0: (i, nn_src(i)) per ref row; 1: those with nn_ref(nn_src(i)) == i; 2: the union of (i, nn_src(i)) and (nn_ref(j), j) without
+ *       duplicates in row-major (i, j) order; 3: the ref rows' entries followed by the src rows' (nn_ref(j), j), duplicates kept.  A row
+ *       with index -1 contributes nothing.
+ *   se3_feature_corr_fill_stack    ref_corr_indices / src_corr_indices (total) int64, pair-local, with the same arrays, mode and offsets. */
+size_t se3_feature_nn_workspace_bytes(int64_t num_ref_rows, int64_t num_src_rows);
+int se3_feature_nn_stack(const float* ref_feats, const float* src_feats, const int64_t* ref_offsets, const int64_t* src_offsets,
+                         int num_pairs, int64_t num_ref_rows, int64_t num_src_rows, int channels, void* workspace, size_t workspace_bytes,
+                         int64_t* nn_src_indices, float* nn_src_sq_distances, int64_t* nn_ref_indices, float* nn_ref_sq_distances,
+                         void* stream);
+int se3_feature_corr_count_stack(const int64_t* nn_src_indices, const int64_t* nn_ref_indices, const int64_t* ref_offsets,
+                                 const int64_t* src_offsets, int num_pairs, int64_t num_ref_rows, int64_t num_src_rows, int mode,
+                                 int64_t* entry_offsets, void* stream);
+int se3_feature_corr_fill_stack(const int64_t* nn_src_indices, const int64_t* nn_ref_indices, const int64_t* ref_offsets,
+                                const int64_t* src_offsets, int num_pairs, int64_t num_ref_rows, int64_t num_src_rows, int mode,
+                                const int64_t* entry_offsets, int64_t total, int64_t* ref_corr_indices, int64_t* src_corr_indices,
+                                void* stream);
 
 /* ---- eval.py's benchmark metrics for stacked pairs (csrc/benchmark.hip) ---------------------------------------------------------------
  * The per-pair metrics and summaries of experiments/se3ete.3dmatch/eval.py:42-357 and experiments/se3eti.kitti/eval.py:32-185.  Every call

@@ -16,6 +16,12 @@
 //      so a hypothesis needs at least one inlier to win.
 //   6. / 7. All H hypotheses are evaluated (no early exit); the winner's own fit is returned (no refit).
 // Non-finite correspondences are never inliers; a hypothesis with a non-finite (or, given explicitly, out-of-range) sample has 0 inliers.
+// Optional checkers (se3_ransac_correspondences_checked_stack; Open3D's CorrespondenceCheckerBasedOnEdgeLength / ...BasedOnDistance, which
+// registration_with_ransac_from_feats of geotransformer/utils/open3d.py:133-166 passes).  A rejected hypothesis scores 0 inliers:
+//   edge length   before the fit, over all pairs (a, b) of the sample, in float64: rejected if |s_a - s_b| < t |r_a - r_b| or
+//                 |r_a - r_b| < t |s_a - s_b| (t = edge_length_similarity);
+//   distance      after the fit: rejected if a sampled correspondence has d^2 > threshold^2 in the scoring arithmetic of 4.
+// With both off the kernels are the instantiation without checker code: every output is bit-identical to the unchecked entry.
 //
 // Three launches, no host synchronisation:
 //   ransac_fit_kernel     one thread per (pair, hypothesis): sample, float64 Kabsch (csrc/kabsch.h), 3x4 float32 transform to the workspace
@@ -61,10 +67,13 @@ __device__ __forceinline__ bool beats(int ca, float ea, int ha, int cb, float eb
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
+// CHECK: the optional checkers (edge_t > 0: edge length similarity; check_thr2 > 0: distance) and the `passed` flags (may be null)
+template <bool CHECK>
 __global__ __launch_bounds__(kFitThreads) void ransac_fit_kernel(const float* __restrict__ src, const float* __restrict__ ref,
                                                                  const int64_t* __restrict__ offsets, int H, int rn, uint64_t key,
                                                                  const int32_t* __restrict__ explicit_idx, int valid,
-                                                                 float4* __restrict__ hyp) {
+                                                                 float4* __restrict__ hyp, double edge_t, float check_thr2,
+                                                                 uint8_t* __restrict__ passed) {
   const int p = blockIdx.y;
   const int h = blockIdx.x * kFitThreads + threadIdx.x;
   if (h >= H) return;
@@ -86,9 +95,21 @@ __global__ __launch_bounds__(kFitThreads) void ransac_fit_kernel(const float* __
     ok = finite3(s[0], s[1], s[2]) && finite3(r[0], r[1], r[2]);
     for (int d = 0; d < 3; d++) { sc[d] += s[d]; rc[d] += r[d]; }
   }
+  if (CHECK && ok && edge_t > 0.0) {
+    for (int a = 0; a < rn && ok; a++)
+      for (int b = a + 1; b < rn && ok; b++) {
+        const int64_t ia = index(a), ib = index(b);
+        const float *sa = src + 3 * (b0 + ia), *sb = src + 3 * (b0 + ib), *ra = ref + 3 * (b0 + ia), *rb = ref + 3 * (b0 + ib);
+        const double sx = (double)sa[0] - sb[0], sy = (double)sa[1] - sb[1], sz = (double)sa[2] - sb[2];
+        const double rx = (double)ra[0] - rb[0], ry = (double)ra[1] - rb[1], rz = (double)ra[2] - rb[2];
+        const double ds = sqrt((sx * sx + sy * sy) + sz * sz), dr = sqrt((rx * rx + ry * ry) + rz * rz);
+        ok = !(ds < edge_t * dr || dr < edge_t * ds);
+      }
+  }
   if (!ok) {
     const float nan = __int_as_float(0x7fc00000);
     for (int k = 0; k < 3; k++) out[k] = make_float4(nan, nan, nan, nan);
+    if (CHECK && passed) passed[(int64_t)p * H + h] = 0;
     return;
   }
   for (int d = 0; d < 3; d++) { sc[d] /= rn; rc[d] /= rn; }
@@ -103,6 +124,23 @@ __global__ __launch_bounds__(kFitThreads) void ransac_fit_kernel(const float* __
   }
   float T[16];
   kabsch(Hm, sc, rc, T);
+  if (CHECK && check_thr2 > 0.f) {
+    for (int j = 0; j < rn && ok; j++) {                      // d = R s + (t - r) and d^2 as ransac_score_kernel forms them
+      const int64_t i = index(j);
+      const float* s = src + 3 * (b0 + i);
+      const float* r = ref + 3 * (b0 + i);
+      float d[3];
+      for (int k = 0; k < 3; k++)
+        d[k] = __builtin_fmaf(T[4 * k], s[0], __builtin_fmaf(T[4 * k + 1], s[1], __builtin_fmaf(T[4 * k + 2], s[2], T[4 * k + 3] - r[k])));
+      const float d2 = __builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], d[0] * d[0]));
+      ok = !(d2 > check_thr2);
+    }
+    if (!ok) {
+      const float nan = __int_as_float(0x7fc00000);
+      for (int k = 0; k < 16; k++) T[k] = nan;
+    }
+  }
+  if (CHECK && passed) passed[(int64_t)p * H + h] = ok;
   for (int k = 0; k < 3; k++) out[k] = make_float4(T[4 * k], T[4 * k + 1], T[4 * k + 2], T[4 * k + 3]);
 }
 
@@ -190,11 +228,14 @@ __global__ __launch_bounds__(SE3_WAVE) void ransac_select_kernel(const int64_t* 
                                                                  const float4* __restrict__ hyp, const Candidate* __restrict__ cand,
                                                                  float* __restrict__ transforms, float* __restrict__ fitness,
                                                                  float* __restrict__ inlier_rmse, int32_t* __restrict__ best_hypothesis,
-                                                                 int32_t* __restrict__ counts, float* __restrict__ err_sums) {
+                                                                 int32_t* __restrict__ counts, float* __restrict__ err_sums,
+                                                                 uint8_t* __restrict__ passed) {
   const int p = blockIdx.x, lane = threadIdx.x;
   const int64_t n = offsets[p + 1] - offsets[p];
   if (num_blocks == 0 && counts)
     for (int64_t h = lane; h < H; h += SE3_WAVE) counts[(int64_t)p * H + h] = 0, err_sums[(int64_t)p * H + h] = 0.f;
+  if (num_blocks == 0 && passed)
+    for (int64_t h = lane; h < H; h += SE3_WAVE) passed[(int64_t)p * H + h] = 0;
   int bc = -1, bh = 0;
   float be = 0.f;
   for (int k = lane; k < num_blocks; k += SE3_WAVE) {
@@ -236,37 +277,67 @@ extern "C" size_t se3_ransac_correspondences_workspace_bytes(int num_pairs, int 
   return hyp_bytes(num_pairs, num_iterations) + (size_t)num_pairs * se3_cdiv(num_iterations, kTile) * sizeof(Candidate);
 }
 
-extern "C" int se3_ransac_correspondences_stack(const float* src_points, const float* ref_points, const int64_t* offsets, int num_pairs,
-                                                float distance_threshold, int ransac_n, int num_iterations, uint64_t seed,
-                                                const int32_t* hypothesis_indices, void* workspace, size_t workspace_bytes,
-                                                float* transforms, float* fitness, float* inlier_rmse, int32_t* best_hypothesis,
-                                                int32_t* counts, float* err_sums, void* stream) {
+namespace {
+int ransac_stack(const char* what, const float* src_points, const float* ref_points, const int64_t* offsets, int num_pairs,
+                 float distance_threshold, int ransac_n, int num_iterations, uint64_t seed, const int32_t* hypothesis_indices,
+                 bool checked, double edge_length_similarity, int check_distance, void* workspace, size_t workspace_bytes, float* transforms,
+                 float* fitness, float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts, float* err_sums, uint8_t* passed,
+                 void* stream) {
   SE3_REQUIRE(src_points && ref_points && offsets && transforms && fitness && inlier_rmse && best_hypothesis, SE3_ERR_INVALID_ARG,
-              "ransac_correspondences_stack: null pointer");
-  SE3_REQUIRE((counts == nullptr) == (err_sums == nullptr), SE3_ERR_INVALID_ARG,
-              "ransac_correspondences_stack: counts and err_sums go together");
-  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= 65535 && num_iterations >= 0, SE3_ERR_INVALID_ARG,
-              "ransac_correspondences_stack: %d pairs, %d iterations", num_pairs, num_iterations);
-  SE3_REQUIRE(ransac_n < 3 || ransac_n <= kMaxSample, SE3_ERR_UNSUPPORTED, "ransac_correspondences_stack: ransac_n = %d (3 .. %d)",
-              ransac_n, kMaxSample);
+              "%s: null pointer", what);
+  SE3_REQUIRE((counts == nullptr) == (err_sums == nullptr), SE3_ERR_INVALID_ARG, "%s: counts and err_sums go together", what);
+  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= 65535 && num_iterations >= 0, SE3_ERR_INVALID_ARG, "%s: %d pairs, %d iterations", what,
+              num_pairs, num_iterations);
+  SE3_REQUIRE(ransac_n < 3 || ransac_n <= kMaxSample, SE3_ERR_UNSUPPORTED, "%s: ransac_n = %d (3 .. %d)", what, ransac_n, kMaxSample);
+  SE3_REQUIRE(!checked || (edge_length_similarity >= 0.0 && edge_length_similarity <= 1.0), SE3_ERR_INVALID_ARG,
+              "%s: edge_length_similarity = %g (0: off, up to 1)", what, edge_length_similarity);
   if (num_pairs == 0) return SE3_OK;
   const size_t need = se3_ransac_correspondences_workspace_bytes(num_pairs, num_iterations);
-  SE3_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), SE3_ERR_INVALID_ARG,
-              "ransac_correspondences_stack: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  SE3_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), SE3_ERR_INVALID_ARG, "%s: workspace of %zu bytes, %zu needed", what,
+              workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const int H = num_iterations;
   const bool valid = ransac_n >= 3 && distance_threshold > 0.f && H > 0;   // (a NaN threshold is not > 0)
   float4* hyp = (float4*)workspace;
   Candidate* cand = valid ? (Candidate*)((char*)workspace + hyp_bytes(num_pairs, H)) : nullptr;
   const int blocks = valid ? (int)se3_cdiv(H, kTile) : 0;
+  const float thr2 = distance_threshold * distance_threshold;
   if (valid) {
-    ransac_fit_kernel<<<dim3((unsigned)se3_cdiv(H, kFitThreads), (unsigned)num_pairs), kFitThreads, 0, st>>>(
-        src_points, ref_points, offsets, H, ransac_n, splitmix64(seed), hypothesis_indices, 1, hyp);
-    ransac_score_kernel<<<dim3((unsigned)blocks, (unsigned)num_pairs), kScoreThreads, 0, st>>>(
-        src_points, ref_points, offsets, H, distance_threshold * distance_threshold, hyp, counts, err_sums, cand);
+    const dim3 fit_grid((unsigned)se3_cdiv(H, kFitThreads), (unsigned)num_pairs);
+    if (checked)
+      ransac_fit_kernel<true><<<fit_grid, kFitThreads, 0, st>>>(src_points, ref_points, offsets, H, ransac_n, splitmix64(seed),
+                                                                hypothesis_indices, 1, hyp, edge_length_similarity,
+                                                                check_distance ? thr2 : 0.f, passed);
+    else
+      ransac_fit_kernel<false><<<fit_grid, kFitThreads, 0, st>>>(src_points, ref_points, offsets, H, ransac_n, splitmix64(seed),
+                                                                 hypothesis_indices, 1, hyp, 0.0, 0.f, nullptr);
+    ransac_score_kernel<<<dim3((unsigned)blocks, (unsigned)num_pairs), kScoreThreads, 0, st>>>(src_points, ref_points, offsets, H, thr2, hyp,
+                                                                                              counts, err_sums, cand);
   }
   ransac_select_kernel<<<(unsigned)num_pairs, SE3_WAVE, 0, st>>>(offsets, H, blocks, hyp, cand, transforms, fitness, inlier_rmse,
-                                                               best_hypothesis, counts, err_sums);
-  SE3_CHECK_LAUNCH("ransac_correspondences_stack");
+                                                               best_hypothesis, counts, err_sums, passed);
+  SE3_CHECK_LAUNCH(what);
   return SE3_OK;
+}
+}  // namespace
+
+extern "C" int se3_ransac_correspondences_stack(const float* src_points, const float* ref_points, const int64_t* offsets, int num_pairs,
+                                                float distance_threshold, int ransac_n, int num_iterations, uint64_t seed,
+                                                const int32_t* hypothesis_indices, void* workspace, size_t workspace_bytes,
+                                                float* transforms, float* fitness, float* inlier_rmse, int32_t* best_hypothesis,
+                                                int32_t* counts, float* err_sums, void* stream) {
+  return ransac_stack("ransac_correspondences_stack", src_points, ref_points, offsets, num_pairs, distance_threshold, ransac_n,
+                      num_iterations, seed, hypothesis_indices, false, 0.0, 0, workspace, workspace_bytes, transforms, fitness, inlier_rmse,
+                      best_hypothesis, counts, err_sums, nullptr, stream);
+}
+
+extern "C" int se3_ransac_correspondences_checked_stack(const float* src_points, const float* ref_points, const int64_t* offsets,
+                                                        int num_pairs, float distance_threshold, int ransac_n, int num_iterations,
+                                                        uint64_t seed, const int32_t* hypothesis_indices, double edge_length_similarity,
+                                                        int check_distance, void* workspace, size_t workspace_bytes, float* transforms,
+                                                        float* fitness, float* inlier_rmse, int32_t* best_hypothesis, int32_t* counts,
+                                                        float* err_sums, uint8_t* passed, void* stream) {
+  return ransac_stack("ransac_correspondences_checked_stack", src_points, ref_points, offsets, num_pairs, distance_threshold, ransac_n,
+                      num_iterations, seed, hypothesis_indices, true, edge_length_similarity, check_distance, workspace, workspace_bytes,
+                      transforms, fitness, inlier_rmse, best_hypothesis, counts, err_sums, passed, stream);
 }

@@ -1965,12 +1965,15 @@ def count_inliers(src, ref, transforms, radius, range_begin=None, range_end=None
     return votes
 
 
-def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed=0, hypothesis_indices=None, per_hypothesis=False):
+def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed=0, hypothesis_indices=None, per_hypothesis=False,
+                 edge_length_similarity=None, check_distance=False):
     """HIP (csrc/ransac.hip): RANSAC from correspondences for the P = len(offsets) - 1 pairs of stacked src / ref (total, 3), pair p on
     rows [offsets[p], offsets[p+1]) (offsets int64 on the device), three launches and no host synchronisation.  hypothesis_indices:
     (P, num_iterations, ransac_n) int32 pair-local samples instead of the seeded sampler.  Returns a dict of device tensors: transforms
     (P, 4, 4), fitness (P,), inlier_rmse (P,), best_hypothesis (P,) int32 (-1: identity); with per_hypothesis also counts (P, H) int32
-    and err_sums (P, H) float32."""
+    and err_sums (P, H) float32.  edge_length_similarity (a float in (0, 1]) and check_distance switch on Open3D's correspondence checkers
+    (se3_ransac_correspondences_checked_stack; a rejected hypothesis scores 0 inliers); per_hypothesis then also returns passed (P, H)
+    bool.  Without them the call and its outputs are the unchecked entry's."""
     src = _req(src.contiguous(), torch.float32, 'src', 2)
     ref = _req(ref.contiguous(), torch.float32, 'ref', 2)
     offsets = _req(offsets.contiguous(), torch.int64, 'offsets', 1)
@@ -1993,15 +1996,88 @@ def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations
         out['err_sums'] = torch.empty((P, H), dtype=torch.float32, device=dev)
     nbytes = lib().se3_ransac_correspondences_workspace_bytes(P, H)
     ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
-    check(lib().se3_ransac_correspondences_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn, H,
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                 hypothesis_indices.data_ptr() if hypothesis_indices is not None else None,
-                                                 ws.data_ptr(), nbytes, out['transforms'].data_ptr(), out['fitness'].data_ptr(),
-                                                 out['inlier_rmse'].data_ptr(), out['best_hypothesis'].data_ptr(),
-                                                 out['counts'].data_ptr() if per_hypothesis else None,
-                                                 out['err_sums'].data_ptr() if per_hypothesis else None, _stream()),
-          'se3_ransac_correspondences_stack')
+    hyp = hypothesis_indices.data_ptr() if hypothesis_indices is not None else None
+    results = (out['transforms'].data_ptr(), out['fitness'].data_ptr(), out['inlier_rmse'].data_ptr(), out['best_hypothesis'].data_ptr(),
+               out['counts'].data_ptr() if per_hypothesis else None, out['err_sums'].data_ptr() if per_hypothesis else None)
+    if edge_length_similarity is None and not check_distance:
+        check(lib().se3_ransac_correspondences_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn, H,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, hyp, ws.data_ptr(), nbytes, *results, _stream()),
+              'se3_ransac_correspondences_stack')
+        return out
+    edge = 0.0 if edge_length_similarity is None else float(edge_length_similarity)
+    if edge_length_similarity is not None and not 0.0 < edge <= 1.0:
+        raise RuntimeError('ransac_stack: edge_length_similarity = %r outside (0, 1]' % (edge_length_similarity,))
+    passed = torch.empty((P, H), dtype=torch.uint8, device=dev) if per_hypothesis else None
+    check(lib().se3_ransac_correspondences_checked_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn,
+                                                         H, int(seed) & 0xFFFFFFFFFFFFFFFF, hyp, edge, 1 if check_distance else 0,
+                                                         ws.data_ptr(), nbytes, *results,
+                                                         passed.data_ptr() if passed is not None else None, _stream()),
+          'se3_ransac_correspondences_checked_stack')
+    if passed is not None:
+        out['passed'] = passed.bool()
     return out
+
+
+# ---- feature-space matching (csrc/feature_nn.hip) -----------------------------------------------------------------------------------------
+CORR_MODES = {'one_way': 0, 'mutual': 1, 'bilateral_mask': 2, 'bilateral_concat': 3}
+
+
+def _feature_offsets(ref_offsets, src_offsets, nref, nsrc, what):
+    ref_offsets = _req(ref_offsets.contiguous(), torch.int64, 'ref_offsets', 1)
+    src_offsets = _req(src_offsets.contiguous(), torch.int64, 'src_offsets', 1)
+    P = ref_offsets.shape[0] - 1
+    if P < 0 or src_offsets.shape[0] != P + 1 or (P == 0 and nref + nsrc > 0):
+        raise RuntimeError('%s: ref_offsets and src_offsets must both hold one entry per pair and the end' % what)
+    return ref_offsets, src_offsets, P
+
+
+def feature_nn_stack(ref_feats, src_feats, ref_offsets, src_offsets):
+    """HIP (csrc/feature_nn.hip): the nearest neighbour in feature space of every row in the other cloud of its pair, both directions, with
+    O(rows) memory.  ref_feats (sum N_p, C) / src_feats (sum M_p, C) float32, pair p on rows [ref_offsets[p], ref_offsets[p+1]) and
+    [src_offsets[p], src_offsets[p+1]) (int64 on the device, from 0 to the row count).  Returns (nn_src_indices (sum N_p,) int64 pair-local,
+    -1 without a finite candidate; nn_src_sq_distances float32, recomputed as sum (x - y)^2, +inf for -1; nn_ref_indices (sum M_p,);
+    nn_ref_sq_distances).  Three launches, no host synchronisation; deterministic."""
+    ref_feats = _req(ref_feats.contiguous(), torch.float32, 'ref_feats', 2)
+    src_feats = _req(src_feats.contiguous(), torch.float32, 'src_feats', 2)
+    nref, nsrc, C = ref_feats.shape[0], src_feats.shape[0], ref_feats.shape[1]
+    if src_feats.shape[1] != C or C < 1:
+        raise RuntimeError('feature_nn_stack: features of %d and %d channels' % (C, src_feats.shape[1]))
+    ref_offsets, src_offsets, P = _feature_offsets(ref_offsets, src_offsets, nref, nsrc, 'feature_nn_stack')
+    dev = ref_feats.device
+    _same_device(dev, (src_feats, ref_offsets, src_offsets), 'feature_nn_stack')
+    nn_src = torch.empty((nref,), dtype=torch.int64, device=dev)
+    d_src = torch.empty((nref,), dtype=torch.float32, device=dev)
+    nn_ref = torch.empty((nsrc,), dtype=torch.int64, device=dev)
+    d_ref = torch.empty((nsrc,), dtype=torch.float32, device=dev)
+    nbytes = lib().se3_feature_nn_workspace_bytes(nref, nsrc)
+    ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
+    check(lib().se3_feature_nn_stack(ref_feats.data_ptr(), src_feats.data_ptr(), ref_offsets.data_ptr(), src_offsets.data_ptr(), P, nref, nsrc,
+                                     C, ws.data_ptr(), nbytes, nn_src.data_ptr(), d_src.data_ptr(), nn_ref.data_ptr(), d_ref.data_ptr(),
+                                     _stream()), 'se3_feature_nn_stack')
+    return nn_src, d_src, nn_ref, d_ref
+
+
+def feature_corr_stack(nn_src, nn_ref, ref_offsets, src_offsets, mode):
+    """HIP (csrc/feature_nn.hip): the correspondence lists of feature_nn_stack's index arrays for all pairs: count, exclusive scan, fill, and
+    ONE host synchronisation (the pair boundaries of the list).  mode: a key of CORR_MODES.  Returns (ref_corr_indices, src_corr_indices)
+    int64 pair-local on the device, and the host list of P + 1 boundaries: pair p's entries are [bounds[p], bounds[p+1])."""
+    nn_src = _req(nn_src.contiguous(), torch.int64, 'nn_src', 1)
+    nn_ref = _req(nn_ref.contiguous(), torch.int64, 'nn_ref', 1)
+    nref, nsrc = nn_src.shape[0], nn_ref.shape[0]
+    ref_offsets, src_offsets, P = _feature_offsets(ref_offsets, src_offsets, nref, nsrc, 'feature_corr_stack')
+    dev = nn_src.device
+    _same_device(dev, (nn_ref, ref_offsets, src_offsets), 'feature_corr_stack')
+    m = CORR_MODES[mode]
+    entry_offsets = torch.empty((nref + nsrc + 1,), dtype=torch.int64, device=dev)
+    args = (nn_src.data_ptr(), nn_ref.data_ptr(), ref_offsets.data_ptr(), src_offsets.data_ptr(), P, nref, nsrc, m)
+    check(lib().se3_feature_corr_count_stack(*args, entry_offsets.data_ptr(), _stream()), 'se3_feature_corr_count_stack')
+    bounds = entry_offsets[ref_offsets + src_offsets].cpu().tolist()      # the one read-back
+    total = bounds[-1] if bounds else 0
+    ref_idx = torch.empty((total,), dtype=torch.int64, device=dev)
+    src_idx = torch.empty((total,), dtype=torch.int64, device=dev)
+    check(lib().se3_feature_corr_fill_stack(*args, entry_offsets.data_ptr(), total, ref_idx.data_ptr(), src_idx.data_ptr(), _stream()),
+          'se3_feature_corr_fill_stack')
+    return ref_idx, src_idx, bounds
 
 
 # ---- evaluation (csrc/evaluation.hip) ---------------------------------------------------------------------------------------------------

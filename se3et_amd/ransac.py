@@ -4,6 +4,9 @@
 
   ransac_pairs(src_list, ref_list, threshold, ransac_n, iterations)    (P, ...) device tensors for P pairs, three launches
   registration_with_ransac_from_correspondences(src, ref, ...)         drop-in: float64 numpy (4, 4) like result.transformation
+  ransac_from_feats_pairs(src_points, ref_points, src_feats, ref_feats, ...)   descriptor matching (se3et_amd/feature_matching.py), then
+                                                                       RANSAC with Open3D's edge-length and distance checkers
+  registration_with_ransac_from_feats(src, ref, src_feats, ref_feats, ...)     drop-in (geotransformer/utils/open3d.py:133-166)
   select_correspondences(out, num_corr)                                eval.py's --num_corr cut (top scores, stable order)
   register_pairs(cfg, outs, method, num_corr)                          (B, 4, 4) estimated transforms of B forward_pairs dicts
   sample_indices(seed, n, num_iterations, ransac_n)                    the device sampler's indices, in numpy
@@ -31,7 +34,13 @@ Where this differs from Open3D:
   - Arithmetic: the fit is float64, rounded to float32; the test is d^2 < threshold^2 in float32 with d = R s + (t - r), and each
     hypothesis sums its inlier d^2 in float32, serially in correspondence order.  Counts are integers.  A pair's result is therefore
     bit-identical alone or in any batch, and from run to run.
-  - Non-finite correspondences are never inliers; a hypothesis whose sample is non-finite has 0 inliers."""
+  - Non-finite correspondences are never inliers; a hypothesis whose sample is non-finite has 0 inliers.
+
+Optional checkers (Open3D's CorrespondenceCheckerBasedOnEdgeLength and ...BasedOnDistance; off by default, and then every output is
+bit-identical to a call without them).  A rejected hypothesis scores 0 inliers:
+  - edge_length_similarity = t: before the fit, over all pairs (a, b) of the sampled correspondences, the hypothesis is rejected if
+    |s_a - s_b| < t |r_a - r_b| or |r_a - r_b| < t |s_a - s_b|, in float64;
+  - check_distance: after the fit, it is rejected if a sampled correspondence has d^2 > distance_threshold^2 in the scoring arithmetic."""
 import numpy as np
 import torch
 
@@ -69,11 +78,12 @@ def _device_points(x, device):
 
 @torch.no_grad()
 def ransac_pairs(src_list, ref_list, distance_threshold, ransac_n, num_iterations, seed=0, correspondences=None, hypothesis_indices=None,
-                 per_hypothesis=False, device='cuda'):
+                 per_hypothesis=False, device='cuda', edge_length_similarity=None, check_distance=False):
     """RANSAC for P pairs in one batched call: src_list[p] / ref_list[p] (n_p, 3) numpy arrays or tensors, corresponding row by row, or
     -- with correspondences[p], a (K_p, 2) table of (src index, ref index) as Open3D takes it -- the pair's point clouds.  Returns
     {transforms (P, 4, 4), fitness (P,), inlier_rmse (P,), best_hypothesis (P,) int32 (-1: identity)} as device tensors (and counts /
-    err_sums (P, H) with per_hypothesis).  hypothesis_indices: (P, H, ransac_n) int32 samples instead of the seeded sampler."""
+    err_sums (P, H) with per_hypothesis).  hypothesis_indices: (P, H, ransac_n) int32 samples instead of the seeded sampler.
+    edge_length_similarity / check_distance: the optional checkers of the module docstring (with per_hypothesis also passed (P, H) bool)."""
     if len(src_list) != len(ref_list) or (correspondences is not None and len(correspondences) != len(src_list)):
         raise ValueError('ransac_pairs: one src, ref (and correspondence table) per pair')
     if len(src_list) and torch.is_tensor(src_list[0]) and src_list[0].is_cuda:
@@ -98,7 +108,10 @@ def ransac_pairs(src_list, ref_list, distance_threshold, ransac_n, num_iteration
         hypothesis_indices = torch.as_tensor(np.asarray(hypothesis_indices, dtype=np.int32))
     if hypothesis_indices is not None:
         hypothesis_indices = hypothesis_indices.to(device=device, dtype=torch.int32)
-    return _ops.ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed, hypothesis_indices, per_hypothesis)
+    if edge_length_similarity is None and not check_distance:
+        return _ops.ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed, hypothesis_indices, per_hypothesis)
+    return _ops.ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations, seed, hypothesis_indices, per_hypothesis,
+                             edge_length_similarity, check_distance)
 
 
 def registration_with_ransac_from_correspondences(src_points, ref_points, correspondences=None, distance_threshold=0.05, ransac_n=3,
@@ -107,6 +120,64 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
     sampler's seed): the (4, 4) float64 numpy transform src -> ref."""
     out = ransac_pairs([src_points], [ref_points], distance_threshold, ransac_n, num_iterations, seed,
                        None if correspondences is None else [correspondences])
+    return out['transforms'][0].cpu().numpy().astype(np.float64)
+
+
+@torch.no_grad()
+def ransac_from_feats_pairs(src_points_list, ref_points_list, src_feats_list, ref_feats_list, distance_threshold=0.05, ransac_n=3,
+                            num_iterations=50000, mutual_filter=False, seed=0, edge_length_similarity=0.9, check_distance=True,
+                            per_hypothesis=False):
+    """Registration from descriptors for P pairs (Open3D's registration_ransac_based_on_feature_matching as
+    registration_with_ransac_from_feats calls it): each SRC point is matched to its feature-nearest REF point
+    (feature_matching.nearest_feature_pairs: no (N, M) matrix), then ransac_pairs runs on those correspondences with the edge-length (0.9)
+    and distance checkers.  mutual_filter keeps only the correspondences whose ref point's nearest src point is the src point itself; a
+    pair left with fewer than ransac_n of them falls back to all of its correspondences, as Open3D does.  The host synchronises a fixed
+    number of times per call (the mutual counts, the compaction and its pair boundaries), not once per pair.  Points and features are (n, 3) /
+    (n, C) float32 GPU tensors.  Returns the dict of ransac_pairs plus correspondences: per pair an (K_p, 2) int64 (src, ref) table."""
+    from . import feature_matching as _fm
+    P = len(src_points_list)
+    if not (len(ref_points_list) == len(src_feats_list) == len(ref_feats_list) == P):
+        raise ValueError('ransac_from_feats_pairs: one src / ref point and feature array per pair')
+    for p in range(P):
+        if src_points_list[p].shape[0] != src_feats_list[p].shape[0] or ref_points_list[p].shape[0] != ref_feats_list[p].shape[0]:
+            raise ValueError('ransac_from_feats_pairs: pair %d has a different number of points and features' % p)
+    nn_src, _ds, nn_ref, _dr = _fm.nearest_feature_pairs(ref_feats_list, src_feats_list)
+    keep = [i >= 0 for i in nn_ref]                          # per src row: it has a ref row at all
+    sizes = [int(i.shape[0]) for i in nn_ref]
+    if mutual_filter and P:
+        mutual = []
+        for p in range(P):                                   # (an empty ref cloud has nothing to gather from: no mutual correspondence)
+            j = torch.arange(sizes[p], dtype=torch.int64, device=nn_ref[p].device)
+            mutual.append(keep[p] & (nn_src[p][nn_ref[p].clamp(min=0)] == j) if nn_src[p].shape[0] else torch.zeros_like(keep[p]))
+        enough = torch.stack([m.sum() for m in mutual]).cpu().tolist()          # one read-back for all pairs
+        keep = [m if c >= ransac_n else k for m, k, c in zip(mutual, keep, enough)]
+    tables = []
+    if P:
+        rows = torch.nonzero(torch.cat(keep)).reshape(-1)    # one compaction for all pairs; rows ascend, so pairs stay contiguous
+        starts = np.concatenate([[0], np.cumsum(sizes)])
+        cuts = torch.searchsorted(rows, torch.as_tensor(starts, dtype=torch.int64, device=rows.device)).cpu().tolist()
+        all_ref = torch.cat(nn_ref)
+        for p in range(P):
+            j = rows[cuts[p]:cuts[p + 1]]
+            tables.append(torch.stack([j - int(starts[p]), all_ref[j]], 1))
+    out = ransac_pairs(src_points_list, ref_points_list, distance_threshold, ransac_n, num_iterations, seed, correspondences=tables,
+                       per_hypothesis=per_hypothesis, edge_length_similarity=edge_length_similarity, check_distance=check_distance)
+    out['correspondences'] = tables
+    return out
+
+
+def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_feats, distance_threshold=0.05, ransac_n=3,
+                                        num_iterations=50000, val_iterations=1000, mutual_filter=False, seed=0):
+    """Drop-in for geotransformer.utils.open3d.registration_with_ransac_from_feats (same signature and defaults, plus mutual_filter and the
+    sampler's seed): the (4, 4) float64 numpy transform src -> ref.  Arrays are uploaded inside the call.
+    val_iterations is accepted and has NO effect: in Open3D >= 0.13 that slot of RANSACConvergenceCriteria is a confidence, clamped to 1,
+    so all num_iterations hypotheses are evaluated (item 6 of the contract).  The early stop of older Open3D versions after
+    val_iterations validated hypotheses is not reproduced."""
+    dev = 'cuda'
+    up = lambda a, w: torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.float32).reshape(-1, w)).to(dev)
+    src_feats, ref_feats = np.asarray(src_feats), np.asarray(ref_feats)
+    out = ransac_from_feats_pairs([up(src_points, 3)], [up(ref_points, 3)], [up(src_feats, src_feats.shape[-1])],
+                                  [up(ref_feats, ref_feats.shape[-1])], distance_threshold, ransac_n, num_iterations, mutual_filter, seed)
     return out['transforms'][0].cpu().numpy().astype(np.float64)
 
 
