@@ -965,6 +965,37 @@ int se3_debug_pair_nearest_neighbor_host(const void* q_points, int64_t nq, const
 int se3_debug_pair_ball_host(const void* q_points, int64_t nq, const void* s_points, int64_t ns, int elem, const double* transform,
                              double radius, int64_t* counts, int64_t* out, int64_t capacity, int64_t* total);
 
+/* ---- scan preparation: voxel downsampling, k nearest neighbours, k-NN normals (csrc/voxel_downsample.hip, csrc/knn_normals.hip) ---------------
+ * Open3D's voxel_down_sample and estimate_normals (utils/open3d.py:49-65) for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, all float64;
+ * the contract is the header comment of the two kernel files.  Points (and normals) are (rows, 3) on the device, float32 (elem 0) or float64
+ * (elem 1), promoted on load; cloud c owns rows [offsets_host[c], offsets_host[c + 1]) (HOST int64, num_clouds + 1 entries from 0).
+ *   se3_voxel_downsample_stack   out_points (and out_normals when normals is given) sized by the input row count, float64: the clouds'
+ *                           voxel means back to back, cloud c's out_counts[c] rows (DEVICE int) in the order of each voxel's first member.
+ *                           status (DEVICE int): 0, or bit 1 = a non-finite point or normal, bit 2 = an axis needs 2^21 voxels or more (the
+ *                           clouds concerned give no rows, and out_counts[c] holds MINUS their bits); read it with the counts.
+ *                           voxel_size must be positive and finite; at most 2^30 - 64 points per call.  A voxel above 64 members is
+ *                           ordered by one workgroup (quadratic in its members) and summed by one thread: correct, slow.
+ *   se3_knn_stack           on a grid built by se3_pair_grid_build over the support clouds (identity transforms, cell_hint 0): out_idx
+ *                           (nq, k) int64 cloud-local and out_d2 (nq, k) float64 squared distances, rows ascending by (d^2, index); -1 and
+ *                           +inf in the columns a smaller cloud leaves.  k in [1, 64].
+ *   se3_knn_normals_stack   the fused form: out_normals (nq, 3) float64 from each row's k neighbours, the tables never leave the registers.
+ *                           viewpoints_host: NULL, or (num_clouds, 3) float64 on the HOST (checked finite): n . (viewpoint - p) >= 0.
+ *   se3_debug_*_host        the same text on HOST memory for one cloud, no GPU: every pointer a host pointer.  voxel: *status as above;
+ *                           normals: the cloud searched in itself, out_covariances (n, 6: xx xy xz yy yz zz) may be NULL. */
+size_t se3_voxel_downsample_workspace_bytes(int64_t n_total, int num_clouds);
+int se3_voxel_downsample_stack(const void* points, int elem, const void* normals, const int64_t* offsets_host, int num_clouds, double voxel_size,
+                               double* out_points, double* out_normals, int* out_counts, int* status, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int se3_knn_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                  const int64_t* q_offsets_host, int num_clouds, int k, int64_t* out_idx, double* out_d2, void* stream);
+int se3_knn_normals_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                          const int64_t* q_offsets_host, int num_clouds, int k, const double* viewpoints_host, double* out_normals, void* stream);
+int se3_debug_voxel_downsample_host(const void* points, int64_t n, int elem, const void* normals, double voxel_size, double* out_points,
+                                    double* out_normals, int64_t* out_count, int* status);
+int se3_debug_knn_host(const void* q_points, int64_t nq, const void* s_points, int64_t ns, int elem, int k, int64_t* out_idx, double* out_d2);
+int se3_debug_knn_normals_host(const void* points, int64_t n, int elem, int k, const double* viewpoint, double* out_normals,
+                               double* out_covariances);
+
 #ifdef __cplusplus
 }
 #endif

@@ -389,3 +389,78 @@ __global__ __launch_bounds__(256) void pair_grid_scatter_kernel(PairRows rows, i
   G.sorted_idx[s0 + pos] = (int)(i - s0);
 }
 #endif  // __HIPCC__
+
+// ---- k nearest neighbours (csrc/knn_normals.hip) ---------------------------------------------------------------------------------------------
+// The k support points of pair `m` with the smallest d^2 = pg_dist2, ascending by (d^2, index): among equal distances the lower index comes
+// first and wins the last slot.  The caller's `list` holds the best k found so far, sorted; it offers every point of a ring's cells and the
+// rings widen until the k-th best d^2 is no larger than pg_shell_bound2 of everything outside them (a list that is not full holds +inf
+// there, so the walk goes on until the rings cover the grid).  The result is a sorted SET: it does not depend on the order of the points
+// inside a cell, nor on which lane met which point.
+//   list.offer(valid, d2, j)   every lane of the row calls it together (the kernel inserts across lanes); valid = this lane holds a point
+//   list.kth_d2()              the k-th best d^2 so far, the same on every lane
+constexpr int kPairKnnMax = 64;               // one list entry per lane of a wave
+constexpr int kPairKnnEmpty = 0x7fffffff;     // index of an empty list entry: sorts behind every point at d^2 = +inf
+
+// (d2, j) comes before (e2, ej) in a row
+PG_HD bool pg_knn_before(double d2, int j, double e2, int ej) { return d2 < e2 || (d2 == e2 && j < ej); }
+
+template <class List>
+PG_HD void pg_knn(const PairGridView& g, int p, const double* q, int lane, int nlanes, List& list) {
+  const PairGridMeta& m = g.meta[p];
+  const int* cells = g.cells + (size_t)p * (kPairCellCap + 1);
+  const double* pts = g.sorted + 3 * m.s_start;
+  const int* idx = g.sorted_idx + m.s_start;
+  int c[3];
+  for (int d = 0; d < 3; d++) c[d] = pg_cell_coord(q[d], m.org[d], m.inv_cell, m.dim[d]);
+  for (int k = 0; k < kPairGridCap; k++) {
+    pg_ring_runs(m, c, k, [&](int a, int b) {
+      const int end = cells[b + 1];
+      for (int t0 = cells[a]; t0 < end; t0 += nlanes) {                // (uniform over the lanes: offer is a collective)
+        const int t = t0 + lane;
+        const bool valid = t < end;
+        double d2 = INFINITY;
+        int j = kPairKnnEmpty;
+        if (valid) d2 = pg_dist2(q, pts + 3 * (size_t)t), j = idx[t];
+        list.offer(valid, d2, j);
+      }
+    });
+    if (list.kth_d2() <= pg_shell_bound2(m, q, c, k)) break;
+  }
+}
+
+// the list of a serial caller (the debug entries): insertion into a sorted array
+struct PairKnnSerialList {
+  double d2[kPairKnnMax];
+  int j[kPairKnnMax];
+  int k;
+  PG_HD void init(int k_) {
+    k = k_;
+    for (int t = 0; t < kPairKnnMax; t++) d2[t] = INFINITY, j[t] = kPairKnnEmpty;
+  }
+  PG_HD double kth_d2() const { return d2[k - 1]; }
+  PG_HD void offer(bool valid, double cd, int cj) {
+    if (!valid || !pg_knn_before(cd, cj, d2[k - 1], j[k - 1])) return;
+    int t = k - 1;
+    for (; t > 0 && pg_knn_before(cd, cj, d2[t - 1], j[t - 1]); t--) d2[t] = d2[t - 1], j[t] = j[t - 1];
+    d2[t] = cd, j[t] = cj;
+  }
+};
+
+// the pair (or cloud) that owns row i of a stacked array
+PG_HD int pg_pair_of_row(const PairRows& rows, int64_t i) {
+  int p = 0;
+  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  return p;
+}
+
+// host-side offsets -> PairRows; false unless 0 = offsets[0] <= offsets[1] <= ...
+inline bool pg_fill_rows(PairRows* rows, const int64_t* offsets, int num_pairs) {
+  rows->n = num_pairs;
+  if (offsets[0] != 0) return false;
+  for (int p = 0; p <= num_pairs; p++) {
+    rows->start[p] = offsets[p];
+    if (p > 0 && offsets[p] < offsets[p - 1]) return false;
+  }
+  for (int p = num_pairs + 1; p <= kPairMaxPairs; p++) rows->start[p] = offsets[num_pairs];
+  return true;
+}

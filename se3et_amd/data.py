@@ -31,40 +31,56 @@ def cap_coarsest(points, lengths, cap=2000):
     return torch.cat(keep, 0), torch.clamp(lengths, max=cap)
 
 
-def stage_clouds(points, lengths, num_stages, voxel_size):
+def stage_clouds(points, lengths, num_stages, voxel_size, normals=None):
     """The point pyramid of the reference's precompute_data_stack_mode: stage 0 the clouds as given, stage i > 0 the grid subsampling of
     stage i - 1 at voxel_size * 2^i, the coarsest stage capped at 2000 points per cloud.  points (N, 3) float32 on the GPU, lengths host
-    int64.  -> (points_list, lengths_list of host int64 tensors)"""
-    points_list, lengths_list = [], []
+    int64.  -> (points_list, lengths_list of host int64 tensors); with normals (N, 3) float32 (carried through every subsampling stage and
+    capped with the points, as the reference carries them) also the normals_list."""
+    points_list, lengths_list, normals_list = [], [], []
     # the S-1 subsampling stages back to back: every stage takes the per-cloud counts of the one before from DEVICE memory (outputs sized
     # by the stage-0 row count, an upper bound), and ONE synchronisation fetches the counts of all stages
-    sub_pts, sub_len, cur_pts, cur_len, v = [], [], points, lengths, voxel_size
+    sub_pts, sub_nrm, sub_len, cur_pts, cur_nrm, cur_len, v = [], [], [], points, normals, lengths, voxel_size
     for i in range(1, num_stages):
         v *= 2
-        cur_pts, _, cur_len = _ops.grid_subsample(cur_pts, cur_len, None, v)
+        cur_pts, cur_nrm, cur_len = _ops.grid_subsample(cur_pts, cur_len, cur_nrm, v)
         sub_pts.append(cur_pts)
+        sub_nrm.append(cur_nrm)
         sub_len.append(cur_len)
     sub_len = torch.stack(sub_len).cpu() if sub_len else None
     for i in range(num_stages):
         if i > 0:
             lengths = sub_len[i - 1].clone()
             points = sub_pts[i - 1][:int(lengths.sum())]
+            if normals is not None:
+                normals = sub_nrm[i - 1][:int(lengths.sum())]
         if i == num_stages - 1:
+            if normals is not None:
+                normals = cap_coarsest(normals, lengths)[0]
             points, lengths = cap_coarsest(points, lengths)
         points_list.append(points.contiguous())
         lengths_list.append(lengths)
-    return points_list, lengths_list
+        if normals is not None:
+            normals_list.append(normals.contiguous())
+    return (points_list, lengths_list) if normals is None else (points_list, lengths_list, normals_list)
 
 
-def precompute_data_stack_mode(points, lengths, num_stages, voxel_size, radius, neighbor_limits):
+def precompute_data_stack_mode(points, lengths, num_stages, voxel_size, radius, neighbor_limits, normals=False):
     """points (N, 3) float32 GPU tensor (ref rows then src rows; several pairs may be stacked: ref0, src0, ref1, src1, ...),
     lengths (2 B,) int64 (host).  Returns the dict of lists
-    {'points', 'lengths', 'neighbors', 'subsampling', 'upsampling'}; `lengths` entries are host int64 tensors."""
+    {'points', 'lengths', 'neighbors', 'subsampling', 'upsampling'}; `lengths` entries are host int64 tensors.  normals=True adds the
+    reference's 'normals' list of (N_i, 3) float32 (utils/data.py:23-28): stage 0 estimated per cloud on the device (se3et_amd.scan_prep:
+    k-NN 33, canonical sign, cast to float32), later stages carried by the grid subsampling, the coarsest capped with its points."""
     assert num_stages == len(neighbor_limits)
     if not points.is_cuda:
         raise RuntimeError('precompute_data_stack_mode: points must be on the GPU')
     lengths = torch.as_tensor(lengths, dtype=torch.int64).cpu()
-    points_list, lengths_list = stage_clouds(points, lengths, num_stages, voxel_size)
+    normals_list = None
+    if normals:
+        from .scan_prep import estimate_normals_clouds
+        normals0 = torch.cat(estimate_normals_clouds(list(torch.split(points, lengths.tolist()))), 0).float()
+        points_list, lengths_list, normals_list = stage_clouds(points, lengths, num_stages, voxel_size, normals0)
+    else:
+        points_list, lengths_list = stage_clouds(points, lengths, num_stages, voxel_size)
 
     # a spatial order of every stage's points for the union-staged KPConv (tile membership only; csrc/kpconv_union.hip)
     # (the default policy runs that kernel on the layers whose queries are stage 0 / 1 points: ops._kpconv_union_pays)
@@ -136,6 +152,8 @@ def precompute_data_stack_mode(points, lengths, num_stages, voxel_size, radius, 
     num_pairs = counts.shape[1] // 2
     pair_counts = counts.view(counts.shape[0], num_pairs, 2).amax(2).tolist() if counts.shape[1] % 2 == 0 else None
     out = {'points': points_list, 'lengths': lengths_list, 'neighbors': [], 'subsampling': [], 'upsampling': []}
+    if normals_list is not None:
+        out['normals'] = normals_list
     stage_of = {'neighbors': lambda k: k, 'subsampling': lambda k: k + 1, 'upsampling': lambda k: k}
     for j, (kind, (full, _)) in enumerate(jobs):
         width = min(full.shape[1], int(counts[j].max()))
@@ -165,8 +183,9 @@ def precompute_data_stack_mode(points, lengths, num_stages, voxel_size, radius, 
 
 
 def registration_collate_fn_stack_mode(data_dicts, num_stages, voxel_size, search_radius, neighbor_limits,
-                                       precompute_data=True, device='cuda'):
-    """One-pair version of the reference collate: uploads the pair and builds the pyramid on the device."""
+                                       precompute_data=True, device='cuda', normals=False):
+    """One-pair version of the reference collate: uploads the pair and builds the pyramid on the device (normals: the 'normals' list of
+    precompute_data_stack_mode)."""
     if len(data_dicts) != 1:
         raise NotImplementedError('one registration pair per call (as the reference, batch_size = 1)')
     d = data_dicts[0]
@@ -177,7 +196,7 @@ def registration_collate_fn_stack_mode(data_dicts, num_stages, voxel_size, searc
     points = torch.cat((ref, src), 0).to(device)
     lengths = torch.tensor([ref.shape[0], src.shape[0]], dtype=torch.int64)
     if precompute_data:
-        out.update(precompute_data_stack_mode(points, lengths, num_stages, voxel_size, search_radius, neighbor_limits))
+        out.update(precompute_data_stack_mode(points, lengths, num_stages, voxel_size, search_radius, neighbor_limits, normals=normals))
     else:
         out['points'], out['lengths'] = points, lengths
     out['batch_size'] = 1

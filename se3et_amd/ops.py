@@ -2424,3 +2424,71 @@ def pair_info_covariance_stack(src_points, s_lengths, transforms, selected, sele
     check(lib().se3_pair_info_covariance_stack(_dp(s), elem, s_off, T.data_ptr(), _dp(sel), k_off, P, _dp(out), _stream()),
           'se3_pair_info_covariance_stack')
     return out
+
+
+# ---- scan preparation: voxel downsampling, k nearest neighbours, k-NN normals (csrc/voxel_downsample.hip, csrc/knn_normals.hip) ---------------
+KNN_MAX = 64                 # one list entry per lane of a wave
+_ws_voxel = Workspace(1 << 22)
+
+
+def voxel_downsample_stack(points, lengths, voxel_size, normals=None):
+    """HIP: Open3D's voxel_down_sample of stacked clouds.  points (total, 3) float32 / float64 on the device, cloud c on the next lengths[c]
+    rows (host ints); normals: None or the same shape and type.  Returns (out_points (total, 3) float64, out_normals or None, words): the
+    clouds' voxel means back to back in out_points[:sum(counts)]; words (len(lengths) + 1,) int32 on the DEVICE holds the counts and, last,
+    the status word (0; bit 1: a non-finite value, bit 2: an axis needs 2^21 voxels or more; the count of a refused cloud is minus its bits)
+    -- one copy fetches both."""
+    p, elem = _pair_points(points, 'points')
+    nr = None
+    if normals is not None:
+        nr, nelem = _pair_points(normals, 'normals')
+        if nr.shape != p.shape or nelem != elem or nr.device != p.device:
+            raise RuntimeError('voxel_downsample_stack: normals must have the shape, type and device of the points')
+    C = len(lengths)
+    offsets = _pair_offsets(lengths, p.shape[0], 'voxel_downsample_stack')
+    out = torch.empty((p.shape[0], 3), dtype=torch.float64, device=p.device)
+    out_n = torch.empty_like(out) if nr is not None else None
+    words = torch.empty((C + 1,), dtype=torch.int32, device=p.device)
+    nbytes = lib().se3_voxel_downsample_workspace_bytes(p.shape[0], C)
+    stream = _stream()
+    ws = _ws_voxel.get(p.device, stream.value, nbytes)
+    check(lib().se3_voxel_downsample_stack(_dp(p), elem, None if nr is None else _dp(nr), offsets, C, float(voxel_size), _dp(out),
+                                           None if out_n is None else _dp(out_n), words.data_ptr(), words[C:].data_ptr(), ws.data_ptr(),
+                                           nbytes, stream), 'se3_voxel_downsample_stack')
+    return out, out_n, words
+
+
+def _knn_k(k, what):
+    k = int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise RuntimeError('%s: k %d not in [1, %d]' % (what, k, KNN_MAX))
+    return k
+
+
+def knn_stack(grid, q_points, q_lengths, k):
+    """HIP: the k nearest support points of every query row in its own cloud of `grid` (pair_grid_build with identity transforms and
+    cell_hint 0).  Returns (idx (nq, k) int64 cloud-local, d2 (nq, k) float64), rows ascending by (d2, index); -1 / inf where the cloud
+    has fewer than k points."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'knn_stack')
+    k = _knn_k(k, 'knn_stack')
+    idx = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+    d2 = torch.empty((q.shape[0], k), dtype=torch.float64, device=q.device)
+    check(lib().se3_knn_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, k, _dp(idx), _dp(d2),
+                              _stream()), 'se3_knn_stack')
+    return idx, d2
+
+
+def knn_normals_stack(grid, q_points, q_lengths, k, viewpoints=None):
+    """HIP: the normal of every query row from its k nearest support points, fused (no (nq, k) table is written).  viewpoints: None or
+    (clouds, 3), moved to the host as float64.  Returns (nq, 3) float64."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'knn_normals_stack')
+    k = _knn_k(k, 'knn_normals_stack')
+    view = None
+    if viewpoints is not None:
+        view = torch.as_tensor(viewpoints).detach().to(device='cpu', dtype=torch.float64).contiguous()
+        if tuple(view.shape) != (grid.num_pairs, 3):
+            raise RuntimeError('knn_normals_stack: viewpoints must be (%d, 3)' % grid.num_pairs)
+    out = torch.empty((q.shape[0], 3), dtype=torch.float64, device=q.device)
+    check(lib().se3_knn_normals_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, k,
+                                      None if view is None or grid.num_pairs == 0 else view.data_ptr(), _dp(out), _stream()),
+          'se3_knn_normals_stack')
+    return out

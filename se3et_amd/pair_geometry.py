@@ -4,7 +4,9 @@ kernels (csrc/pair_geometry.hip, csrc/pair_grid.h) in place of the reference's s
   nearest_neighbor_pairs(q_list, s_list, transforms=None, return_index=False)      get_nearest_neighbor per pair
   compute_overlap_pairs(ref_list, src_list, transforms, positive_radius)            (P,) float64
   get_correspondences_pairs(ref_list, src_list, transforms, matching_radius)        list of (n_p, 2) int64
-  calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size, max_points)   overlaps (P,), covariances (P, 6, 6)
+  calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size, max_points, downsample)   overlaps (P,), covariances (P, 6, 6)
+  modified_chamfer_distance_pairs(raw_list, ref_list, src_list, gt_transforms, transforms)   (P,) float64
+  modified_chamfer_distance(raw_points, ref_points, src_points, gt_transform, transform, reduction)   the reference's metric on (B, N, 3)
   get_nearest_neighbor / compute_overlap / get_correspondences / calibrate_ground_truth   the reference's names and signatures: numpy in
                                                                                     and out, upload inside, one pair per call
   write_info_file(file_name, test_pairs)                                            the gt.info text format (benchmark.read_info_file reads it)
@@ -36,7 +38,11 @@ Transforms are (P, 4, 4) float64.
       np.random.choice(nn_indices, max_points, replace=False), on the host (the pattern of SuperPointTargetGenerator: seeded runs equal the
       reference); the 6x6 covariance is sum G^T G over the selected transformed src points, G = [I3 | -[p]x] in the sign layout of
       threedmatch/utils.py:214-221, summed in a fixed order; no selected point gives the zero matrix.  The reference voxel-downsamples
-      with Open3D first; that step is out of scope: the functions take the clouds as given."""
+      both clouds with Open3D at 0.01 first: downsample=0.01 does that on the device (se3et_amd.scan_prep.voxel_downsample_clouds, whose
+      output order is its own, not Open3D's); the default None takes the clouds as given.
+  modified chamfer distance   the reference's formula (modules/registration/metrics.py:8-44) in float64: per pair
+      mean_i |T src_i - nn_raw(T src_i)| + mean_j |ref_j - nn_(T T_gt^-1 raw)(ref_j)|, both terms with the exact nearest neighbour above
+      (no (N, M) distance matrix); T src is formed by a float64 matmul, T T_gt^-1 raw by the support transform above."""
 import os
 
 import numpy as np
@@ -149,9 +155,14 @@ def get_correspondences_pairs(ref_list, src_list, transforms, matching_radius, d
 
 
 @torch.no_grad()
-def calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size=0.006, max_points=5000, device=None):
-    """calibrate_ground_truth (datasets/registration/threedmatch/utils.py:197-228) for P pairs, on the clouds as given (no voxel
-    downsampling).  Returns (overlaps (P,) at 5 voxel_size, covariances (P, 6, 6)) float64 on the device: the records of gt.info."""
+def calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size=0.006, max_points=5000, device=None, downsample=None):
+    """calibrate_ground_truth (datasets/registration/threedmatch/utils.py:197-228) for P pairs.  downsample: None takes the clouds as
+    given; a voxel size (the reference's 0.01) voxel-downsamples both clouds first (se3et_amd.scan_prep).  Returns (overlaps (P,) at
+    5 voxel_size, covariances (P, 6, 6)) float64 on the device: the records of gt.info."""
+    if downsample is not None:
+        from .scan_prep import voxel_downsample_clouds
+        ref_list = voxel_downsample_clouds(list(ref_list), downsample, device=device)
+        src_list = voxel_downsample_clouds(list(src_list), downsample, device=device)
     overlaps, covs = [], []
     dev = _device(device, ref_list, src_list)
     for _, q, ql, s, sl, T in _chunks(ref_list, src_list, transforms, device, 'calibrate_ground_truth_pairs'):
@@ -169,6 +180,38 @@ def calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size=0.00
     if not overlaps:
         return torch.zeros((0,), dtype=torch.float64, device=dev), torch.zeros((0, 6, 6), dtype=torch.float64, device=dev)
     return torch.cat(overlaps), torch.cat(covs, 0)
+
+
+@torch.no_grad()
+def modified_chamfer_distance_pairs(raw_list, ref_list, src_list, gt_transforms, transforms, device=None):
+    """modified_chamfer_distance (modules/registration/metrics.py:8-44) for P pairs of (n, 3) GPU clouds: (P,) float64 on the device.  An
+    empty src or ref cloud gives NaN (the mean of nothing), an empty raw cloud inf."""
+    P = len(raw_list)
+    if not (len(ref_list) == len(src_list) == P):
+        raise ValueError('modified_chamfer_distance_pairs: one raw, ref and src cloud per pair')
+    dev = _device(device, raw_list, ref_list, src_list)
+    T, G = _host_transforms(transforms, P), _host_transforms(gt_transforms, P)
+    srcs = [_cloud(s, dev, 'modified_chamfer_distance_pairs: src cloud %d' % p) for p, s in enumerate(src_list)]
+    Td = T.to(dev)
+    moved = [s.to(torch.float64) @ Td[p, :3, :3].T + Td[p, :3, 3] for p, s in enumerate(srcs)]
+    composed = torch.matmul(T, torch.linalg.inv(G)) if P else T
+    d_pq = nearest_neighbor_pairs(moved, raw_list, None, device=dev)
+    d_qp = nearest_neighbor_pairs(ref_list, raw_list, composed, device=dev)
+    if not P:
+        return torch.zeros((0,), dtype=torch.float64, device=dev)
+    return torch.stack([a.mean() + b.mean() for a, b in zip(d_pq, d_qp)])
+
+
+def modified_chamfer_distance(raw_points, ref_points, src_points, gt_transform, transform, reduction='mean'):
+    """The reference's signature: (B, N, 3) GPU tensors and (B, 4, 4) transforms; reduction 'mean', 'sum' or 'none'.  float64."""
+    assert reduction in ['mean', 'sum', 'none']
+    for name, t in (('raw_points', raw_points), ('ref_points', ref_points), ('src_points', src_points)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError('modified_chamfer_distance: %s must be a GPU tensor' % name)
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] != raw_points.shape[0]:
+            raise RuntimeError('modified_chamfer_distance: %s must be (B, N, 3)' % name)
+    out = modified_chamfer_distance_pairs(list(raw_points), list(ref_points), list(src_points), gt_transform, transform)
+    return out.mean() if reduction == 'mean' else out.sum() if reduction == 'sum' else out
 
 
 # ---- the reference's single-pair functions: numpy in and out -------------------------------------------------------------------------------
@@ -197,10 +240,11 @@ def get_correspondences(ref_points, src_points, transform, matching_radius, devi
     return get_correspondences_pairs([_upload(ref_points, device)], [_upload(src_points, device)], [transform], matching_radius)[0].cpu().numpy()
 
 
-def calibrate_ground_truth(ref_points, src_points, transform, voxel_size=0.006, device=None):
-    """threedmatch.utils.calibrate_ground_truth on point arrays (the reference takes Open3D clouds and voxel-downsamples them first; here the
-    clouds are taken as given): (overlap, covariance (6, 6)) numpy float64."""
-    ov, cov = calibrate_ground_truth_pairs([_upload(ref_points, device)], [_upload(src_points, device)], [transform], voxel_size)
+def calibrate_ground_truth(ref_points, src_points, transform, voxel_size=0.006, device=None, downsample=None):
+    """threedmatch.utils.calibrate_ground_truth on point arrays (the reference takes Open3D clouds and voxel-downsamples them at 0.01
+    first: downsample=0.01; None takes the clouds as given): (overlap, covariance (6, 6)) numpy float64."""
+    ov, cov = calibrate_ground_truth_pairs([_upload(ref_points, device)], [_upload(src_points, device)], [transform], voxel_size,
+                                           downsample=downsample)
     return np.float64(ov.cpu().numpy()[0]), cov[0].cpu().numpy()
 
 
