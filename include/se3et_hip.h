@@ -9,7 +9,10 @@
  *   - three workspaces begin with arrival counters of an in-kernel reduction (se3_dense_norm_fwd, se3_group_norm_stats,
  *     se3_kpconv_so3_fused's split form): they must be ZERO before their first use; every completed call leaves them zero;
  *   - return value: 0 = ok, otherwise an SE3_ERR_* code (the Python host raises RuntimeError, mirroring the
- *     TORCH_CHECK failures of the reference extension, geotransformer/extensions/common/torch_helper.h:6-35).
+ *     TORCH_CHECK failures of the reference extension, geotransformer/extensions/common/torch_helper.h:6-35);
+ *   - this file is the only declaration: the Python binding (se3et_amd/_lib.py) reads each prototype and each integer `#define SE3_*`
+ *     from it.  It maps pointers, int / int32_t, int64_t, uint64_t / unsigned long long, size_t, float and double, and refuses anything
+ *     else (a struct by value, an array or function-pointer parameter), so an entry point keeps to these.
  *
  * Hard limits (requests beyond them return SE3_ERR_UNSUPPORTED, nothing is truncated silently):
  *   - stacked calls take at most SE3_MAX_BATCH = 32 clouds (16 registration pairs per forward);
@@ -977,11 +980,12 @@ int se3_debug_pair_ball_host(const void* q_points, int64_t nq, const void* s_poi
  *                           ordered by one workgroup (quadratic in its members) and summed by one thread: correct, slow.
  *   se3_knn_stack           on a grid built by se3_pair_grid_build over the support clouds (identity transforms, cell_hint 0): out_idx
  *                           (nq, k) int64 cloud-local and out_d2 (nq, k) float64 squared distances, rows ascending by (d^2, index); -1 and
- *                           +inf in the columns a smaller cloud leaves.  k in [1, 64].
+ *                           +inf in the columns a smaller cloud leaves.  k in [1, SE3_KNN_MAX].
  *   se3_knn_normals_stack   the fused form: out_normals (nq, 3) float64 from each row's k neighbours, the tables never leave the registers.
  *                           viewpoints_host: NULL, or (num_clouds, 3) float64 on the HOST (checked finite): n . (viewpoint - p) >= 0.
  *   se3_debug_*_host        the same text on HOST memory for one cloud, no GPU: every pointer a host pointer.  voxel: *status as above;
  *                           normals: the cloud searched in itself, out_covariances (n, 6: xx xy xz yy yz zz) may be NULL. */
+#define SE3_KNN_MAX 64
 size_t se3_voxel_downsample_workspace_bytes(int64_t n_total, int num_clouds);
 int se3_voxel_downsample_stack(const void* points, int elem, const void* normals, const int64_t* offsets_host, int num_clouds, double voxel_size,
                                double* out_points, double* out_normals, int* out_counts, int* status, void* workspace, size_t workspace_bytes,

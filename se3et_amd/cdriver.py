@@ -11,9 +11,9 @@ import torch
 
 from . import caches
 from . import ops as _ops
-from ._lib import check, lib
+from ._lib import CONSTANTS, check, lib
 
-MAX_BLOCKS, MAX_BATCH = 16, 32
+MAX_BLOCKS, MAX_BATCH = CONSTANTS['SE3_MAX_BLOCKS'], CONSTANTS['SE3_MAX_BATCH']        # (they size the plan structs below)
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 

@@ -30,6 +30,7 @@
 namespace {
 #include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
 
+static_assert(kPairKnnMax == SE3_KNN_MAX, "pair_grid.h and include/se3et_hip.h name one limit");
 constexpr int kKnnWaves = 4;          // query rows per workgroup
 constexpr int kJacobiSweeps = 10;     // (a 3x3 matrix is diagonal to rounding after 5 or 6)
 

@@ -14,9 +14,10 @@ import numpy as np
 import torch
 
 from . import ops as _ops
+from ._lib import CONSTANTS
 from .modules.ops import grid_subsample
 
-SE3_MAX_BATCH, SE3_MAX_NEIGHBOR_LIMIT = 32, 64        # include/se3et_hip.h
+SE3_MAX_BATCH, SE3_MAX_NEIGHBOR_LIMIT = CONSTANTS['SE3_MAX_BATCH'], CONSTANTS['SE3_MAX_NEIGHBOR_LIMIT']
 
 
 def cap_coarsest(points, lengths, cap=2000):

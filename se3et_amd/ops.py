@@ -8,7 +8,7 @@ import threading
 import torch
 
 from .caches import CACHE_EPOCH, Derived, Workspace, _Shared, also_clear, clear_caches, clear_weight_caches, validate_weight_caches  # noqa: F401
-from ._lib import check, lib
+from ._lib import CONSTANTS, check, lib
 
 
 # Library GEMM dispatch: through torch a GEMM with a bias epilogue goes to hipBLASLt (descriptor set-up + heuristic query,
@@ -2289,7 +2289,7 @@ def benchmark_summary(rows, is_gt, group_lengths, kitti, inlier_ratio_threshold,
 
 
 # ---- pair ground truth: nearest neighbour, overlap, correspondences, gt.info covariance (csrc/pair_geometry.hip) ---------------------------
-PAIR_MAX_PAIRS = 32          # SE3_PAIR_MAX_PAIRS: pairs per stacked call (se3et_amd/pair_geometry.py chunks longer lists)
+PAIR_MAX_PAIRS = CONSTANTS['SE3_PAIR_MAX_PAIRS']          # pairs per stacked call (se3et_amd/pair_geometry.py chunks longer lists)
 _ws_pair_grid = Workspace(1 << 22)          # the cell grid of the call in flight on a stream
 
 
@@ -2427,7 +2427,7 @@ def pair_info_covariance_stack(src_points, s_lengths, transforms, selected, sele
 
 
 # ---- scan preparation: voxel downsampling, k nearest neighbours, k-NN normals (csrc/voxel_downsample.hip, csrc/knn_normals.hip) ---------------
-KNN_MAX = 64                 # one list entry per lane of a wave
+KNN_MAX = CONSTANTS['SE3_KNN_MAX']                 # one list entry per lane of a wave
 _ws_voxel = Workspace(1 << 22)
 
 

@@ -1,4 +1,5 @@
-"""CPU: the C-ABI library loads and exports every symbol include/se3et_hip.h declares (no compute without a GPU)."""
+"""CPU: the C-ABI library loads and exports every symbol include/se3et_hip.h declares, and the binding reads its signatures and limits from
+that header (no compute without a GPU)."""
 import ctypes
 import os
 import re
@@ -23,6 +24,67 @@ def test_library_exports_every_declared_symbol():
         assert n in _lib.SIGNATURES, 'no ctypes signature for %s' % n
     assert set(_lib.SIGNATURES) == set(names)
     assert b'gfx950' in L.se3_version()
+
+
+def test_signatures_are_the_headers_prototypes():
+    """One prototype per branch of the binding's type map, written out from include/se3et_hip.h: a char* / uint64 / void / size_t return,
+    float, double, uint64_t and size_t among pointers, a struct pointer, T* const*."""
+    from se3et_amd._lib import SIGNATURES
+    vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
+    f32, f64, u64 = ctypes.c_float, ctypes.c_double, ctypes.c_uint64
+    want = {
+        'se3_version': (ctypes.c_char_p, []),
+        'se3_debug_dense_saturated_rows': (u64, [i32]),
+        'se3_debug_kernel_timing': (None, [i32]),
+        'se3_radius_grid_workspace_bytes': (sz, [i64, i32]),
+        'se3_radius_neighbors': (i32, [vp, i64, vp, i64, vp, vp, i32, f32, i32, vp, vp, vp]),
+        'se3_ransac_correspondences_checked_stack': (i32, [vp, vp, vp, i32, f32, i32, i32, u64, vp, f64, i32, vp, sz,
+                                                           vp, vp, vp, vp, vp, vp, vp, vp]),
+        'se3_benchmark_summary': (i32, [vp, vp, vp, i32, i64, i32, f64, f64, f64, f64, vp, vp, vp]),
+        'se3_transformer_forward': (i32, [vp, vp, vp, vp, sz, vp]),
+        'se3_point_order_stages': (i32, [vp, vp, vp, vp, vp, vp, i32, vp]),
+    }
+    for name, (res, args) in want.items():
+        assert SIGNATURES[name][0] is res, name
+        assert SIGNATURES[name][1] == args, name
+
+
+def test_header_reader_on_synthetic_text():
+    from se3et_amd._lib import read_header
+    sigs, consts = read_header('#define SE3_A 7 /* seven */\n#define SE3_S "text"\n#define OTHER 1\n// int se3_hidden(int);\n'
+                               'const char *se3_a(void);\nvoid se3_b(unsigned long long, const float* const* p,\n  int32_t n);')
+    assert consts == {'SE3_A': 7}
+    assert sigs == {'se3_a': (ctypes.c_char_p, []), 'se3_b': (None, [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int])}
+
+
+@pytest.mark.parametrize('text, offender', [('int se3_f(const float* x, short n);', 'short n'),            # an unknown scalar type
+                                            ('long se3_f(int n);', 'long'),
+                                            ('int se3_f(se3_linear_t w, int n);', 'se3_linear_t w'),        # a struct by value
+                                            ('int se3_f(int n, float x[3]);', r'float x\[3\]'),             # an array
+                                            ('int se3_f(void (*done)(int), int n);', r'void \(\*done\)\(int\)')])
+def test_header_reader_refuses_what_it_cannot_map(text, offender):
+    from se3et_amd._lib import read_header
+    with pytest.raises(RuntimeError, match='se3_f.*%s' % offender):
+        read_header(text)
+
+
+def test_limits_are_the_headers_defines():
+    from se3et_amd import _lib, cdriver, data, ops
+    assert _lib.CONSTANTS == {'SE3_OK': 0, 'SE3_ERR_INVALID_ARG': 1, 'SE3_ERR_UNSUPPORTED': 2, 'SE3_ERR_LAUNCH': 3, 'SE3_ERR_WORKSPACE': 4,
+                              'SE3_MAX_BATCH': 32, 'SE3_MAX_NEIGHBOR_LIMIT': 64, 'SE3_MAX_BLOCKS': 16, 'SE3_PAIR_MAX_PAIRS': 32,
+                              'SE3_KNN_MAX': 64}
+    got = {'SE3_MAX_BATCH': data.SE3_MAX_BATCH, 'SE3_MAX_NEIGHBOR_LIMIT': data.SE3_MAX_NEIGHBOR_LIMIT, 'SE3_MAX_BLOCKS': cdriver.MAX_BLOCKS,
+           'SE3_PAIR_MAX_PAIRS': ops.PAIR_MAX_PAIRS, 'SE3_KNN_MAX': ops.KNN_MAX}
+    for name, value in got.items():
+        assert type(value) is int and value == _lib.CONSTANTS[name], name
+    assert type(cdriver.MAX_BATCH) is int and cdriver.MAX_BATCH == _lib.CONSTANTS['SE3_MAX_BATCH']
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    from se3et_amd import _lib
+    monkeypatch.setattr(_lib, 'HEADER', str(tmp_path / 'se3et_hip.h'))
+    with pytest.raises(RuntimeError, match='se3et_hip.h is missing'):
+        _lib._read()
 
 
 def test_plan_structs_match_the_library():
