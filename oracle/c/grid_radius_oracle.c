@@ -9,7 +9,8 @@
  *                         radius result set :432-440, sort by distance :1286-1287) replaced by an exhaustive
  *                         scan that applies the same float32 arithmetic ((dx*dx + dy*dy) + dz*dz < r*r).
  *
- * Pinned against the genuine reference build (oracle/_ref/libref_ext.so) in tests/test_oracle_vs_reference.py
+ * Pinned against the genuine reference build (oracle/_ref/libref_ext.so) in tests/test_oracle_vs_reference.py,
+ * at the geometric edges in tests/test_precompute_edges_cpu.py,
  * and against the committed fixtures tests/golden/precompute_*.npz.
  *
  * Build: gcc -O2 -ffp-contract=off -fPIC -shared (no -march flags: the float expressions must not be fused).

@@ -261,6 +261,12 @@ __device__ __forceinline__ int cell_coord(float v, float org, float inv_cell, in
   return c < 0 ? 0 : (c >= dim ? dim - 1 : c);
 }
 
+// cell coordinate of a QUERY: not clamped to the grid (a query outside the support box still has to see the boundary cells), but kept
+// within two cells of it so that a far-away, infinite or NaN coordinate stays an int (it sees no cell, or cells that hold no hit)
+__device__ __forceinline__ int query_cell(float v, float org, float inv_cell, int dim) {
+  return (int)fminf(fmaxf(floorf((v - org) * inv_cell), -2.f), (float)(dim + 1));
+}
+
 __global__ __launch_bounds__(1024) void grid_bounds_kernel(const float* __restrict__ s, BatchTable bt, float radius,
                                                            GridLayout G) {
   __shared__ float sh[16];
@@ -366,9 +372,8 @@ __global__ __launch_bounds__(256) void radius_grid_search_kernel(const float* __
   const GridMeta m = G.meta[b];
   const int64_t gq = bt.q_start[b] + qi;
   const float qx = q[3 * gq], qy = q[3 * gq + 1], qz = q[3 * gq + 2];
-  // cell coordinates of the query, NOT clamped: a query outside the support box still has to see the boundary cells
-  const int cx = (int)floorf((qx - m.org[0]) * m.inv_cell), cy = (int)floorf((qy - m.org[1]) * m.inv_cell),
-            cz = (int)floorf((qz - m.org[2]) * m.inv_cell);
+  const int cx = query_cell(qx, m.org[0], m.inv_cell, m.dim[0]), cy = query_cell(qy, m.org[1], m.inv_cell, m.dim[1]),
+            cz = query_cell(qz, m.org[2], m.inv_cell, m.dim[2]);
   const int x0 = max(cx - 1, 0), x1 = min(cx + 1, m.dim[0] - 1);
   const int* cs = G.cell_start + (size_t)b * (kCellCap + 1);
   const float4* pts = G.sorted + bt.s_start[b];
@@ -676,12 +681,6 @@ __global__ __launch_bounds__(kWaves* SE3_WAVE) void radius_count_kernel(const fl
     if (lane == 0 && qbase + j < qn) count_note(count_lds, hist_n, c);
   }
   count_flush(count_lds, hist_n, hist + (size_t)slots.slot[b] * hist_n, dropped + slots.slot[b], max_count + b);
-}
-
-// cell coordinate of a QUERY: not clamped to the grid (a query outside the support box still has to see the boundary cells), but kept
-// within two cells of it so that a far-away, infinite or NaN coordinate stays an int (it sees no cell, or cells that hold no hit)
-__device__ __forceinline__ int query_cell(float v, float org, float inv_cell, int dim) {
-  return (int)fminf(fmaxf(floorf((v - org) * inv_cell), -2.f), (float)(dim + 1));
 }
 
 // the 27-cell walk of radius_grid_search_kernel, counting only; a wave takes kGridCountQPW queries one after the other
