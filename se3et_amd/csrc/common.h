@@ -81,13 +81,10 @@ __device__ __forceinline__ void se3_fixed_add(unsigned long long* acc, float v, 
 
 __device__ __forceinline__ int se3_lane() { return threadIdx.x & (SE3_WAVE - 1); }
 
-__device__ __forceinline__ float se3_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ float se3_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
+
+#include "block_ops.h"          // se3_wave_sum, the block scan, the block bounding box, the workspace carver

@@ -231,8 +231,7 @@ enum { kDense, kRows, kCols, kRefNode, kSrcNode, kNumPred, kRefCorr, kSrcCorr, k
 
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T* scratch) {            // fixed order: wave trees, then the four wave sums in wave order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = se3_wave_sum(v);
   const int wave = threadIdx.x / SE3_WAVE;
   __syncthreads();
   if (se3_lane() == 0) scratch[wave] = v;

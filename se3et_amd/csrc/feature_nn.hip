@@ -235,8 +235,6 @@ int segments_for(int64_t nref, int64_t nsrc) {
   return (int)(s < 1 ? 1 : (s > kMaxSegments ? kMaxSegments : s));
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---- correspondence extraction ------------------------------------------------------------------------------------------------------------
 struct CorrView {
   const int64_t* nn_src;     // (nref) pair-local src index of every ref row, -1: none
@@ -303,31 +301,6 @@ __global__ __launch_bounds__(kThreads) void feature_corr_count_kernel(CorrView v
   counts[e] = n;
 }
 
-// a[0, n) counts -> exclusive offsets, a[n] = total; one workgroup, each thread a consecutive chunk
-__global__ __launch_bounds__(1024) void feature_corr_scan_kernel(int64_t* __restrict__ a, int64_t n) {
-  __shared__ int64_t sh[1024];
-  const int t = threadIdx.x;
-  const int64_t chunk = (n + 1023) / 1024;
-  const int64_t lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-  int64_t sum = 0;
-  for (int64_t i = lo; i < hi; i++) sum += a[i];
-  sh[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int64_t u = t >= off ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += u;
-    __syncthreads();
-  }
-  int64_t run = sh[t] - sum;
-  for (int64_t i = lo; i < hi; i++) {
-    const int64_t u = a[i];
-    a[i] = run;
-    run += u;
-  }
-  if (t == 1023) a[n] = sh[1023];
-}
-
 __global__ __launch_bounds__(kThreads) void feature_corr_fill_kernel(CorrView v, const int64_t* __restrict__ offsets, int64_t total,
                                                                      int64_t* __restrict__ out_ref, int64_t* __restrict__ out_src) {
   const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -369,7 +342,9 @@ extern "C" size_t se3_feature_nn_workspace_bytes(int64_t num_ref_rows, int64_t n
   if (num_ref_rows < 0 || num_src_rows < 0) return 0;
   const size_t rows = (size_t)(num_ref_rows + num_src_rows);
   const size_t S = (size_t)segments_for(num_ref_rows, num_src_rows);
-  return align256(rows * sizeof(float)) + 2 * align256(rows * S * sizeof(float)) + 256;
+  Se3Carver c(nullptr);
+  c.take<float>(rows), c.take<float>(rows * S), c.take<int32_t>(rows * S);
+  return c.bytes() + 256;
 }
 
 extern "C" int se3_feature_nn_stack(const float* ref_feats, const float* src_feats, const int64_t* ref_offsets, const int64_t* src_offsets,
@@ -390,10 +365,10 @@ extern "C" int se3_feature_nn_stack(const float* ref_feats, const float* src_fea
   SE3_REQUIRE(workspace && workspace_bytes >= need, SE3_ERR_INVALID_ARG, "feature_nn_stack: workspace of %zu bytes, %zu needed",
               workspace_bytes, need);
   const int S = segments_for(num_ref_rows, num_src_rows), C = channels;
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  float* norms = (float*)base;
-  float* part_v = (float*)(base + align256((size_t)rows * sizeof(float)));
-  int32_t* part_i = (int32_t*)((char*)part_v + align256((size_t)rows * S * sizeof(float)));
+  Se3Carver c((void*)se3_align256((uintptr_t)workspace));
+  float* norms = c.take<float>((size_t)rows);
+  float* part_v = c.take<float>((size_t)rows * S);
+  int32_t* part_i = c.take<int32_t>((size_t)rows * S);
   hipStream_t st = (hipStream_t)stream;
   const unsigned row_blocks = (unsigned)se3_cdiv(rows, kWaves);
   const int ref_strips = (int)se3_cdiv(num_ref_rows, kStrip), src_strips = (int)se3_cdiv(num_src_rows, kStrip);
@@ -424,7 +399,7 @@ extern "C" int se3_feature_corr_count_stack(const int64_t* nn_src_indices, const
   hipStream_t st = (hipStream_t)stream;
   const CorrView v{nn_src_indices, nn_ref_indices, ref_offsets, src_offsets, num_pairs, num_ref_rows, num_src_rows, mode};
   if (rows > 0) feature_corr_count_kernel<<<(unsigned)se3_cdiv(rows, kThreads), kThreads, 0, st>>>(v, entry_offsets);
-  feature_corr_scan_kernel<<<1, 1024, 0, st>>>(entry_offsets, rows);
+  se3_exclusive_scan_i64(entry_offsets, rows, st);
   SE3_CHECK_LAUNCH("feature_corr_count_stack");
   return SE3_OK;
 }

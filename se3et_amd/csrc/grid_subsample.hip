@@ -100,48 +100,6 @@ __host__ __device__ inline unsigned long long bucket_cap_for(int64_t n) {
   return 0ull;
 }
 
-// ---- block-wide helpers (kBlock threads) ---------------------------------------------------------------------------
-__device__ float block_reduce(float v, bool is_max, float* sh) {
-  for (int o = 32; o > 0; o >>= 1) {
-    float t = __shfl_xor(v, o);
-    v = is_max ? fmaxf(v, t) : fminf(v, t);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int w = 1; w < kBlock / 64; w++) r = is_max ? fmaxf(r, sh[w]) : fminf(r, sh[w]);
-  return r;
-}
-
-// exclusive prefix sum of a[0..n) in place (or suffix sum when `reverse`), one workgroup; returns the total
-__device__ int block_scan(int* a, int n, bool reverse, int* sh) {
-  const int t = threadIdx.x;
-  const int chunk = (n + kBlock - 1) / kBlock;
-  const int lo = t * chunk, hi = min(n, lo + chunk);
-  int s = 0;
-  for (int i = lo; i < hi; i++) s += reverse ? a[n - 1 - i] : a[i];
-  __syncthreads();
-  sh[t] = s;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {          // Hillis-Steele inclusive scan over the 1024 partials
-    int v = (t >= off) ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  const int total = sh[kBlock - 1];
-  int run = sh[t] - s;
-  for (int i = lo; i < hi; i++) {
-    int idx = reverse ? n - 1 - i : i;
-    int v = a[idx];
-    a[idx] = run;
-    run += v;
-  }
-  __syncthreads();
-  return total;
-}
-
 // ---- kernels -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void bounds_kernel(const float* __restrict__ pts, const BatchInfo* __restrict__ bip, float voxel,
                                                         Layout L) {
@@ -157,18 +115,14 @@ __global__ __launch_bounds__(kBlock) void bounds_kernel(const float* __restrict_
       mn[d] = fminf(mn[d], v);
       mx[d] = fmaxf(mx[d], v);
     }
-  float rmn[3], rmx[3];
-  for (int d = 0; d < 3; d++) {
-    rmn[d] = block_reduce(mn[d], false, sh);
-    rmx[d] = block_reduce(mx[d], true, sh);
-  }
+  se3_block_bounds<float, kBlock>(mn, mx, sh);
   if (threadIdx.x == 0) {
     CloudMeta m;
     const float inv = (float)(1.0 / (double)voxel);
-    for (int d = 0; d < 3; d++) m.org[d] = __fmul_rn(floorf(__fmul_rn(rmn[d], inv)), voxel);
+    for (int d = 0; d < 3; d++) m.org[d] = __fmul_rn(floorf(__fmul_rn(mn[d], inv)), voxel);
     m.voxel = voxel;
-    m.nx = n > 0 ? (unsigned long long)__fadd_rn(floorf(se3_exact_div(__fsub_rn(rmx[0], m.org[0]), voxel)), 1.0f) : 1ull;
-    m.ny = n > 0 ? (unsigned long long)__fadd_rn(floorf(se3_exact_div(__fsub_rn(rmx[1], m.org[1]), voxel)), 1.0f) : 1ull;
+    m.nx = n > 0 ? (unsigned long long)__fadd_rn(floorf(se3_exact_div(__fsub_rn(mx[0], m.org[0]), voxel)), 1.0f) : 1ull;
+    m.ny = n > 0 ? (unsigned long long)__fadd_rn(floorf(se3_exact_div(__fsub_rn(mx[1], m.org[1]), voxel)), 1.0f) : 1ull;
     m.n_vox = 0;
     m.pad = 0;
     L.meta[b] = m;
@@ -223,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const BatchInfo* __restric
   int* flag = L.vox_off + p0;
   for (int i = threadIdx.x; i < n; i += kBlock) flag[i] = L.vox_at_point[p0 + i] ? 1 : 0;
   __syncthreads();
-  const int nv = block_scan(flag, n, false, sh);
+  const int nv = se3_block_scan<kSe3ScanExclusive>(flag, n, sh);
   for (int i = threadIdx.x; i < n; i += kBlock) {
     const int h1 = L.vox_at_point[p0 + i];
     if (h1) {
@@ -237,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const BatchInfo* __restric
   // 2. CSR offsets over voxel ids
   for (int v = threadIdx.x; v < nv; v += kBlock) L.vox_off[p0 + v] = L.vox_cnt[p0 + v];
   __syncthreads();
-  block_scan(L.vox_off + p0, nv, false, sh);
+  se3_block_scan<kSe3ScanExclusive>(L.vox_off + p0, nv, sh);
   if (threadIdx.x == 0) L.meta[b].n_vox = nv;
 }
 
@@ -351,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void order_kernel(const BatchInfo* __restri
     __syncthreads();
     for (int p = threadIdx.x; p < n; p += kBlock) pw[p] = (first[pbkt[p]] == p) ? cnt[pbkt[p]] : 0;
     __syncthreads();
-    block_scan(pw, n, true, sh);                   // pw[p] = number of nodes in buckets first touched after p
+    se3_block_scan<kSe3ScanSuffix>(pw, n, sh);                   // pw[p] = number of nodes in buckets first touched after p
     for (int p = threadIdx.x; p < n; p += kBlock) {
       const int bk = pbkt[p];
       int later = 0;
@@ -392,38 +346,32 @@ struct Sizes {
 };
 
 size_t carve(int64_t n, int batch, int64_t cap_total, int64_t bk_total, char* base, Layout* L) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  Se3Carver c(base);
   Layout l;
-  l.info = (BatchInfo*)take(sizeof(BatchInfo));
-  l.meta = (CloudMeta*)take(sizeof(CloudMeta) * batch);
-  l.table_key = (unsigned long long*)take(8 * cap_total);
-  l.table_first = (int*)take(4 * cap_total);
-  l.table_cnt = (int*)take(4 * cap_total);
-  l.table_vox = (int*)take(4 * cap_total);
-  l.slot_of_point = (int*)take(4 * n);
-  l.vox_at_point = (int*)take(4 * n);
-  l.vox_key = (unsigned long long*)take(8 * n);
-  l.vox_cnt = (int*)take(4 * n);
-  l.vox_off = (int*)take(4 * n);
-  l.vox_fill = (int*)take(4 * n);
-  l.members = (int*)take(4 * n);
-  l.sel = (int*)take(4 * n);
-  l.seq_a = (int*)take(4 * n);
-  l.seq_b = (int*)take(4 * n);
-  l.pos_bkt = (int*)take(4 * n);
-  l.pos_next = (int*)take(4 * n);
-  l.pos_w = (int*)take(4 * n);
-  l.bk_first = (int*)take(4 * bk_total);
-  l.bk_cnt = (int*)take(4 * bk_total);
-  l.bk_head = (int*)take(4 * bk_total);
+  l.info = c.take<BatchInfo>(1);
+  l.meta = c.take<CloudMeta>(batch);
+  l.table_key = c.take<unsigned long long>(cap_total);
+  l.table_first = c.take<int>(cap_total);
+  l.table_cnt = c.take<int>(cap_total);
+  l.table_vox = c.take<int>(cap_total);
+  l.slot_of_point = c.take<int>(n);
+  l.vox_at_point = c.take<int>(n);
+  l.vox_key = c.take<unsigned long long>(n);
+  l.vox_cnt = c.take<int>(n);
+  l.vox_off = c.take<int>(n);
+  l.vox_fill = c.take<int>(n);
+  l.members = c.take<int>(n);
+  l.sel = c.take<int>(n);
+  l.seq_a = c.take<int>(n);
+  l.seq_b = c.take<int>(n);
+  l.pos_bkt = c.take<int>(n);
+  l.pos_next = c.take<int>(n);
+  l.pos_w = c.take<int>(n);
+  l.bk_first = c.take<int>(bk_total);
+  l.bk_cnt = c.take<int>(bk_total);
+  l.bk_head = c.take<int>(bk_total);
   if (L) *L = l;
-  return (off + 255) & ~(size_t)255;
+  return c.bytes();
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 //   pair_grid_*_kernel          (pair_grid.h) transform + exact bounding box, cell histogram, scan, scatter; batched over pairs.
 //   pair_nearest_kernel         exact 1-NN, one wave per query row of the stacked rows: lanes stride the points of the cells of a ring,
 //                               the wave reduces on (d^2, index), the running best stays in registers, the rings stop by the shell rule.
-//   pair_ball_count_kernel      ball query, pass 1: hits per row.  pair_ball_scan_kernel: exclusive scan over the stacked rows (int64).
+//   pair_ball_count_kernel      ball query, pass 1: hits per row, then se3_exclusive_scan_i64 over the stacked rows (block_ops.h).
 //   pair_ball_fill_kernel       pass 2: each row's (i, j), j ascending (sorted as it is written: no result depends on an atomic).
 //   pair_overlap_kernel         one workgroup per pair: integer count of d_nn < r in a fixed tree, one division.
 //   pair_covariance_kernel      one workgroup per pair: the ten float64 sums of a gt.info covariance, each lane serially over a fixed
@@ -51,18 +51,12 @@ constexpr int kBallThreads = 64;     // query rows per ball-query workgroup
 constexpr int kRowThreads = 256;
 constexpr int kSums = 10;            // n, x, y, z, zz+yy, zz+xx, yy+xx, xy, xz, yz
 
-__device__ __forceinline__ int pair_of_row(const PairRows& rows, int64_t i) {
-  int p = 0;
-  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
-  return p;
-}
-
 __global__ __launch_bounds__(kNnWaves* SE3_WAVE) void pair_nearest_kernel(PairGridView g, const void* __restrict__ q, int elem, PairRows rows,
                                                                           int64_t nq_total, double* __restrict__ dist,
                                                                           int64_t* __restrict__ index) {
   const int64_t i = (int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6);
   if (i >= nq_total) return;                               // (uniform over the wave)
-  const int p = pair_of_row(rows, i);
+  const int p = pg_pair_of_row(rows, i);
   const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
   double d2;
   int j;
@@ -83,32 +77,7 @@ __global__ __launch_bounds__(kBallThreads) void pair_ball_count_kernel(PairGridV
   const int64_t i = (int64_t)blockIdx.x * kBallThreads + threadIdx.x;
   if (i >= nq_total) return;
   const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
-  row_offsets[i] = pg_ball_count(g, pair_of_row(rows, i), qv, r, r2);
-}
-
-// a[0, n) counts -> exclusive offsets, a[n] = total; one workgroup, each thread a consecutive chunk
-__global__ __launch_bounds__(1024) void pair_ball_scan_kernel(int64_t* __restrict__ a, int64_t n) {
-  __shared__ int64_t sh[1024];
-  const int t = threadIdx.x;
-  const int64_t chunk = (n + 1023) / 1024;
-  const int64_t lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-  int64_t sum = 0;
-  for (int64_t i = lo; i < hi; i++) sum += a[i];
-  sh[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int64_t v = t >= off ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t run = sh[t] - sum;
-  for (int64_t i = lo; i < hi; i++) {
-    const int64_t v = a[i];
-    a[i] = run;
-    run += v;
-  }
-  if (t == 1023) a[n] = sh[1023];
+  row_offsets[i] = pg_ball_count(g, pg_pair_of_row(rows, i), qv, r, r2);
 }
 
 __global__ __launch_bounds__(kBallThreads) void pair_ball_fill_kernel(PairGridView g, const void* __restrict__ q, int elem, PairRows rows,
@@ -118,7 +87,7 @@ __global__ __launch_bounds__(kBallThreads) void pair_ball_fill_kernel(PairGridVi
   if (i >= nq_total) return;
   const int64_t base = row_offsets[i], room = row_offsets[i + 1] - base;
   if (base < 0 || room <= 0 || base + room > total) return;           // (offsets that do not belong to `out`: nothing is written)
-  const int p = pair_of_row(rows, i);
+  const int p = pg_pair_of_row(rows, i);
   const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
   pg_ball_fill(g, p, qv, r, r2, i - rows.start[p], out + 2 * base, room);
 }
@@ -143,8 +112,7 @@ __global__ __launch_bounds__(kRowThreads) void pair_overlap_kernel(const double*
 }
 
 __device__ __forceinline__ double block_sum(double v, double* scratch) {   // fixed order: wave trees, then the four wave sums in wave order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = se3_wave_sum(v);
   __syncthreads();
   if (se3_lane() == 0) scratch[threadIdx.x / SE3_WAVE] = v;
   __syncthreads();
@@ -188,18 +156,6 @@ __global__ __launch_bounds__(kRowThreads) void pair_covariance_kernel(const void
   }
 }
 
-// host-side offsets -> PairRows; false unless 0 = offsets[0] <= offsets[1] <= ...
-bool fill_rows(PairRows* rows, const int64_t* offsets, int num_pairs) {
-  rows->n = num_pairs;
-  if (offsets[0] != 0) return false;
-  for (int p = 0; p <= num_pairs; p++) {
-    rows->start[p] = offsets[p];
-    if (p > 0 && offsets[p] < offsets[p - 1]) return false;
-  }
-  for (int p = num_pairs + 1; p <= kPairMaxPairs; p++) rows->start[p] = offsets[num_pairs];
-  return true;
-}
-
 bool finite_transforms(const double* T, int num_pairs) {
   for (int i = 0; i < 16 * num_pairs; i++)
     if (!isfinite(T[i])) return false;
@@ -217,7 +173,7 @@ void fill_transforms(PairTransforms* tf, const double* T, int num_pairs) {
   SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && ns_total >= 0 && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,                \
               name ": %d pairs (at most %d), ns_total %lld, elem %d", num_pairs, kPairMaxPairs, (long long)ns_total, elem);                 \
   PairRows rows;                                                                                                                             \
-  SE3_REQUIRE(fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, name ": offsets must start at 0 and not decrease");          \
+  SE3_REQUIRE(pg_fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, name ": offsets must start at 0 and not decrease");          \
   PairGridLayout G;                                                                                                                          \
   SE3_REQUIRE(pg_carve(ns_total, num_pairs, (char*)grid_workspace, &G) <= workspace_bytes, SE3_ERR_WORKSPACE,                                \
               name ": grid workspace of %zu bytes is too small", workspace_bytes);                                                          \
@@ -239,7 +195,7 @@ extern "C" int se3_pair_grid_build(const void* s_points, int elem, const int64_t
   SE3_REQUIRE(isfinite(cell_hint) && cell_hint >= 0.0, SE3_ERR_INVALID_ARG, "pair_grid_build: cell size hint %g", cell_hint);
   SE3_REQUIRE(finite_transforms(transforms_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_grid_build: non-finite transform");
   PairRows rows;
-  SE3_REQUIRE(fill_rows(&rows, s_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_grid_build: offsets must start at 0 and not decrease");
+  SE3_REQUIRE(pg_fill_rows(&rows, s_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_grid_build: offsets must start at 0 and not decrease");
   const int64_t ns_total = rows.start[num_pairs];
   SE3_REQUIRE(ns_total < (1ll << 31), SE3_ERR_UNSUPPORTED, "pair_grid_build: %lld support points in one call", (long long)ns_total);
   PairGridLayout G;
@@ -279,7 +235,7 @@ extern "C" int se3_pair_ball_count_stack(const void* grid_workspace, size_t work
   if (nq_total > 0)
     pair_ball_count_kernel<<<(unsigned)se3_cdiv(nq_total, kBallThreads), kBallThreads, 0, st>>>(G.view(), q_points, elem, rows, nq_total, radius,
                                                                                                radius * radius, row_offsets);
-  pair_ball_scan_kernel<<<1, 1024, 0, st>>>(row_offsets, nq_total);
+  se3_exclusive_scan_i64(row_offsets, nq_total, st);
   SE3_CHECK_LAUNCH("pair_ball_count_stack");
   return SE3_OK;
 }
@@ -304,7 +260,7 @@ extern "C" int se3_pair_overlap_stack(const double* nn_distances, const int64_t*
               kPairMaxPairs);
   SE3_REQUIRE(isfinite(radius) && radius >= 0.0, SE3_ERR_INVALID_ARG, "pair_overlap_stack: radius %g", radius);
   PairRows rows;
-  SE3_REQUIRE(fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_overlap_stack: offsets must start at 0 and not decrease");
+  SE3_REQUIRE(pg_fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_overlap_stack: offsets must start at 0 and not decrease");
   if (num_pairs == 0) return SE3_OK;
   pair_overlap_kernel<<<(unsigned)num_pairs, kRowThreads, 0, (hipStream_t)stream>>>(nn_distances, rows, radius * radius, out);
   SE3_CHECK_LAUNCH("pair_overlap_stack");
@@ -320,7 +276,7 @@ extern "C" int se3_pair_info_covariance_stack(const void* src_points, int elem, 
               "pair_info_covariance_stack: %d pairs (at most %d), elem %d", num_pairs, kPairMaxPairs, elem);
   SE3_REQUIRE(finite_transforms(transforms_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_info_covariance_stack: non-finite transform");
   PairRows src_rows, sel_rows;
-  SE3_REQUIRE(fill_rows(&src_rows, s_offsets_host, num_pairs) && fill_rows(&sel_rows, selected_offsets_host, num_pairs), SE3_ERR_INVALID_ARG,
+  SE3_REQUIRE(pg_fill_rows(&src_rows, s_offsets_host, num_pairs) && pg_fill_rows(&sel_rows, selected_offsets_host, num_pairs), SE3_ERR_INVALID_ARG,
               "pair_info_covariance_stack: offsets must start at 0 and not decrease");
   if (num_pairs == 0) return SE3_OK;
   PairTransforms tf;

@@ -12,7 +12,7 @@
 // moved (3 float64 per support point, in input order: the transformed cloud), sorted (3 float64 per point, cell by cell), sorted_idx (the
 // pair-local index of each sorted point).  The order of the points INSIDE a cell follows the arrival of the scatter's integer atomics; no
 // result depends on it: the nearest neighbour reduces on (d^2, index), the ball query sorts each row, counts are integers.
-#pragma once
+#pragma once          // (after common.h: the kernels use block_ops.h)
 #include <math.h>
 #include <stdint.h>
 
@@ -45,6 +45,13 @@ struct PairRows {
   int64_t start[kPairMaxPairs + 1];
   int n;
 };
+
+// the pair (or cloud) that owns row i of a stacked array
+PG_HD int pg_pair_of_row(const PairRows& rows, int64_t i) {
+  int p = 0;
+  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  return p;
+}
 
 PG_HD double pg_load(const void* p, int elem, int64_t i) { return elem ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
 
@@ -247,22 +254,16 @@ struct PairGridLayout {
 };
 
 inline size_t pg_carve(int64_t ns_total, int num_pairs, char* base, PairGridLayout* L) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  Se3Carver c(base);
   const size_t n = (size_t)(ns_total > 0 ? ns_total : 1), P = (size_t)(num_pairs > 0 ? num_pairs : 1);
   PairGridLayout l;
-  l.meta = (PairGridMeta*)take(sizeof(PairGridMeta) * P);
-  l.cells = (int*)take(sizeof(int) * P * (kPairCellCap + 1));
-  l.moved = (double*)take(sizeof(double) * 3 * n);
-  l.sorted = (double*)take(sizeof(double) * 3 * n);
-  l.sorted_idx = (int*)take(sizeof(int) * n);
+  l.meta = c.take<PairGridMeta>(P);
+  l.cells = c.take<int>(P * (kPairCellCap + 1));
+  l.moved = c.take<double>(3 * n);
+  l.sorted = c.take<double>(3 * n);
+  l.sorted_idx = c.take<int>(n);
   if (L) *L = l;
-  return (off + 255) & ~(size_t)255;
+  return c.bytes();
 }
 
 // The grid build on host memory, serial, over a workspace laid out by pg_carve in `base` (the debug entries).
@@ -322,24 +323,12 @@ __global__ __launch_bounds__(kPairBoundsThreads) void pair_grid_bounds_kernel(co
       mx[d] = fmax(mx[d], w[d]);
     }
   }
-  double r[6];
-#pragma unroll
-  for (int d = 0; d < 6; d++) {
-    double v = d < 3 ? mn[d] : -mx[d - 3];
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = sh[0];
-    for (int w = 1; w < kPairBoundsThreads / 64; w++) t = fmin(t, sh[w]);
-    r[d] = t;
-  }
+  se3_block_bounds<double, kPairBoundsThreads>(mn, mx, sh);
   if (threadIdx.x == 0) {
     PairGridMeta* m = G.meta + p;
     for (int k = 0; k < 12; k++) m->T[k] = T[k];
     m->s_start = s0, m->ns = n;
-    const double lo[3] = {r[0], r[1], r[2]}, hi[3] = {-r[3], -r[4], -r[5]};
-    pg_make_grid(lo, hi, n, cell_hint, m);
+    pg_make_grid(mn, mx, n, cell_hint, m);
   }
 }
 
@@ -347,42 +336,23 @@ __global__ __launch_bounds__(kPairBoundsThreads) void pair_grid_bounds_kernel(co
 __global__ __launch_bounds__(256) void pair_grid_count_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= ns_total) return;
-  int p = 0;
-  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  const int p = pg_pair_of_row(rows, i);
   atomicAdd(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1);
 }
 
 // one workgroup per pair: counts -> INCLUSIVE ends (the scatter counts each end down to its cell's start); cells[ncells] = ns
 __global__ __launch_bounds__(1024) void pair_grid_scan_kernel(PairGridLayout G) {
   __shared__ int sh[1024];
-  const int p = blockIdx.x, t = threadIdx.x;
-  const int n = G.meta[p].ncells;
-  int* a = G.cells + (size_t)p * (kPairCellCap + 1);
-  const int chunk = (n + 1023) / 1024;
-  const int lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-  int sum = 0;
-  for (int i = lo; i < hi; i++) sum += a[i];
-  sh[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = t >= off ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int run = sh[t] - sum;
-  for (int i = lo; i < hi; i++) {
-    run += a[i];
-    a[i] = run;
-  }
-  if (t == 1023) a[n] = sh[1023];
+  const int n = G.meta[blockIdx.x].ncells;
+  int* a = G.cells + (size_t)blockIdx.x * (kPairCellCap + 1);
+  const int total = se3_block_scan<kSe3ScanInclusive>(a, n, sh);
+  if (threadIdx.x == 0) a[n] = total;
 }
 
 __global__ __launch_bounds__(256) void pair_grid_scatter_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= ns_total) return;
-  int p = 0;
-  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
+  const int p = pg_pair_of_row(rows, i);
   const int64_t s0 = rows.start[p];
   const int pos = atomicSub(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1) - 1;
   for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
@@ -445,13 +415,6 @@ struct PairKnnSerialList {
     d2[t] = cd, j[t] = cj;
   }
 };
-
-// the pair (or cloud) that owns row i of a stacked array
-PG_HD int pg_pair_of_row(const PairRows& rows, int64_t i) {
-  int p = 0;
-  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
-  return p;
-}
 
 // host-side offsets -> PairRows; false unless 0 = offsets[0] <= offsets[1] <= ...
 inline bool pg_fill_rows(PairRows* rows, const int64_t* offsets, int num_pairs) {

@@ -239,21 +239,15 @@ struct GridLayout {
 };
 
 size_t grid_carve(int64_t ns, int batch, char* base, GridLayout* L) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  Se3Carver c(base);
   GridLayout l;
-  l.meta = (GridMeta*)take(sizeof(GridMeta) * batch);
-  l.cell_start = (int*)take(sizeof(int) * (size_t)batch * (kCellCap + 1));
-  l.cell_fill = (int*)take(sizeof(int) * (size_t)batch * kCellCap);
-  l.cell_of = (int*)take(sizeof(int) * (size_t)(ns > 0 ? ns : 1));
-  l.sorted = (float4*)take(sizeof(float4) * (size_t)(ns > 0 ? ns : 1));
+  l.meta = c.take<GridMeta>((size_t)batch);
+  l.cell_start = c.take<int>((size_t)batch * (kCellCap + 1));
+  l.cell_fill = c.take<int>((size_t)batch * kCellCap);
+  l.cell_of = c.take<int>((size_t)(ns > 0 ? ns : 1));
+  l.sorted = c.take<float4>((size_t)(ns > 0 ? ns : 1));
   if (L) *L = l;
-  return (off + 255) & ~(size_t)255;
+  return c.bytes();
 }
 
 __device__ __forceinline__ int cell_coord(float v, float org, float inv_cell, int dim) {
@@ -280,28 +274,18 @@ __global__ __launch_bounds__(1024) void grid_bounds_kernel(const float* __restri
       mn[d] = fminf(mn[d], v);
       mx[d] = fmaxf(mx[d], v);
     }
-  float r[6];
-  for (int d = 0; d < 6; d++) {
-    float v = d < 3 ? mn[d] : -mx[d - 3];
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = sh[0];
-    for (int w = 1; w < 16; w++) t = fminf(t, sh[w]);
-    r[d] = t;
-  }
+  se3_block_bounds<float, 1024>(mn, mx, sh);
   if (threadIdx.x == 0) {
     GridMeta m;
     float ext = 0.f;
-    for (int d = 0; d < 3; d++) ext = fmaxf(ext, (-r[3 + d]) - r[d]);
+    for (int d = 0; d < 3; d++) ext = fmaxf(ext, mx[d] - mn[d]);
     float cell = fmaxf(radius, ext / (float)(kGridCap - 1));
     cell = fmaxf(cell, 1e-20f) * 1.0001f;          // strictly larger than the radius: the 3x3x3 block always covers the ball
     m.inv_cell = 1.0f / cell;
     m.ncells = 1;
     for (int d = 0; d < 3; d++) {
-      m.org[d] = n > 0 ? r[d] : 0.f;
-      int dim = n > 0 ? (int)floorf(((-r[3 + d]) - r[d]) * m.inv_cell) + 1 : 1;
+      m.org[d] = n > 0 ? mn[d] : 0.f;
+      int dim = n > 0 ? (int)floorf((mx[d] - mn[d]) * m.inv_cell) + 1 : 1;
       m.dim[d] = dim < 1 ? 1 : (dim > kGridCap ? kGridCap : dim);
       m.ncells *= m.dim[d];
     }
@@ -325,29 +309,10 @@ __global__ void grid_count_kernel(const float* __restrict__ s, BatchTable bt, Gr
 
 __global__ __launch_bounds__(1024) void grid_scan_kernel(GridLayout G) {
   __shared__ int sh[1024];
-  const int b = blockIdx.x;
-  const int n = G.meta[b].ncells;
-  int* a = G.cell_start + (size_t)b * (kCellCap + 1);
-  const int t = threadIdx.x;
-  const int chunk = (n + 1023) / 1024;
-  const int lo = t * chunk, hi = min(n, lo + chunk);
-  int sum = 0;
-  for (int i = lo; i < hi; i++) sum += a[i];
-  sh[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = (t >= off) ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int run = sh[t] - sum;
-  for (int i = lo; i < hi; i++) {
-    const int v = a[i];
-    a[i] = run;
-    run += v;
-  }
-  if (t == 1023) a[n] = sh[1023];
+  const int n = G.meta[blockIdx.x].ncells;
+  int* a = G.cell_start + (size_t)blockIdx.x * (kCellCap + 1);
+  const int total = se3_block_scan<kSe3ScanExclusive>(a, n, sh);
+  if (threadIdx.x == 0) a[n] = total;
 }
 
 __global__ void grid_scatter_kernel(const float* __restrict__ s, BatchTable bt, GridLayout G) {
@@ -620,12 +585,6 @@ __device__ __forceinline__ void count_flush(const int* lds, int hist_n, int32_t*
   }
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(kWaves* SE3_WAVE) void radius_count_kernel(const float* __restrict__ q, const float* __restrict__ s, BatchTable bt,
                                                                        SlotTable slots, float r2, int hist_n, int32_t* __restrict__ hist,
                                                                        int32_t* __restrict__ dropped, int32_t* __restrict__ max_count) {
@@ -677,7 +636,7 @@ __global__ __launch_bounds__(kWaves* SE3_WAVE) void radius_count_kernel(const fl
   __syncthreads();                                  // (the cleared histogram, also when the support is empty)
 #pragma unroll
   for (int j = 0; j < kCountQPW; j++) {
-    const int c = wave_sum_int(count[j]);
+    const int c = se3_wave_sum(count[j]);
     if (lane == 0 && qbase + j < qn) count_note(count_lds, hist_n, c);
   }
   count_flush(count_lds, hist_n, hist + (size_t)slots.slot[b] * hist_n, dropped + slots.slot[b], max_count + b);
@@ -734,7 +693,7 @@ __global__ __launch_bounds__(256) void radius_grid_count_kernel(const float* __r
       const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dyv, dyv)), __fmul_rn(dzv, dzv));
       count += (valid && (d2 < r2)) ? 1 : 0;
     }
-    count = wave_sum_int(count);
+    count = se3_wave_sum(count);
     if (lane == 0) count_note(count_lds, hist_n, count);
   }
   count_flush(count_lds, hist_n, hist + (size_t)slots.slot[b] * hist_n, dropped + slots.slot[b], max_count + b);

@@ -52,8 +52,6 @@ struct KdHeader {           // 64 bytes
 constexpr int32_t kMagic = 0x6b645433;
 static_assert(sizeof(KdCloud) == 48 && sizeof(KdNode) == 32 && sizeof(KdHeader) == 64, "flattened k-d tree layout");
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Batch {
   int64_t q_start[SE3_MAX_BATCH], q_count[SE3_MAX_BATCH], s_start[SE3_MAX_BATCH], s_count[SE3_MAX_BATCH];
   int n;
@@ -314,8 +312,8 @@ int fill_batch(Batch* bt, const int64_t* q_len, const int64_t* s_len, int batch,
 // at least one point on each side, so there are at most 2 ns - batch nodes).
 extern "C" size_t se3_kdtree_max_bytes(int64_t ns, int batch) {
   if (ns < 0 || batch < 1 || batch > SE3_MAX_BATCH) return 0;
-  return align256(sizeof(KdHeader)) + align256(sizeof(KdCloud) * (size_t)batch) + align256(sizeof(int32_t) * (size_t)(ns + 1)) +
-         align256(sizeof(KdNode) * (size_t)(2 * ns + batch));
+  return se3_align256(sizeof(KdHeader)) + se3_align256(sizeof(KdCloud) * (size_t)batch) + se3_align256(sizeof(int32_t) * (size_t)(ns + 1)) +
+         se3_align256(sizeof(KdNode) * (size_t)(2 * ns + batch));
 }
 
 // HOST memory in, HOST memory out: the reference's k-d tree of every support cloud (nanoflann.hpp:857-1002 as restated in csrc/kdtree_ref.h),
@@ -329,9 +327,9 @@ extern "C" int se3_kdtree_build_host(const float* s_points_host, int64_t ns, con
   KdHeader H{};
   H.magic = kMagic;
   H.batch = batch;
-  H.off_clouds = (int64_t)align256(sizeof(KdHeader));
-  H.off_perm = H.off_clouds + (int64_t)align256(sizeof(KdCloud) * (size_t)batch);
-  H.off_nodes = H.off_perm + (int64_t)align256(sizeof(int32_t) * (size_t)(ns + 1));
+  H.off_clouds = (int64_t)se3_align256(sizeof(KdHeader));
+  H.off_perm = H.off_clouds + (int64_t)se3_align256(sizeof(KdCloud) * (size_t)batch);
+  H.off_nodes = H.off_perm + (int64_t)se3_align256(sizeof(int32_t) * (size_t)(ns + 1));
   KdCloud* clouds = (KdCloud*)(base + H.off_clouds);
   int32_t* perm = (int32_t*)(base + H.off_perm);
   KdNode* nodes = (KdNode*)(base + H.off_nodes);
@@ -392,7 +390,7 @@ extern "C" int se3_kdtree_build_host(const float* s_points_host, int64_t ns, con
 
 extern "C" size_t se3_radius_tie_scratch_bytes(int64_t num_rows, int max_hits) {
   if (num_rows < 0 || max_hits < 0) return 0;
-  return align256(sizeof(unsigned long long) * (size_t)num_rows * (size_t)(max_hits > 0 ? max_hits : 1)) + 256;
+  return se3_align256(sizeof(unsigned long long) * (size_t)num_rows * (size_t)(max_hits > 0 ? max_hits : 1)) + 256;
 }
 
 // Rewrites the rows `tie_rows` (DEVICE int32 list, num_tie_rows entries: what se3_radius_neighbors_ties / _grid_ties flagged) of the

@@ -18,7 +18,7 @@
 namespace {
 
 __device__ double block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = se3_wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -65,8 +65,7 @@ __global__ __launch_bounds__(256) void procrustes_kernel(const float* __restrict
   }
   __shared__ double red[4][16];
   for (int k = 0; k < 16; k++) {
-    double v = m[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const double v = se3_wave_sum(m[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
   }
   __syncthreads();
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(256) void vote_kernel(const float* __restrict__ src
     const float dz = ref[3 * i + 2] - (Tp[8] * sx + Tp[9] * sy + Tp[10] * sz + Tp[11]);
     cnt += (sqrtf(dx * dx + dy * dy + dz * dz) < radius) ? 1 : 0;
   }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  cnt = se3_wave_sum(cnt);
   if ((threadIdx.x & 63) == 0) shv[threadIdx.x >> 6] = cnt;
   __syncthreads();
   if (threadIdx.x == 0) votes[blockIdx.x] = shv[0] + shv[1] + shv[2] + shv[3];

@@ -354,8 +354,7 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
     }
   }
   // the bin entries' gradient -> alpha
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) bin += __shfl_xor(bin, o);
+  bin = se3_wave_sum(bin);
   if ((tid & 63) == 0) s_alpha[tid >> 6] = bin;
   __syncthreads();
   if (tid == 0) {

@@ -24,7 +24,7 @@ struct Arena {
   size_t size, used;
   bool ok;
   void* take(size_t bytes) {
-    const size_t at = (used + 255) & ~(size_t)255;
+    const size_t at = se3_align256(used);
     if (at + bytes > size) {
       ok = false;
       return base;      // (reported by the caller; never dereferenced by a launch: the driver returns before issuing it)

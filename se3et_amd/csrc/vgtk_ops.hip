@@ -240,24 +240,14 @@ __global__ void inter_bucket_count_kernel(const int* __restrict__ nbr, int64_t e
 
 __global__ void exclusive_scan_kernel(const int* __restrict__ count, int64_t total, int64_t* __restrict__ offsets) {
   // single workgroup, chunked: offsets[i] = sum_{j < i} count[j], offsets[total] = grand total
-  __shared__ int64_t carry, part[1024];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  __shared__ int64_t part[1024];
+  int64_t carry = 0;          // (the same in every thread)
   for (int64_t base = 0; base < total; base += 1024) {
     const int64_t i = base + threadIdx.x;
-    const int64_t v = i < total ? count[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const int64_t t = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < total) offsets[i] = carry + part[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += part[1023];
-    __syncthreads();
+    int64_t tile;
+    const int64_t before = se3_block_exclusive<int64_t>(i < total ? count[i] : 0, part, &tile);
+    if (i < total) offsets[i] = carry + before;
+    carry += tile;
   }
   if (threadIdx.x == 0) offsets[total] = carry;
 }

@@ -1,5 +1,6 @@
-// Scan preparation, part 1: Open3D's voxel_down_sample (geotransformer/utils/open3d.py:57-65) for stacked clouds, with the stages of
-// csrc/grid_subsample.hip under Open3D's voxel semantics.  se3et_amd/scan_prep.py carries the same contract.
+// Scan preparation, part 1: Open3D's voxel_down_sample (geotransformer/utils/open3d.py:57-65) for stacked clouds: the stages of
+// csrc/grid_subsample.hip (bounds, hash, rank, fill, select) under Open3D's voxel semantics, on the scan and bounding box of block_ops.h.
+// se3et_amd/scan_prep.py carries the same contract.
 // (SE3_EXACT_FP: the file is built with contraction off.)
 //
 //   voxel_bounds_kernel   one workgroup per cloud: float64 bounding box, the non-finite flag, the extent check, the origin.
@@ -78,28 +79,22 @@ struct VoxelLayout {
 };
 
 size_t vd_carve(int64_t n_total, int num_clouds, char* base, VoxelLayout* L) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  Se3Carver c(base);
   const size_t n = (size_t)(n_total > 0 ? n_total : 1), P = (size_t)(num_clouds > 0 ? num_clouds : 1), T = 2 * n + P;
   VoxelLayout l;
-  l.meta = (VoxelMeta*)take(sizeof(VoxelMeta) * P);
-  l.keys = (unsigned long long*)take(sizeof(unsigned long long) * T);
-  l.first = (int*)take(sizeof(int) * T);
-  l.count = (int*)take(sizeof(int) * (T + n));
+  l.meta = c.take<VoxelMeta>(P);
+  l.keys = c.take<unsigned long long>(T);
+  l.first = c.take<int>(T);
+  l.count = c.take<int>(T + n);
   l.cursor = l.count + T;
-  l.vrank = (int*)take(sizeof(int) * T);
-  l.slot_of = (int*)take(sizeof(int) * n);
-  l.member_start = (int*)take(sizeof(int) * n);
-  l.voxel_count = (int*)take(sizeof(int) * n);
-  l.members = (int*)take(sizeof(int) * n);
-  l.ordered = (int*)take(sizeof(int) * n);
+  l.vrank = c.take<int>(T);
+  l.slot_of = c.take<int>(n);
+  l.member_start = c.take<int>(n);
+  l.voxel_count = c.take<int>(n);
+  l.members = c.take<int>(n);
+  l.ordered = c.take<int>(n);
   if (L) *L = l;
-  return (off + 255) & ~(size_t)255;
+  return c.bytes();
 }
 
 __global__ __launch_bounds__(kVoxelThreads) void voxel_bounds_kernel(const void* __restrict__ pts, const void* __restrict__ nrm, int elem,
@@ -120,24 +115,13 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_bounds_kernel(const void*
       mx[d] = fmax(mx[d], v);
     }
   if (!finite) bad = kVoxelNonFinite;                       // (every writer stores the same word)
-  double r[6];
-#pragma unroll
-  for (int d = 0; d < 6; d++) {
-    double v = d < 3 ? mn[d] : -mx[d - 3];
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = sh[0];
-    for (int w = 1; w < kVoxelThreads / 64; w++) t = fmin(t, sh[w]);
-    r[d] = t;
-  }
+  se3_block_bounds<double, kVoxelThreads>(mn, mx, sh);
   if (threadIdx.x == 0) {
     VoxelMeta* m = L.meta + c;
     int flags = bad;
     for (int d = 0; d < 3; d++) {
-      m->org[d] = vd_origin(r[d], voxel_size);
-      if (n > 0 && !flags && !vd_axis_ok(-r[3 + d], m->org[d], voxel_size)) flags |= kVoxelTooMany;
+      m->org[d] = vd_origin(mn[d], voxel_size);
+      if (n > 0 && !flags && !vd_axis_ok(mx[d], m->org[d], voxel_size)) flags |= kVoxelTooMany;
     }
     m->ok = flags == 0;
     m->flags = flags;
@@ -167,22 +151,6 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_insert_kernel(const void*
   L.slot_of[i] = (int)slot;
 }
 
-// a[lo .. hi) of every thread's chunk -> exclusive prefix over the workgroup; returns this thread's start, *total the sum
-__device__ __forceinline__ int block_exclusive(int sum, int* sh, int* total) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  sh[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = t >= off ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  *total = sh[1023];
-  return sh[t] - sum;
-}
-
 __global__ __launch_bounds__(1024) void voxel_rank_kernel(PairRows rows, VoxelLayout L, int* __restrict__ out_counts) {
   __shared__ int sh[1024];
   const int c = blockIdx.x, t = threadIdx.x;
@@ -192,7 +160,7 @@ __global__ __launch_bounds__(1024) void voxel_rank_kernel(PairRows rows, VoxelLa
   const int lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
   int sum = 0, voxels;
   for (int i = lo; i < hi; i++) sum += L.first[L.slot_of[s0 + i]] == i;
-  int run = block_exclusive(sum, sh, &voxels);
+  int run = se3_block_exclusive(sum, sh, &voxels);
   for (int i = lo; i < hi; i++) {
     const int slot = L.slot_of[s0 + i];
     if (L.first[slot] == i) {
@@ -208,7 +176,7 @@ __global__ __launch_bounds__(1024) void voxel_rank_kernel(PairRows rows, VoxelLa
   sum = 0;
   for (int v = vlo; v < vhi; v++) sum += L.voxel_count[s0 + v];
   int total;
-  run = block_exclusive(sum, sh, &total);
+  run = se3_block_exclusive(sum, sh, &total);
   for (int v = vlo; v < vhi; v++) {
     L.member_start[s0 + v] = run;
     run += L.voxel_count[s0 + v];

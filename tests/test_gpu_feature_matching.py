@@ -238,6 +238,23 @@ def test_extraction_modes_equal_the_twin_and_the_fixture():
         assert np.allclose(d, np.linalg.norm(ref[i].astype(np.float64) - src[j], axis=1), rtol=1e-5)
 
 
+@pytest.mark.parametrize('total', [1, 1023, 1024, 1025, 2049])
+def test_extraction_at_the_chunk_sizes_of_the_entry_scan(total):
+    """ref rows + src rows is the length of the one-workgroup scan of the entry offsets: one entry, the last sizes with one entry per
+    thread, the first with two, an uneven multi-entry size."""
+    from se3et_amd import feature_matching as FM
+    rng = np.random.default_rng(total)
+    ref = rng.normal(size=((total + 1) // 2, 16)).astype(np.float32)
+    src = rng.normal(size=(total // 2, 16)).astype(np.float32)
+    refs, srcs = [_gpu(ref)], [_gpu(src)]
+    nn_src, _, nn_ref, _ = FM.nearest_feature_pairs(refs, srcs)
+    for mode, kwargs in (('one_way', {}), ('mutual', dict(mutual=True))):
+        ci, cj = FM.extract_correspondences_from_feats_pairs(refs, srcs, **kwargs)
+        ti, tj = twin.extract(nn_src[0].cpu().numpy(), nn_ref[0].cpu().numpy(), mode)
+        assert mode != 'one_way' or len(ti) == (len(ref) if len(src) else 0)          # (every ref row has a nearest src row)
+        assert np.array_equal(ci[0].cpu().numpy(), ti) and np.array_equal(cj[0].cpu().numpy(), tj), mode
+
+
 def test_torch_mirror_against_the_matrix_composition():
     from se3et_amd import ops
     from se3et_amd.modules.registration import extract_correspondences_from_feats

@@ -148,6 +148,18 @@ def test_edge_cases_in_one_stacked_call():
         assert np.array_equal(corr[p].cpu().numpy(), tc), name
 
 
+@pytest.mark.parametrize('rows', [1, 1023, 1024, 1025, 2049])
+def test_correspondences_at_the_chunk_sizes_of_the_row_scan(rows):
+    """One pair whose query row count is the length of the one-workgroup scan of row_offsets: one row, the last sizes with one row per
+    thread, the first with two, an uneven multi-row size."""
+    from se3et_amd import pair_geometry as PG
+    rng = np.random.default_rng(rows)
+    q, s, T = rng.uniform(0, 1, (rows, 3)), rng.uniform(0, 1, (2000, 3)), np.eye(4)
+    corr = PG.get_correspondences_pairs([dev(q)], [dev(s)], [T], 0.1)[0].cpu().numpy()
+    want = twin.scan(q, s, T, 0.1)[2]
+    assert len(want) >= rows and np.array_equal(corr, want)          # (~8 support points inside every ball)
+
+
 def test_sixteen_pair_batch_matches_the_twin():
     from se3et_amd import pair_geometry as PG
     from se3et_amd.synthetic import make_pair

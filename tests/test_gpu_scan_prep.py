@@ -51,6 +51,27 @@ def test_voxel_downsample_equals_the_host_entry():
     assert isinstance(a, np.ndarray) and np.array_equal(a, b)
 
 
+def test_voxel_downsample_at_the_chunk_sizes_of_the_rank_scans():
+    """Three clouds of 1023, 1024 and 1025 points in one call: the last sizes at which a thread of voxel_rank_kernel scans one point, and the
+    first with two.  The first two clouds share voxels (both kinds of flag, member lists of several points); the third is a jittered lattice
+    with one point per voxel, so its 1025 voxels take the scan of the member counts past one voxel per thread as well."""
+    from se3et_amd.scan_prep import voxel_downsample_clouds
+    rng = np.random.default_rng(5)
+    v = 0.05
+    lattice = np.stack(np.unravel_index(rng.permutation(11 * 11 * 9)[:1025], (11, 11, 9)), 1) * v + rng.uniform(-0.2 * v, 0.2 * v, (1025, 3))
+    clouds = [rng.uniform(0, 8 * v, (1023, 3)), rng.uniform(0, 8 * v, (1024, 3)), lattice]
+    for dtype in (np.float32, np.float64):
+        group = [np.asarray(p, dtype) for p in clouds]
+        normals = [rng.standard_normal(p.shape).astype(dtype) for p in group]
+        pts, nrm = voxel_downsample_clouds([dev(p) for p in group], v, [dev(n) for n in normals])
+        counts = []
+        for p, n, gp, gn in zip(group, normals, _np(pts), _np(nrm)):
+            hp, hn, status = F.host_voxel(p, v, n)
+            assert status == 0 and gp.shape == hp.shape and np.array_equal(gp, hp) and np.array_equal(gn, hn)
+            counts.append(len(hp))
+        assert counts[0] < 1023 and counts[1] < 1024 and counts[2] == 1025
+
+
 def test_voxel_downsample_refusals():
     from se3et_amd.scan_prep import voxel_downsample_clouds
     p = F.cloud('micro').astype(np.float64)

@@ -29,6 +29,27 @@ def test_inter_zpconv_grouping_matches_reference_twin(golden_dir):
     assert torch.equal(out2, out) and torch.equal(f2.grad, feats.grad)
 
 
+@pytest.mark.parametrize('b,nq,na', [(1, 33, 31), (2, 32, 16), (1, 25, 41), (1, 89, 23), (2, 64, 16), (1, 683, 3)])
+def test_inter_zpconv_backward_at_the_tile_sizes_of_the_bucket_scan(b, nq, na):
+    """b nq na = 1023, 1024, 1025, 2047, 2048, 2049 targets: the backward's exclusive scan over the bucket counts runs in tiles of 1024.
+    Against autograd of the definition out[b, c, k, p, a] = sum_n w[b, p, a, k, n] feats[b, c, idx[b, p, a, k, n], a] in float64."""
+    from se3et_amd import vgtk
+    g = torch.Generator().manual_seed(b * nq * na)
+    c, p, ks, ann = 4, 20, 2, 3
+    idx = torch.randint(0, nq, (b, p, na, ks, ann), generator=g, dtype=torch.int32).cuda()
+    w = torch.rand(b, p, na, ks, ann, generator=g).cuda()
+    feats = torch.randn(b, c, nq, na, generator=g).cuda().requires_grad_(True)
+    cot = torch.randn(b, c, ks, p, na, generator=g).cuda()
+    out = vgtk.inter_zpconv_grouping(idx, w, feats)
+    (out * cot).sum().backward()
+    ref = feats.detach().double().requires_grad_(True)
+    bi, ai = torch.arange(b, device='cuda').view(b, 1, 1, 1, 1), torch.arange(na, device='cuda').view(1, 1, na, 1, 1)
+    want = torch.einsum('bpaknc,bpakn->bckpa', ref.permute(0, 2, 3, 1)[bi, idx.long(), ai], w.double())
+    (want * cot.double()).sum().backward()
+    assert_close(out.detach().cpu(), want.detach().float().cpu(), 1e-5, 'inter zpconv forward')
+    assert_close(feats.grad.cpu(), ref.grad.float().cpu(), 1e-5, 'inter zpconv backward')
+
+
 def test_gather_points_matches_reference_twin(golden_dir):
     from se3et_amd import vgtk
     g = np.load(golden_dir + '/vgtk_ops.npz')
