@@ -1000,6 +1000,46 @@ int se3_debug_knn_host(const void* q_points, int64_t nq, const void* s_points, i
 int se3_debug_knn_normals_host(const void* points, int64_t n, int elem, int k, const double* viewpoint, double* out_normals,
                                double* out_covariances);
 
+/* ---- ICP refinement of stacked pairs (csrc/icp.hip, csrc/icp_core.h) ---------------------------------------------------------------------------
+ * Open3D's registration_icp, point-to-point (no scale) or point-to-plane, for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64 and
+ * resident on the device: a call enqueues every evaluation and update and waits for nothing; the contract is the header comment of
+ * csrc/icp.hip.  Points and normals are (rows, 3) on the device, float32 (elem 0) or float64 (elem 1), promoted on load; pair p owns rows
+ * [src_offsets_host[p], src_offsets_host[p + 1]) of the stacked source (HOST int64, num_pairs + 1 entries from 0).
+ *   se3_icp_stack           grid_workspace: se3_pair_grid_build over the REFERENCE clouds with identity transforms and cell_hint = the
+ *                           correspondence distance (nref_total rows; the reference points are read from it).  ref_normals: (nref_total, 3) of
+ *                           normals_elem, NULL for point-to-point.  T0: (num_pairs, 4, 4) float64 on the DEVICE, ref ~ T0 src.  Results, all on
+ *                           the device: out_transforms (num_pairs, 4, 4) float64, out_fitness and out_rmse float64, out_iterations,
+ *                           out_converged and out_status int per pair; out_correspondences NULL or int64 per stacked source row: the
+ *                           pair-local reference row of the final evaluation, -1 for none.  status is a sum of SE3_ICP_* bits: NONFINITE
+ *                           refuses the pair (NaN transform); TOO_FEW, SINGULAR and EMPTY mark an identity update; STEP_REFUSED a
+ *                           point-to-plane step of 1 rad or more, at which the pair ends with its previous transform.
+ *                           max_iteration in [0, SE3_ICP_MAX_ITERATION]; 0 evaluates T0 only.
+ *   se3_debug_icp_host      the same text for one pair on HOST memory, no GPU, in the same summation order: every pointer a host pointer,
+ *                           T0 and out_transform (4, 4).  trace: NULL, or (max_iteration + 1, n) int64 whose row k receives evaluation k's
+ *                           correspondence per source row; rows of evaluations not made are left untouched.
+ *   se3_debug_icp_sincos_host   the series the point-to-plane update takes sin and cos from, on n HOST values of (-1, 1). */
+enum {                             /* (an enum, not limits: se3et_amd/ops.py reads the names and values from this block) */
+  SE3_ICP_POINT_TO_POINT = 0,      /* mode */
+  SE3_ICP_POINT_TO_PLANE = 1,
+  SE3_ICP_NONFINITE = 1,           /* status bits */
+  SE3_ICP_TOO_FEW = 2,
+  SE3_ICP_SINGULAR = 4,
+  SE3_ICP_EMPTY = 8,
+  SE3_ICP_STEP_REFUSED = 16,
+  SE3_ICP_MAX_ITERATION = 1000
+};
+size_t se3_icp_workspace_bytes(int64_t nsrc_total, int num_pairs);
+int se3_icp_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
+                  const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem, const double* T0,
+                  double max_correspondence_distance, int mode, double relative_fitness, double relative_rmse, int max_iteration,
+                  double* out_transforms, double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged, int* out_status,
+                  int64_t* out_correspondences, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_icp_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
+                       int normals_elem, const double* T0, double max_correspondence_distance, int mode, double relative_fitness,
+                       double relative_rmse, int max_iteration, double* out_transform, double* out_fitness, double* out_rmse,
+                       int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace);
+int se3_debug_icp_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,21 @@
 // Float64 3x3 Kabsch solve shared by the registration kernels (csrc/registration.hip: weighted Procrustes; csrc/ransac.hip: RANSAC
-// hypotheses): a cyclic Jacobi eigen-solve of H^T H, the left singular vectors from H v, the reflection fix by cross products.
+// hypotheses; csrc/icp.hip: the point-to-point update): a cyclic Jacobi eigen-solve of H^T H, the left singular vectors from H v, the
+// reflection fix by cross products.
+// The text is __host__ __device__ and takes its square root from `Math`: KabschLibm is the plain sqrt of the two registration kernels
+// (their arithmetic is what it was); icp.hip passes a root that rounds alike on the host and on the device, and asks for a float64 T.
 #pragma once
+#include <math.h>
+
 #include "common.h"
 
 namespace {
 
-__device__ void jacobi_eig3(double A[3][3], double V[3][3]) {     // symmetric A -> eigenvalues on the diagonal, vectors in V columns
+struct KabschLibm {
+  static __host__ __device__ __forceinline__ double root(double x) { return sqrt(x); }
+};
+
+template <class Math>
+__host__ __device__ void jacobi_eig3(double A[3][3], double V[3][3]) {     // symmetric A -> eigenvalues on the diagonal, vectors in V columns
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) V[i][j] = (i == j) ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 30; sweep++) {
@@ -16,8 +26,8 @@ __device__ void jacobi_eig3(double A[3][3], double V[3][3]) {     // symmetric A
       for (int q = p + 1; q < 3; q++) {
         if (fabs(A[p][q]) < 1e-300) continue;
         const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + Math::root(theta * theta + 1.0));
+        const double c = 1.0 / Math::root(t * t + 1.0), s = t * c;
         for (int k = 0; k < 3; k++) {          // A <- A J
           const double akp = A[k][p], akq = A[k][q];
           A[k][p] = c * akp - s * akq;
@@ -38,7 +48,8 @@ __device__ void jacobi_eig3(double A[3][3], double V[3][3]) {     // symmetric A
 }
 
 // R = V diag(1, 1, det(V U^T)) U^T for H = U S V^T; t = rc - R sc; writes a row-major 4x4
-__device__ void kabsch(const double H_in[3][3], const double sc[3], const double rc[3], float* __restrict__ T) {
+template <class Math = KabschLibm, class Out = float>
+__host__ __device__ void kabsch(const double H_in[3][3], const double sc[3], const double rc[3], Out* __restrict__ T) {
   // R depends only on the direction of H: scale it by an exact power of two so that max |H| lies in [0.5, 1).  The solve's floors
   // below (1e-40, 1e-300) are then relative to H, and R is the same for a problem scaled by 2^k.  A zero H stays zero (identity);
   // NaN entries are skipped by fmax and still reach R; an infinite H is left as it is.
@@ -53,7 +64,7 @@ __device__ void kabsch(const double H_in[3][3], const double sc[3], const double
   double A[3][3], V[3][3];
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) A[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];   // H^T H
-  jacobi_eig3(A, V);
+  jacobi_eig3<Math>(A, V);
   int o[3] = {0, 1, 2};                                   // eigenvalues in descending order
   for (int i = 0; i < 2; i++)
     for (int j = i + 1; j < 3; j++)
@@ -72,7 +83,7 @@ __device__ void kabsch(const double H_in[3][3], const double sc[3], const double
       n2 = 0;
       for (int i = 0; i < 3; i++) { u[1][i] -= d * u[0][i]; n2 += u[1][i] * u[1][i]; }
     }
-    const double inv = n2 > 1e-300 ? 1.0 / sqrt(n2) : 0.0;
+    const double inv = n2 > 1e-300 ? 1.0 / Math::root(n2) : 0.0;
     for (int i = 0; i < 3; i++) u[k][i] *= inv;
     if (n2 <= 1e-300) {                                   // rank < k+1: any unit vector orthogonal to the previous ones
       const double* b = u[0];
@@ -82,7 +93,7 @@ __device__ void kabsch(const double H_in[3][3], const double sc[3], const double
         const double d = e[0] * b[0] + e[1] * b[1] + e[2] * b[2];
         double m2 = 0;
         for (int i = 0; i < 3; i++) { u[1][i] = e[i] - d * b[i]; m2 += u[1][i] * u[1][i]; }
-        for (int i = 0; i < 3; i++) u[1][i] /= sqrt(m2);
+        for (int i = 0; i < 3; i++) u[1][i] /= Math::root(m2);
       }
     }
   }
@@ -97,10 +108,10 @@ __device__ void kabsch(const double H_in[3][3], const double sc[3], const double
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) R[i][j] = v[0][i] * u[0][j] + v[1][i] * u[1][j] + w2[i] * u[2][j];
   for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[i][j];
-    T[4 * i + 3] = (float)(rc[i] - (R[i][0] * sc[0] + R[i][1] * sc[1] + R[i][2] * sc[2]));
+    for (int j = 0; j < 3; j++) T[4 * i + j] = (Out)R[i][j];
+    T[4 * i + 3] = (Out)(rc[i] - (R[i][0] * sc[0] + R[i][1] * sc[1] + R[i][2] * sc[2]));
   }
-  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+  T[12] = (Out)0; T[13] = (Out)0; T[14] = (Out)0; T[15] = (Out)1;
 }
 
 }  // namespace

@@ -55,17 +55,6 @@ PG_HD void kn_covariance(int m, Point&& point, double* C) {
   for (int e = 0; e < 6; e++) C[e] = a[e] / (double)m;
 }
 
-// sqrt rounded to nearest on the host and on the device alike: the device's float64 root is good to an ulp, not to the last bit, so one
-// step on the exact residual x - r r (an fma) settles it
-PG_HD double kn_sqrt(double x) {
-#pragma clang fp contract(off)
-  const double r = sqrt(x);
-  if (!(r > 0.0) || !(r < INFINITY)) return r;
-  const double e = __builtin_fma(-r, r, x);
-  const double c = e / (2.0 * r);
-  return r + c;
-}
-
 // one Jacobi rotation that annihilates a[P][Q]; R is the third index
 template <int P, int Q, int R>
 PG_HD void kn_rotate(double (&a)[3][3], double (&v)[3][3]) {
@@ -75,10 +64,10 @@ PG_HD void kn_rotate(double (&a)[3][3], double (&v)[3][3]) {
   const double den = 2.0 * apq;
   const double theta = (a[Q][Q] - a[P][P]) / den;
   const double tt = theta * theta;
-  const double root = kn_sqrt(tt + 1.0);
+  const double root = pg_sqrt(tt + 1.0);
   const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + root);          // (an overflowing theta gives t = 0: nothing to rotate)
   const double t2 = t * t;
-  const double c = 1.0 / kn_sqrt(t2 + 1.0);
+  const double c = 1.0 / pg_sqrt(t2 + 1.0);
   const double s = t * c;
   const double shift = t * apq;
   a[P][P] = a[P][P] - shift;
@@ -113,7 +102,7 @@ PG_HD void kn_normal(int m, const double* C, double* n) {
   if (a[1][1] < best) x = v[0][1], y = v[1][1], z = v[2][1], best = a[1][1];
   if (a[2][2] < best) x = v[0][2], y = v[1][2], z = v[2][2];
   const double xx = x * x, yy = y * y, zz = z * z;
-  const double len = kn_sqrt((xx + yy) + zz);
+  const double len = pg_sqrt((xx + yy) + zz);
   if (!(len > 0.0) || !(len < INFINITY)) return;                                  // (non-finite input: the fallback)
   x = x / len, y = y / len, z = z / len;
   // the canonical sign: that of the last non-zero of (x, y, z) is made positive, by selects and an exact product by +-1.  (Observed with

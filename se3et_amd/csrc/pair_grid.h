@@ -75,6 +75,17 @@ PG_HD double pg_dist2(const double* q, const double* s) {
   return a + zz;
 }
 
+// sqrt rounded to nearest on the host and on the device alike: the device's float64 root is good to an ulp, not to the last bit, so one
+// step on the exact residual x - r r (an fma) settles it
+PG_HD double pg_sqrt(double x) {
+#pragma clang fp contract(off)
+  const double r = sqrt(x);
+  if (!(r > 0.0) || !(r < INFINITY)) return r;
+  const double e = __builtin_fma(-r, r, x);
+  const double c = e / (2.0 * r);
+  return r + c;
+}
+
 // floor((v - org) / cell) kept inside [-1, dim] (a NaN gives -1); monotone in v
 PG_HD int pg_cell_floor(double v, double org, double inv_cell, int dim) {
   const double f = floor((v - org) * inv_cell);

@@ -2492,3 +2492,65 @@ def knn_normals_stack(grid, q_points, q_lengths, k, viewpoints=None):
                                       None if view is None or grid.num_pairs == 0 else view.data_ptr(), _dp(out), _stream()),
           'se3_knn_normals_stack')
     return out
+
+
+# ---- ICP refinement of stacked pairs (csrc/icp.hip) --------------------------------------------------------------------------------------------
+def _header_enum(prefix):
+    """name -> value of the enumerators `prefix...` of include/se3et_hip.h (its #defines are _lib.CONSTANTS)."""
+    import re
+    from ._lib import HEADER
+    with open(HEADER) as f:
+        text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
+    return {name: int(value) for name, value in re.findall(r'\b(%s\w+)[ \t]*=[ \t]*(\d+)[ \t]*,?[ \t]*$' % prefix, text, flags=re.M)}
+
+
+_ICP = _header_enum('SE3_ICP_')
+ICP_MODES = {'point_to_point': _ICP['SE3_ICP_POINT_TO_POINT'], 'point_to_plane': _ICP['SE3_ICP_POINT_TO_PLANE']}
+ICP_STATUS = {name[len('SE3_ICP_'):].lower(): _ICP[name]
+              for name in ('SE3_ICP_NONFINITE', 'SE3_ICP_TOO_FEW', 'SE3_ICP_SINGULAR', 'SE3_ICP_EMPTY', 'SE3_ICP_STEP_REFUSED')}
+ICP_MAX_ITERATION = _ICP['SE3_ICP_MAX_ITERATION']
+_ws_icp = Workspace(1 << 20)
+
+
+def icp_stack(grid, src_points, src_lengths, init_transforms, max_correspondence_distance, mode, ref_normals=None, relative_fitness=1e-6,
+              relative_rmse=1e-6, max_iteration=30, return_correspondences=False):
+    """HIP: ICP of up to PAIR_MAX_PAIRS stacked pairs, resident on the device.  grid: pair_grid_build over the REFERENCE clouds with identity
+    transforms and cell_hint = max_correspondence_distance; src_points (total, 3) float32 / float64, pair p on the next src_lengths[p] rows;
+    init_transforms (P, 4, 4) float64 on the DEVICE; mode: a key of ICP_MODES; ref_normals (grid.ns_total, 3) float32 / float64 or None.
+    Every launch is enqueued without a host synchronisation.  Returns a dict of device tensors: transforms (P, 4, 4) float64, fitness,
+    inlier_rmse (P,) float64, iterations, converged, status (P,) int32 (status: a sum of the ICP_STATUS bits), and with
+    return_correspondences the final pair-local reference row of every stacked source row (int64, -1 for none)."""
+    s, elem = _pair_points(src_points, 'src_points')
+    P = len(src_lengths)
+    if s.device != grid.device or P != grid.num_pairs:
+        raise RuntimeError('icp_stack: %d pairs on %s expected' % (grid.num_pairs, grid.device))
+    if mode not in ICP_MODES:
+        raise ValueError('icp_stack: estimation %r is not one of %s' % (mode, ', '.join(sorted(ICP_MODES))))
+    offsets = _pair_offsets(src_lengths, s.shape[0], 'icp_stack')
+    T0 = _req(init_transforms, torch.float64, 'init_transforms', 3)
+    if tuple(T0.shape) != (P, 4, 4) or T0.device != s.device:
+        raise RuntimeError('icp_stack: init_transforms must be (%d, 4, 4) on %s' % (P, s.device))
+    nr, nelem = None, 1
+    if ref_normals is not None:
+        nr, nelem = _pair_points(ref_normals, 'ref_normals')
+        if nr.shape[0] != grid.ns_total or nr.device != s.device:
+            raise RuntimeError('icp_stack: ref_normals must be (%d, 3) on %s' % (grid.ns_total, s.device))
+    elif ICP_MODES[mode] == ICP_MODES['point_to_plane']:
+        raise RuntimeError('icp_stack: point_to_plane needs the reference normals')
+    dev = s.device
+    out = {'transforms': torch.empty((P, 4, 4), dtype=torch.float64, device=dev),
+           'fitness': torch.empty((P,), dtype=torch.float64, device=dev), 'inlier_rmse': torch.empty((P,), dtype=torch.float64, device=dev),
+           'iterations': torch.empty((P,), dtype=torch.int32, device=dev), 'converged': torch.empty((P,), dtype=torch.int32, device=dev),
+           'status': torch.empty((P,), dtype=torch.int32, device=dev)}
+    corr = torch.empty((s.shape[0],), dtype=torch.int64, device=dev) if return_correspondences else None
+    nbytes = lib().se3_icp_workspace_bytes(s.shape[0], P)
+    stream = _stream()
+    ws = _ws_icp.get(dev, stream.value, nbytes)
+    check(lib().se3_icp_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(s), elem, offsets, P, None if nr is None else _dp(nr), nelem,
+                              _dp(T0), float(max_correspondence_distance), ICP_MODES[mode], float(relative_fitness), float(relative_rmse),
+                              int(max_iteration), _dp(out['transforms']), _dp(out['fitness']), _dp(out['inlier_rmse']), _dp(out['iterations']),
+                              _dp(out['converged']), _dp(out['status']), None if corr is None else _dp(corr), ws.data_ptr(), nbytes, stream),
+          'se3_icp_stack')
+    if corr is not None:
+        out['correspondences'] = corr
+    return out
