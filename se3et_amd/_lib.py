@@ -30,10 +30,13 @@ def _ctype(spelling, proto, ret=False):
 
 
 def read_header(text):
-    """(signatures, constants) of a C header: name -> (restype, argtypes) of every `ret se3_name(args);`, and its integer `#define SE3_*`s.
+    """(signatures, constants) of a C header: name -> (restype, argtypes) of every `ret se3_name(args);`, and its integer `#define SE3_*`s
+    together with the enumerators `SE3_NAME = integer,` of its enums.
     A prototype outside the closed type map of _ctype raises: a symbol is never left to ctypes' default int signature."""
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
     constants = {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(SE3_\w+)[ \t]+(-?\d+)[ \t]*$', text, flags=re.M)}
+    for body in re.findall(r'\benum\b[^{;]*\{([^}]*)\}', text):
+        constants.update((k, int(v)) for k, v in re.findall(r'\b(SE3_\w+)\s*=\s*(-?\d+)\s*(?:,|$)', body))
     text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
     signatures = {}
     for ret, name, params in re.findall(r'([\w\s*]+?)\b(se3_\w+)\s*\(((?:[^()]|\([^()]*\))*)\)\s*;', text):
@@ -52,7 +55,7 @@ def _read():
         return read_header(f.read())
 
 
-# name -> (restype, argtypes) of every symbol, and the integer limits, that include/se3et_hip.h declares: read once per process
+# name -> (restype, argtypes) of every symbol, and the integer limits and enumerators, that include/se3et_hip.h declares: read once per process
 SIGNATURES, CONSTANTS = _read()
 
 _lib = None

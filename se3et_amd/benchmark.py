@@ -35,48 +35,12 @@ import numpy as np
 import torch
 
 from . import ops as _ops
+from .stacking import as_rows, as_tensor, device_of, device_offsets, lengths, stack, transforms_of
 
 SUMMARY_KEYS = ('PIR', 'PMR>0', 'PMR>=0.1', 'PMR>=0.3', 'PMR>=0.5', 'FMR', 'IR', 'OV', 'FMR_std', 'RR', 'mean_RRE', 'mean_RTE',
                 'median_RRE', 'median_RTE')
 BENCHMARKS = ('3DMatch', '3DLoMatch', 'KITTI')
 MAX_GROUP_PAIRS = 4096
-
-
-def _points(x, device):
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    return t.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
-
-
-def _indices(x, device, cols=None):
-    t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    t = t.to(device=device, dtype=torch.int64)
-    return t.reshape(-1, cols).contiguous() if cols else t.reshape(-1).contiguous()
-
-
-def _transforms(x, n, device, dtype):
-    if isinstance(x, (list, tuple)):
-        if not x:
-            return torch.zeros((0, 4, 4), dtype=dtype, device=device)
-        x = torch.stack([_as_tensor(v).to(device=device, dtype=dtype).reshape(4, 4) for v in x], 0)
-    return _as_tensor(x).to(device=device, dtype=dtype).reshape(n, 4, 4).contiguous()
-
-
-def _as_tensor(x):
-    return x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-
-
-def _offsets(lengths, device):
-    return _ops.to_device(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int64).tolist(), torch.int64, device)
-
-
-def _device(device, *lists):
-    if device is not None:
-        return torch.device(device)
-    for lst in lists:
-        for v in lst:
-            if torch.is_tensor(v) and v.is_cuda:
-                return v.device
-    return torch.device('cuda')
 
 
 @torch.no_grad()
@@ -86,16 +50,16 @@ def evaluate_correspondences_pairs(ref_list, src_list, transforms, positive_radi
     num_corr: (P,) int64} device tensors."""
     if len(ref_list) != len(src_list):
         raise ValueError('evaluate_correspondences_pairs: one ref and one src set per pair')
-    dev = _device(device, ref_list, src_list)
-    refs, srcs = [_points(r, dev) for r in ref_list], [_points(s, dev) for s in src_list]
+    dev = device_of(device, ref_list, src_list)
+    refs, srcs = [as_rows(r, dev) for r in ref_list], [as_rows(s, dev) for s in src_list]
     for p, (r, s) in enumerate(zip(refs, srcs)):
         if r.shape != s.shape:
             raise ValueError('evaluate_correspondences_pairs: pair %d has %d ref and %d src rows' % (p, r.shape[0], s.shape[0]))
-    lengths = [int(r.shape[0]) for r in refs]
+    counts = lengths(refs)
     empty = torch.zeros((0, 3), dtype=torch.float32, device=dev)
-    rows = _ops.benchmark_correspondences_stack(torch.cat(refs, 0) if refs else empty, torch.cat(srcs, 0) if srcs else empty,
-                                                _offsets(lengths, dev), max(lengths, default=0),
-                                                _transforms(transforms, len(refs), dev, torch.float32), positive_radius)
+    T = transforms_of(transforms, len(refs), 'evaluate_correspondences_pairs', dev, torch.float32, error=RuntimeError)
+    rows = _ops.benchmark_correspondences_stack(stack(refs, empty), stack(srcs, empty), device_offsets(counts, dev), max(counts, default=0), T,
+                                                positive_radius)
     return dict(overlap=rows[:, 0], inlier_ratio=rows[:, 1], residual=rows[:, 2], num_corr=rows[:, 3].to(torch.int64))
 
 
@@ -107,17 +71,16 @@ def evaluate_sparse_correspondences_pairs(ref_node_idx_list, src_node_idx_list, 
     P = len(ref_node_idx_list)
     if not (len(src_node_idx_list) == len(gt_node_corr_list) == len(num_ref_nodes) == len(num_src_nodes) == P):
         raise ValueError('evaluate_sparse_correspondences_pairs: one entry per pair in every list')
-    dev = _device(device, ref_node_idx_list, gt_node_corr_list)
-    ri = [_indices(v, dev) for v in ref_node_idx_list]
-    si = [_indices(v, dev) for v in src_node_idx_list]
-    gi = [_indices(v, dev, 2) for v in gt_node_corr_list]
+    dev = device_of(device, ref_node_idx_list, gt_node_corr_list)
+    ri = [as_rows(v, dev, None, torch.int64) for v in ref_node_idx_list]
+    si = [as_rows(v, dev, None, torch.int64) for v in src_node_idx_list]
+    gi = [as_rows(v, dev, 2, torch.int64) for v in gt_node_corr_list]
     for p in range(P):
         if ri[p].shape != si[p].shape:
             raise ValueError('evaluate_sparse_correspondences_pairs: pair %d has mismatched ref / src node indices' % p)
     z1, z2 = torch.zeros((0,), dtype=torch.int64, device=dev), torch.zeros((0, 2), dtype=torch.int64, device=dev)
-    rows = _ops.benchmark_sparse_stack(torch.cat(ri) if ri else z1, torch.cat(si) if si else z1, _offsets([v.shape[0] for v in ri], dev),
-                                       torch.cat(gi, 0) if gi else z2, _offsets([v.shape[0] for v in gi], dev),
-                                       list(zip(num_ref_nodes, num_src_nodes)))
+    rows = _ops.benchmark_sparse_stack(stack(ri, z1), stack(si, z1), device_offsets(lengths(ri), dev), stack(gi, z2),
+                                       device_offsets(lengths(gi), dev), list(zip(num_ref_nodes, num_src_nodes)))
     return dict(precision=rows[:, 0], recall=rows[:, 1], hit_ratio=rows[:, 2])
 
 
@@ -126,19 +89,17 @@ def compute_transform_error_pairs(transforms, covariances, estimated, device=Non
     """compute_transform_error (datasets/registration/threedmatch/utils.py:131-137) and compute_registration_error (registration.py:51-67)
     for P pairs in float64: transforms / estimated (P, 4, 4), covariances (P, 6, 6), a list with None for the pairs without one, or None.
     Returns {err (NaN without covariance), rre, rte: (P,) float64} device tensors."""
-    est_t = _as_tensor(estimated) if not isinstance(estimated, (list, tuple)) else None
-    dev = torch.device(device) if device is not None else (est_t.device if est_t is not None and est_t.is_cuda else torch.device('cuda'))
+    dev = device_of(device, [estimated])
     P = len(estimated)
-    gt = _transforms(transforms, P, dev, torch.float64)
-    est = _transforms(estimated, P, dev, torch.float64)
+    gt, est = (transforms_of(t, P, 'compute_transform_error_pairs', dev, error=RuntimeError) for t in (transforms, estimated))
     cov = has = None
     if covariances is not None:
         if isinstance(covariances, (list, tuple)):
             has = torch.tensor([c is not None for c in covariances], dtype=torch.int32)
-            cov = torch.stack([torch.zeros((6, 6), dtype=torch.float64) if c is None else _as_tensor(c).to(torch.float64).cpu().reshape(6, 6)
+            cov = torch.stack([torch.zeros((6, 6), dtype=torch.float64) if c is None else as_tensor(c).to(torch.float64).cpu().reshape(6, 6)
                                for c in covariances], 0) if P else torch.zeros((0, 6, 6), dtype=torch.float64)
         else:
-            cov = _as_tensor(covariances).to(torch.float64).reshape(P, 6, 6)
+            cov = as_tensor(covariances).to(torch.float64).reshape(P, 6, 6)
             has = torch.ones((P,), dtype=torch.int32)
         cov, has = cov.to(dev).contiguous(), has.to(dev)
     rows = _ops.benchmark_transform_error_stack(gt, est, cov, has)
@@ -301,7 +262,7 @@ class BenchmarkEvaluator:
     def evaluate_outputs(self, outs, transforms, method='lgr', num_corr=None, estimated=None, group='all', seed=0):
         """The B output dicts of batched.forward_pairs(..., ground_truth=True) as one group, transforms (B, 4, 4) their ground truth.
         (3DMatch: no covariances, so only RRE / RTE; RR follows the KITTI rule only for BenchmarkEvaluator(cfg, 'KITTI').)"""
-        transforms = _as_tensor(transforms).reshape(len(outs), 4, 4)
+        transforms = as_tensor(transforms).reshape(len(outs), 4, 4)
         records = [dict(out, transform=transforms[p]) for p, out in enumerate(outs)]
         return self.evaluate(records, [(group, len(records))], method, num_corr, estimated, seed=seed)
 

@@ -30,16 +30,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-
-
-def _feats(x, name):
-    if not torch.is_tensor(x):
-        raise RuntimeError('%s must be a tensor on the device (the numpy drop-ins upload)' % name)
-    if not x.is_cuda:
-        raise RuntimeError('%s must be a GPU tensor (feature matching has no CPU implementation)' % name)
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise RuntimeError('%s must be (n, C) float32, got %s %s' % (name, tuple(x.shape), x.dtype))
-    return x.contiguous()
+from .stacking import device_offsets, gpu_rows_each, lengths, stack, upload
 
 
 def stack_feature_pairs(ref_feats_list, src_feats_list, what='stack_feature_pairs'):
@@ -47,20 +38,16 @@ def stack_feature_pairs(ref_feats_list, src_feats_list, what='stack_feature_pair
     device --, ref lengths, src lengths)."""
     if len(ref_feats_list) != len(src_feats_list):
         raise ValueError('%s: one ref and one src feature array per pair' % what)
-    refs = [_feats(x, '%s: ref_feats %d' % (what, p)) for p, x in enumerate(ref_feats_list)]
-    srcs = [_feats(x, '%s: src_feats %d' % (what, p)) for p, x in enumerate(src_feats_list)]
+    refs, srcs = (gpu_rows_each(lst, None, '%s: %s_feats' % (what, side), 'feature matching', cols=None, dtypes=(torch.float32,))
+                  for side, lst in (('ref', ref_feats_list), ('src', src_feats_list)))
     if not refs:
         raise ValueError('%s: no pairs' % what)
     C = refs[0].shape[1]
     if any(x.shape[1] != C for x in refs + srcs) or C < 1:
         raise RuntimeError('%s: all features must have the same channel count >= 1' % what)
     dev = refs[0].device
-    nl, ml = [int(x.shape[0]) for x in refs], [int(x.shape[0]) for x in srcs]
-    ro = _ops.to_device(np.concatenate([[0], np.cumsum(nl)]).astype(np.int64).tolist(), torch.int64, dev)
-    so = _ops.to_device(np.concatenate([[0], np.cumsum(ml)]).astype(np.int64).tolist(), torch.int64, dev)
-    ref = refs[0] if len(refs) == 1 else torch.cat(refs, 0)
-    src = srcs[0] if len(srcs) == 1 else torch.cat(srcs, 0)
-    return ref, src, ro, so, nl, ml
+    nl, ml = lengths(refs), lengths(srcs)
+    return stack(refs), stack(srcs), device_offsets(nl, dev), device_offsets(ml, dev), nl, ml
 
 
 @torch.no_grad()
@@ -96,10 +83,9 @@ def extract_correspondences_from_feats_pairs(ref_feats_list, src_feats_list, mut
 
 # ---- the reference's numpy functions: one pair, numpy in and out -------------------------------------------------------------------------------
 def _upload(feats, device):
-    a = np.ascontiguousarray(np.asarray(feats), dtype=np.float32)
-    if a.ndim != 2:
+    if np.ndim(feats) != 2:
         raise ValueError('features must be (n, C)')
-    return torch.from_numpy(a).to(device or 'cuda')
+    return upload(feats, device, None, np.float32)
 
 
 def extract_corr_indices_from_feats(ref_feats, src_feats, mutual=False, bilateral=False, device=None):

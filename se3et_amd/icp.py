@@ -40,24 +40,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from .pair_geometry import _cloud, _device, _stack, _upload
-from .scan_prep import _eyes
-
-
-def _init_transforms(init_transforms, P, dev):
-    """(P, 4, 4) float64 on the device: a device tensor of any float dtype is converted there, host arrays are uploaded."""
-    if torch.is_tensor(init_transforms):
-        t = init_transforms
-    else:
-        if isinstance(init_transforms, (list, tuple)) and any(torch.is_tensor(x) for x in init_transforms):
-            init_transforms = [x.detach().cpu().numpy() if torch.is_tensor(x) else x for x in init_transforms]
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(init_transforms, dtype=np.float64).reshape(-1, 4, 4)))
-    if not t.is_floating_point():
-        raise ValueError('icp_pairs: init_transforms must be floating point')
-    t = t.detach().to(device=dev, dtype=torch.float64).reshape(-1, 4, 4).contiguous()
-    if t.shape[0] != P:
-        raise ValueError('icp_pairs: one (4, 4) initial transform per pair: %d given for %d pairs' % (t.shape[0], P))
-    return t
+from .stacking import chunks, device_of, gpu_rows_each, identities, lengths, stack, transforms_of, upload
 
 
 @torch.no_grad()
@@ -79,9 +62,9 @@ def icp_pairs(src_list, ref_list, init_transforms, max_correspondence_distance, 
         raise ValueError('icp_pairs: max_correspondence_distance %r is not a finite, non-negative number' % (max_correspondence_distance,))
     if not 0 <= int(max_iteration) <= _ops.ICP_MAX_ITERATION:
         raise ValueError('icp_pairs: max_iteration %r not in [0, %d]' % (max_iteration, _ops.ICP_MAX_ITERATION))
-    dev = _device(device, src_list, ref_list)
-    srcs = [_cloud(s, dev, 'icp_pairs: source cloud %d' % p) for p, s in enumerate(src_list)]
-    refs = [_cloud(s, dev, 'icp_pairs: reference cloud %d' % p) for p, s in enumerate(ref_list)]
+    dev = device_of(device, src_list, ref_list)
+    srcs = gpu_rows_each(src_list, dev, 'icp_pairs: source cloud', 'ICP')
+    refs = gpu_rows_each(ref_list, dev, 'icp_pairs: reference cloud', 'ICP')
     if srcs:
         dev = srcs[0].device
     normals = None
@@ -92,17 +75,18 @@ def icp_pairs(src_list, ref_list, init_transforms, max_correspondence_distance, 
         else:
             if len(ref_normals_list) != P:
                 raise ValueError('icp_pairs: one normals array per reference cloud')
-            normals = [_cloud(n, dev, 'icp_pairs: normals %d' % p) for p, n in enumerate(ref_normals_list)]
+            normals = gpu_rows_each(ref_normals_list, dev, 'icp_pairs: normals', 'ICP')
             if any(n.shape != q.shape for n, q in zip(normals, refs)):
                 raise ValueError('icp_pairs: normals must have the shape of their reference cloud')
-    T0 = _init_transforms(init_transforms, P, dev)
-    parts, corrs = [], []
-    for a in range(0, P, _ops.PAIR_MAX_PAIRS):
-        b = min(P, a + _ops.PAIR_MAX_PAIRS)
-        s, sl = _stack(srcs[a:b])
-        q, ql = _stack(refs[a:b])
-        nr = _stack(normals[a:b])[0] if normals is not None else None
-        grid = _ops.pair_grid_build(q, ql, _eyes(b - a), r)
+    if torch.is_tensor(init_transforms) and not init_transforms.is_floating_point():
+        raise ValueError('icp_pairs: init_transforms must be floating point')
+    T0 = transforms_of(init_transforms, P, 'icp_pairs', dev)          # (a device tensor is read on the device; no finiteness check here:
+    parts, corrs = [], []                                             # the kernel refuses a non-finite T0 per pair)
+    for a, b in chunks(P):
+        s, sl = stack(srcs[a:b]), lengths(srcs[a:b])
+        q, ql = stack(refs[a:b]), lengths(refs[a:b])
+        nr = stack(normals[a:b]) if normals is not None else None
+        grid = _ops.pair_grid_build(q, ql, identities(b - a), r)
         out = _ops.icp_stack(grid, s, sl, T0[a:b], r, estimation, nr, relative_fitness, relative_rmse, max_iteration, return_correspondences)
         if return_correspondences:
             corrs += list(torch.split(out.pop('correspondences'), sl))
@@ -111,12 +95,8 @@ def icp_pairs(src_list, ref_list, init_transforms, max_correspondence_distance, 
         refused = [a + p for p, w in enumerate(status) if w & _ops.ICP_STATUS['nonfinite']]
         if refused:
             raise ValueError('icp_pairs: pair %s: a point, normal or initial transform is not finite' % ', '.join(str(p) for p in refused))
-    if not parts:
-        parts = [{'transforms': torch.zeros((0, 4, 4), dtype=torch.float64, device=dev),
-                  'fitness': torch.zeros((0,), dtype=torch.float64, device=dev), 'inlier_rmse': torch.zeros((0,), dtype=torch.float64, device=dev),
-                  'iterations': torch.zeros((0,), dtype=torch.int32, device=dev), 'converged': torch.zeros((0,), dtype=torch.int32, device=dev),
-                  'status': torch.zeros((0,), dtype=torch.int32, device=dev)}]
-    result = {k: (parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts], 0)) for k in parts[0]}
+    parts = parts or [_ops.icp_outputs(0, dev)]
+    result = {k: stack([p[k] for p in parts]) for k in parts[0]}
     if return_correspondences:
         result['correspondences'] = corrs
     return result
@@ -127,8 +107,8 @@ def registration_icp(src_points, ref_points, init=None, max_correspondence_dista
     """One pair, numpy in and out (the arrays are uploaded inside the call): the (4, 4) float64 transform src -> ref, refined from `init`
     (None: the identity).  The argument order follows ransac.registration_with_ransac_from_correspondences: source first."""
     init = np.eye(4) if init is None else np.asarray(init, dtype=np.float64).reshape(4, 4)
-    out = icp_pairs([_upload(src_points, device)], [_upload(ref_points, device)], init[None], max_correspondence_distance, estimation,
-                    None if ref_normals is None else [_upload(ref_normals, device)], relative_fitness, relative_rmse, max_iteration)
+    out = icp_pairs([upload(src_points, device)], [upload(ref_points, device)], init[None], max_correspondence_distance, estimation,
+                    None if ref_normals is None else [upload(ref_normals, device)], relative_fitness, relative_rmse, max_iteration)
     return out['transforms'][0].cpu().numpy()
 
 

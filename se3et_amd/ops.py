@@ -9,6 +9,7 @@ import torch
 
 from .caches import CACHE_EPOCH, Derived, Workspace, _Shared, also_clear, clear_caches, clear_weight_caches, validate_weight_caches  # noqa: F401
 from ._lib import CONSTANTS, check, lib
+from .stacking import PAIR_MAX_PAIRS, device_offsets, exclusive_offsets, to_device
 
 
 # Library GEMM dispatch: through torch a GEMM with a bias epilogue goes to hipBLASLt (descriptor set-up + heuristic query,
@@ -1380,13 +1381,6 @@ def neighbor_table_trim(full, width, pair_row_ends, pair_widths):
     return out
 
 
-def to_device(values, dtype, device):
-    """Small host list -> device tensor through pinned memory and an asynchronous copy.  `torch.tensor(values, device=...)`
-    copies from pageable memory, which makes the host wait for everything queued on the stream (a full synchronisation per
-    index table)."""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
-
-
 def _i64_array(values):
     return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
 
@@ -1997,10 +1991,12 @@ def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations
     nbytes = lib().se3_ransac_correspondences_workspace_bytes(P, H)
     ws = torch.empty((max(1, nbytes),), dtype=torch.uint8, device=dev)
     hyp = hypothesis_indices.data_ptr() if hypothesis_indices is not None else None
-    results = (out['transforms'].data_ptr(), out['fitness'].data_ptr(), out['inlier_rmse'].data_ptr(), out['best_hypothesis'].data_ptr(),
+    # (_dp: a call without pairs, or without rows, has empty tensors, and the library refuses null pointers: such a call raised before it
+    # took the dummy pointer, and returns the empty / identity results now; nothing is read or written through it when n = 0)
+    results = (_dp(out['transforms']), _dp(out['fitness']), _dp(out['inlier_rmse']), _dp(out['best_hypothesis']),
                out['counts'].data_ptr() if per_hypothesis else None, out['err_sums'].data_ptr() if per_hypothesis else None)
     if edge_length_similarity is None and not check_distance:
-        check(lib().se3_ransac_correspondences_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn, H,
+        check(lib().se3_ransac_correspondences_stack(_dp(src), _dp(ref), offsets.data_ptr(), P, float(distance_threshold), rn, H,
                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, hyp, ws.data_ptr(), nbytes, *results, _stream()),
               'se3_ransac_correspondences_stack')
         return out
@@ -2008,7 +2004,7 @@ def ransac_stack(src, ref, offsets, distance_threshold, ransac_n, num_iterations
     if edge_length_similarity is not None and not 0.0 < edge <= 1.0:
         raise RuntimeError('ransac_stack: edge_length_similarity = %r outside (0, 1]' % (edge_length_similarity,))
     passed = torch.empty((P, H), dtype=torch.uint8, device=dev) if per_hypothesis else None
-    check(lib().se3_ransac_correspondences_checked_stack(src.data_ptr(), ref.data_ptr(), offsets.data_ptr(), P, float(distance_threshold), rn,
+    check(lib().se3_ransac_correspondences_checked_stack(_dp(src), _dp(ref), offsets.data_ptr(), P, float(distance_threshold), rn,
                                                          H, int(seed) & 0xFFFFFFFFFFFFFFFF, hyp, edge, 1 if check_distance else 0,
                                                          ws.data_ptr(), nbytes, *results,
                                                          passed.data_ptr() if passed is not None else None, _stream()),
@@ -2120,9 +2116,7 @@ def gt_node_overlaps_stack(points_f, points_c, node_lengths, knn, knn_masks, nod
     if transforms.shape[0] != B or tuple(transforms.shape[1:]) != (4, 4):
         raise RuntimeError('gt_node_overlaps_stack: transforms must be (%d, 4, 4)' % B)
     shapes = [(lengths[2 * p], lengths[2 * p + 1]) for p in range(B)]
-    offs = [0]
-    for n, m in shapes:
-        offs.append(offs[-1] + n * m)
+    offs = exclusive_offsets(n * m for n, m in shapes)
     dev = points_c.device
     dense = torch.empty((offs[-1],), dtype=torch.float32, device=dev)
     indices = torch.empty((offs[-1], 2), dtype=torch.int64, device=dev)
@@ -2161,9 +2155,7 @@ def registration_metrics_stack(pairs, gt_transforms, acceptance_overlap, accepta
             sp = _req(sp.contiguous(), torch.float32, 'src_points', 2)
             if sp.shape[1] != 3:
                 raise RuntimeError('registration_metrics_stack: src_points must be (n, 3)')
-        for t in (ov, ri, si, rc, sc, est) + ((sp,) if not kitti else ()):
-            if t.device != dev:
-                raise RuntimeError('registration_metrics_stack: all tensors on %s' % dev)
+        _same_device(dev, (ov, ri, si, rc, sc, est) + ((sp,) if not kitti else ()), 'registration_metrics_stack')
         keep.append((ov, ri, si, rc, sc, est, sp))
         table += [ov.data_ptr(), ov.shape[0], ov.shape[1], ri.data_ptr(), si.data_ptr(), ri.shape[0], rc.data_ptr(), sc.data_ptr(),
                   rc.shape[0], est.data_ptr(), gt_transforms[p].data_ptr(), 0 if kitti else sp.data_ptr(), 0 if kitti else sp.shape[0],
@@ -2224,9 +2216,7 @@ def benchmark_sparse_stack(ref_idx, src_idx, pred_offsets, gt_idx, gt_offsets, n
     counts = [(int(n), int(m)) for n, m in node_counts]
     if any(n < 0 or m < 0 for n, m in counts):
         raise RuntimeError('benchmark_sparse_stack: negative node count')
-    words = [0]
-    for n, m in counts:
-        words.append(words[-1] + lib().se3_benchmark_sparse_words(n, m))
+    words = exclusive_offsets(lib().se3_benchmark_sparse_words(n, m) for n, m in counts)
     host_counts = _i64_array([v for c in counts for v in c] or [0])
     nbytes = lib().se3_benchmark_sparse_workspace_bytes(host_counts, P)
     if nbytes != 4 * words[-1]:
@@ -2279,7 +2269,7 @@ def benchmark_summary(rows, is_gt, group_lengths, kitti, inlier_ratio_threshold,
         raise RuntimeError('benchmark_summary: rows (P, 6), is_gt (P,) and group lengths summing to P expected')
     dev = rows.device
     _same_device(dev, (is_gt,), 'benchmark_summary')
-    offsets = to_device([0] + [int(v) for v in torch.tensor(lengths, dtype=torch.int64).cumsum(0).tolist()], torch.int64, dev)
+    offsets = device_offsets(lengths, dev)
     groups = torch.empty((max(G, 1), 14), dtype=torch.float64, device=dev)
     overall = torch.empty((14,), dtype=torch.float64, device=dev)
     check(lib().se3_benchmark_summary(rows.data_ptr(), is_gt.data_ptr(), offsets.data_ptr(), G, max(lengths, default=0), 1 if kitti else 0,
@@ -2289,7 +2279,6 @@ def benchmark_summary(rows, is_gt, group_lengths, kitti, inlier_ratio_threshold,
 
 
 # ---- pair ground truth: nearest neighbour, overlap, correspondences, gt.info covariance (csrc/pair_geometry.hip) ---------------------------
-PAIR_MAX_PAIRS = CONSTANTS['SE3_PAIR_MAX_PAIRS']          # pairs per stacked call (se3et_amd/pair_geometry.py chunks longer lists)
 _ws_pair_grid = Workspace(1 << 22)          # the cell grid of the call in flight on a stream
 
 
@@ -2307,10 +2296,7 @@ def _pair_offsets(lengths, rows, what):
     lengths = [int(n) for n in lengths]
     if len(lengths) > PAIR_MAX_PAIRS or any(n < 0 for n in lengths) or sum(lengths) != rows:
         raise RuntimeError('%s: at most %d pairs per call, with lengths that sum to the %d rows given' % (what, PAIR_MAX_PAIRS, rows))
-    offsets = [0]
-    for n in lengths:
-        offsets.append(offsets[-1] + n)
-    return _i64_array(offsets)
+    return _i64_array(exclusive_offsets(lengths))
 
 
 def _pair_transforms(transforms, P, what):
@@ -2495,21 +2481,17 @@ def knn_normals_stack(grid, q_points, q_lengths, k, viewpoints=None):
 
 
 # ---- ICP refinement of stacked pairs (csrc/icp.hip) --------------------------------------------------------------------------------------------
-def _header_enum(prefix):
-    """name -> value of the enumerators `prefix...` of include/se3et_hip.h (its #defines are _lib.CONSTANTS)."""
-    import re
-    from ._lib import HEADER
-    with open(HEADER) as f:
-        text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
-    return {name: int(value) for name, value in re.findall(r'\b(%s\w+)[ \t]*=[ \t]*(\d+)[ \t]*,?[ \t]*$' % prefix, text, flags=re.M)}
-
-
-_ICP = _header_enum('SE3_ICP_')
-ICP_MODES = {'point_to_point': _ICP['SE3_ICP_POINT_TO_POINT'], 'point_to_plane': _ICP['SE3_ICP_POINT_TO_PLANE']}
-ICP_STATUS = {name[len('SE3_ICP_'):].lower(): _ICP[name]
-              for name in ('SE3_ICP_NONFINITE', 'SE3_ICP_TOO_FEW', 'SE3_ICP_SINGULAR', 'SE3_ICP_EMPTY', 'SE3_ICP_STEP_REFUSED')}
-ICP_MAX_ITERATION = _ICP['SE3_ICP_MAX_ITERATION']
+ICP_MODES = {'point_to_point': CONSTANTS['SE3_ICP_POINT_TO_POINT'], 'point_to_plane': CONSTANTS['SE3_ICP_POINT_TO_PLANE']}
+ICP_STATUS = {name.lower(): CONSTANTS['SE3_ICP_' + name] for name in ('NONFINITE', 'TOO_FEW', 'SINGULAR', 'EMPTY', 'STEP_REFUSED')}
+ICP_MAX_ITERATION = CONSTANTS['SE3_ICP_MAX_ITERATION']
 _ws_icp = Workspace(1 << 20)
+
+
+def icp_outputs(P, dev):
+    """The uninitialised result tensors of icp_stack for P pairs (P = 0: the result of a call without pairs)."""
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    return {'transforms': torch.empty((P, 4, 4), **f64), 'fitness': torch.empty((P,), **f64), 'inlier_rmse': torch.empty((P,), **f64),
+            'iterations': torch.empty((P,), **i32), 'converged': torch.empty((P,), **i32), 'status': torch.empty((P,), **i32)}
 
 
 def icp_stack(grid, src_points, src_lengths, init_transforms, max_correspondence_distance, mode, ref_normals=None, relative_fitness=1e-6,
@@ -2538,10 +2520,7 @@ def icp_stack(grid, src_points, src_lengths, init_transforms, max_correspondence
     elif ICP_MODES[mode] == ICP_MODES['point_to_plane']:
         raise RuntimeError('icp_stack: point_to_plane needs the reference normals')
     dev = s.device
-    out = {'transforms': torch.empty((P, 4, 4), dtype=torch.float64, device=dev),
-           'fitness': torch.empty((P,), dtype=torch.float64, device=dev), 'inlier_rmse': torch.empty((P,), dtype=torch.float64, device=dev),
-           'iterations': torch.empty((P,), dtype=torch.int32, device=dev), 'converged': torch.empty((P,), dtype=torch.int32, device=dev),
-           'status': torch.empty((P,), dtype=torch.int32, device=dev)}
+    out = icp_outputs(P, dev)
     corr = torch.empty((s.shape[0],), dtype=torch.int64, device=dev) if return_correspondences else None
     nbytes = lib().se3_icp_workspace_bytes(s.shape[0], P)
     stream = _stream()

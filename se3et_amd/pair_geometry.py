@@ -49,66 +49,21 @@ import numpy as np
 import torch
 
 from . import ops as _ops
+from .stacking import chunks, device_of, gpu_rows_each, lengths, stack, transforms_of, upload
 
-
-def _device(device, *lists):
-    if device is not None:
-        return torch.device(device)
-    for lst in lists:
-        for v in lst:
-            if torch.is_tensor(v) and v.is_cuda:
-                return v.device
-    return torch.device('cuda')
-
-
-def _cloud(x, dev, name):
-    if not torch.is_tensor(x):
-        raise RuntimeError('%s must be a tensor on the device (the numpy wrappers upload)' % name)
-    if not x.is_cuda:
-        raise RuntimeError('%s must be a GPU tensor (pair ground truth has no CPU implementation)' % name)
-    if (dev.index is not None and x.device != dev) or x.dtype not in (torch.float32, torch.float64) or x.dim() != 2 or x.shape[1] != 3:
-        raise RuntimeError('%s must be (n, 3) float32 or float64 on %s' % (name, dev))
-    return x.contiguous()
-
-
-def _stack(clouds):
-    """One stacked tensor of a chunk's clouds (float64 unless all are float32) and their lengths; a single cloud is passed as it is."""
-    if len(clouds) == 1:
-        return clouds[0], [int(clouds[0].shape[0])]
-    dtype = torch.float32 if all(c.dtype == torch.float32 for c in clouds) else torch.float64
-    return torch.cat([c.to(dtype) for c in clouds], 0), [int(c.shape[0]) for c in clouds]
-
-
-def _host_transforms(transforms, P):
-    """(P, 4, 4) float64 on the host; None: identities (the support is searched as given)."""
-    if transforms is None:
-        return torch.eye(4, dtype=torch.float64).repeat(P, 1, 1)
-    if isinstance(transforms, (list, tuple)):
-        transforms = np.stack([np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, np.float64).reshape(4, 4) for t in transforms], 0) \
-            if len(transforms) else np.zeros((0, 4, 4))
-    t = transforms.detach().cpu() if torch.is_tensor(transforms) else torch.as_tensor(np.asarray(transforms))
-    t = t.to(torch.float64).reshape(-1, 4, 4).contiguous()
-    if t.shape[0] != P:
-        raise ValueError('one (4, 4) transform per pair: %d given for %d pairs' % (t.shape[0], P))
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError('non-finite transform')
-    return t
+_FAMILY = 'pair ground truth'
 
 
 def _chunks(q_list, s_list, transforms, device, what):
     """Validated clouds in chunks of at most ops.PAIR_MAX_PAIRS pairs: (first pair, q stacked, q lengths, s stacked, s lengths, T)."""
     if len(q_list) != len(s_list):
         raise ValueError('%s: one query and one support cloud per pair' % what)
-    dev = _device(device, q_list, s_list)
-    P = len(q_list)
-    qs = [_cloud(q, dev, '%s: query cloud %d' % (what, p)) for p, q in enumerate(q_list)]
-    ss = [_cloud(s, dev, '%s: support cloud %d' % (what, p)) for p, s in enumerate(s_list)]
-    T = _host_transforms(transforms, P)
-    for a in range(0, P, _ops.PAIR_MAX_PAIRS):
-        b = min(P, a + _ops.PAIR_MAX_PAIRS)
-        q, ql = _stack(qs[a:b])
-        s, sl = _stack(ss[a:b])
-        yield a, q, ql, s, sl, T[a:b]
+    dev = device_of(device, q_list, s_list)
+    qs = gpu_rows_each(q_list, dev, what + ': query cloud', _FAMILY)
+    ss = gpu_rows_each(s_list, dev, what + ': support cloud', _FAMILY)
+    T = transforms_of(transforms, len(qs), what, 'cpu', finite=True)
+    for a, b in chunks(len(qs)):
+        yield a, stack(qs[a:b]), lengths(qs[a:b]), stack(ss[a:b]), lengths(ss[a:b]), T[a:b]
 
 
 @torch.no_grad()
@@ -130,12 +85,12 @@ def compute_overlap_pairs(ref_list, src_list, transforms, positive_radius, devic
     """compute_overlap (utils/registration.py:149-155) for P pairs: the fraction of ref points whose nearest transformed src point is
     closer than positive_radius.  Returns (P,) float64 on the device."""
     out = []
-    dev = _device(device, ref_list, src_list)
+    dev = device_of(device, ref_list, src_list)
     for _, q, ql, s, sl, T in _chunks(ref_list, src_list, transforms, device, 'compute_overlap_pairs'):
         grid = _ops.pair_grid_build(s, sl, T, 0.0)
         d, _i = _ops.pair_nearest_neighbor_stack(grid, q, ql)
         out.append(_ops.pair_overlap_stack(d, ql, positive_radius))
-    return torch.cat(out) if out else torch.zeros((0,), dtype=torch.float64, device=dev)
+    return stack(out, torch.empty((0,), dtype=torch.float64, device=dev))
 
 
 @torch.no_grad()
@@ -164,7 +119,7 @@ def calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size=0.00
         ref_list = voxel_downsample_clouds(list(ref_list), downsample, device=device)
         src_list = voxel_downsample_clouds(list(src_list), downsample, device=device)
     overlaps, covs = [], []
-    dev = _device(device, ref_list, src_list)
+    dev = device_of(device, ref_list, src_list)
     for _, q, ql, s, sl, T in _chunks(ref_list, src_list, transforms, device, 'calibrate_ground_truth_pairs'):
         grid = _ops.pair_grid_build(s, sl, T, 0.0)
         d, i = _ops.pair_nearest_neighbor_stack(grid, q, ql)
@@ -176,10 +131,9 @@ def calibrate_ground_truth_pairs(ref_list, src_list, transforms, voxel_size=0.00
             if sel.shape[0] > max_points:          # the reference's draw, on the host and on numpy's global generator
                 sel = torch.from_numpy(np.random.choice(sel.cpu().numpy(), max_points, replace=False)).to(q.device)
             selected.append(sel)
-        covs.append(_ops.pair_info_covariance_stack(s, sl, T, torch.cat(selected), [int(v.shape[0]) for v in selected]))
-    if not overlaps:
-        return torch.zeros((0,), dtype=torch.float64, device=dev), torch.zeros((0, 6, 6), dtype=torch.float64, device=dev)
-    return torch.cat(overlaps), torch.cat(covs, 0)
+        covs.append(_ops.pair_info_covariance_stack(s, sl, T, torch.cat(selected), lengths(selected)))
+    return stack(overlaps, torch.empty((0,), dtype=torch.float64, device=dev)), \
+        stack(covs, torch.empty((0, 6, 6), dtype=torch.float64, device=dev))
 
 
 @torch.no_grad()
@@ -189,9 +143,9 @@ def modified_chamfer_distance_pairs(raw_list, ref_list, src_list, gt_transforms,
     P = len(raw_list)
     if not (len(ref_list) == len(src_list) == P):
         raise ValueError('modified_chamfer_distance_pairs: one raw, ref and src cloud per pair')
-    dev = _device(device, raw_list, ref_list, src_list)
-    T, G = _host_transforms(transforms, P), _host_transforms(gt_transforms, P)
-    srcs = [_cloud(s, dev, 'modified_chamfer_distance_pairs: src cloud %d' % p) for p, s in enumerate(src_list)]
+    dev = device_of(device, raw_list, ref_list, src_list)
+    T, G = (transforms_of(t, P, 'modified_chamfer_distance_pairs', 'cpu', finite=True) for t in (transforms, gt_transforms))
+    srcs = gpu_rows_each(src_list, dev, 'modified_chamfer_distance_pairs: src cloud', _FAMILY)
     Td = T.to(dev)
     moved = [s.to(torch.float64) @ Td[p, :3, :3].T + Td[p, :3, 3] for p, s in enumerate(srcs)]
     composed = torch.matmul(T, torch.linalg.inv(G)) if P else T
@@ -215,35 +169,28 @@ def modified_chamfer_distance(raw_points, ref_points, src_points, gt_transform, 
 
 
 # ---- the reference's single-pair functions: numpy in and out -------------------------------------------------------------------------------
-def _upload(points, device):
-    a = np.asarray(points)
-    if a.dtype != np.float32:
-        a = a.astype(np.float64, copy=False)
-    return torch.from_numpy(np.ascontiguousarray(a.reshape(-1, 3))).to(device or 'cuda')
-
-
 def get_nearest_neighbor(q_points, s_points, return_index=False, device=None):
     """geotransformer.utils.pointcloud.get_nearest_neighbor: distances (and indices) as numpy arrays."""
-    d, i = nearest_neighbor_pairs([_upload(q_points, device)], [_upload(s_points, device)], None, True)
+    d, i = nearest_neighbor_pairs([upload(q_points, device)], [upload(s_points, device)], None, True)
     return (d[0].cpu().numpy(), i[0].cpu().numpy()) if return_index else d[0].cpu().numpy()
 
 
 def compute_overlap(ref_points, src_points, transform=None, positive_radius=0.1, device=None):
     """geotransformer.utils.registration.compute_overlap: a numpy float64."""
-    ov = compute_overlap_pairs([_upload(ref_points, device)], [_upload(src_points, device)], None if transform is None else [transform],
+    ov = compute_overlap_pairs([upload(ref_points, device)], [upload(src_points, device)], None if transform is None else [transform],
                                positive_radius)
     return np.float64(ov.cpu().numpy()[0])
 
 
 def get_correspondences(ref_points, src_points, transform, matching_radius, device=None):
     """geotransformer.utils.registration.get_correspondences: (n, 2) int64 numpy."""
-    return get_correspondences_pairs([_upload(ref_points, device)], [_upload(src_points, device)], [transform], matching_radius)[0].cpu().numpy()
+    return get_correspondences_pairs([upload(ref_points, device)], [upload(src_points, device)], [transform], matching_radius)[0].cpu().numpy()
 
 
 def calibrate_ground_truth(ref_points, src_points, transform, voxel_size=0.006, device=None, downsample=None):
     """threedmatch.utils.calibrate_ground_truth on point arrays (the reference takes Open3D clouds and voxel-downsamples them at 0.01
     first: downsample=0.01; None takes the clouds as given): (overlap, covariance (6, 6)) numpy float64."""
-    ov, cov = calibrate_ground_truth_pairs([_upload(ref_points, device)], [_upload(src_points, device)], [transform], voxel_size,
+    ov, cov = calibrate_ground_truth_pairs([upload(ref_points, device)], [upload(src_points, device)], [transform], voxel_size,
                                            downsample=downsample)
     return np.float64(ov.cpu().numpy()[0]), cov[0].cpu().numpy()
 

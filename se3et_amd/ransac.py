@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
+from .stacking import as_rows, device_offsets, exclusive_offsets, lengths, stack, upload
 
 _MASK = (1 << 64) - 1
 _GAMMA, _M1, _M2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
@@ -71,11 +72,6 @@ def sample_indices(seed, n, num_iterations, ransac_n):
         return ((u * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
 
 
-def _device_points(x, device):
-    t = torch.as_tensor(x) if not torch.is_tensor(x) else x
-    return t.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
-
-
 @torch.no_grad()
 def ransac_pairs(src_list, ref_list, distance_threshold, ransac_n, num_iterations, seed=0, correspondences=None, hypothesis_indices=None,
                  per_hypothesis=False, device='cuda', edge_length_similarity=None, check_distance=False):
@@ -86,24 +82,21 @@ def ransac_pairs(src_list, ref_list, distance_threshold, ransac_n, num_iteration
     edge_length_similarity / check_distance: the optional checkers of the module docstring (with per_hypothesis also passed (P, H) bool)."""
     if len(src_list) != len(ref_list) or (correspondences is not None and len(correspondences) != len(src_list)):
         raise ValueError('ransac_pairs: one src, ref (and correspondence table) per pair')
-    if len(src_list) and torch.is_tensor(src_list[0]) and src_list[0].is_cuda:
-        device = src_list[0].device
+    if len(src_list) and torch.is_tensor(src_list[0]) and src_list[0].is_cuda:          # (the first src cloud's device wins over `device`:
+        device = src_list[0].device                                                      # not the rule of stacking.device_of)
     srcs, refs = [], []
     for p, (s, r) in enumerate(zip(src_list, ref_list)):
-        s, r = _device_points(s, device), _device_points(r, device)
+        s, r = as_rows(s, device), as_rows(r, device)
         if correspondences is not None and correspondences[p] is not None:
-            c = torch.as_tensor(correspondences[p]) if not torch.is_tensor(correspondences[p]) else correspondences[p]
-            c = c.to(device=device, dtype=torch.int64).reshape(-1, 2)
+            c = as_rows(correspondences[p], device, 2, torch.int64)
             s, r = s[c[:, 0]], r[c[:, 1]]
         elif s.shape != r.shape:
             raise ValueError('ransac_pairs: pair %d has %d src and %d ref rows' % (p, s.shape[0], r.shape[0]))
         srcs.append(s)
         refs.append(r)
-    lengths = [int(s.shape[0]) for s in srcs]
-    offsets = _ops.to_device(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64).tolist(), torch.int64, device)
+    offsets = device_offsets(lengths(srcs), device)
     empty = torch.zeros((0, 3), dtype=torch.float32, device=device)
-    src = torch.cat(srcs, 0) if srcs else empty
-    ref = torch.cat(refs, 0) if refs else empty
+    src, ref = stack(srcs, empty), stack(refs, empty)
     if hypothesis_indices is not None and not torch.is_tensor(hypothesis_indices):
         hypothesis_indices = torch.as_tensor(np.asarray(hypothesis_indices, dtype=np.int32))
     if hypothesis_indices is not None:
@@ -143,7 +136,7 @@ def ransac_from_feats_pairs(src_points_list, ref_points_list, src_feats_list, re
             raise ValueError('ransac_from_feats_pairs: pair %d has a different number of points and features' % p)
     nn_src, _ds, nn_ref, _dr = _fm.nearest_feature_pairs(ref_feats_list, src_feats_list)
     keep = [i >= 0 for i in nn_ref]                          # per src row: it has a ref row at all
-    sizes = [int(i.shape[0]) for i in nn_ref]
+    sizes = lengths(nn_ref)
     if mutual_filter and P:
         mutual = []
         for p in range(P):                                   # (an empty ref cloud has nothing to gather from: no mutual correspondence)
@@ -154,12 +147,12 @@ def ransac_from_feats_pairs(src_points_list, ref_points_list, src_feats_list, re
     tables = []
     if P:
         rows = torch.nonzero(torch.cat(keep)).reshape(-1)    # one compaction for all pairs; rows ascend, so pairs stay contiguous
-        starts = np.concatenate([[0], np.cumsum(sizes)])
+        starts = exclusive_offsets(sizes)
         cuts = torch.searchsorted(rows, torch.as_tensor(starts, dtype=torch.int64, device=rows.device)).cpu().tolist()
         all_ref = torch.cat(nn_ref)
         for p in range(P):
             j = rows[cuts[p]:cuts[p + 1]]
-            tables.append(torch.stack([j - int(starts[p]), all_ref[j]], 1))
+            tables.append(torch.stack([j - starts[p], all_ref[j]], 1))
     out = ransac_pairs(src_points_list, ref_points_list, distance_threshold, ransac_n, num_iterations, seed, correspondences=tables,
                        per_hypothesis=per_hypothesis, edge_length_similarity=edge_length_similarity, check_distance=check_distance)
     out['correspondences'] = tables
@@ -173,10 +166,9 @@ def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_f
     val_iterations is accepted and has NO effect: in Open3D >= 0.13 that slot of RANSACConvergenceCriteria is a confidence, clamped to 1,
     so all num_iterations hypotheses are evaluated (item 6 of the contract).  The early stop of older Open3D versions after
     val_iterations validated hypotheses is not reproduced."""
-    dev = 'cuda'
-    up = lambda a, w: torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.float32).reshape(-1, w)).to(dev)
     src_feats, ref_feats = np.asarray(src_feats), np.asarray(ref_feats)
-    out = ransac_from_feats_pairs([up(src_points, 3)], [up(ref_points, 3)], [up(src_feats, src_feats.shape[-1])],
+    up = lambda a, w=3: upload(a, 'cuda', w, np.float32)
+    out = ransac_from_feats_pairs([up(src_points)], [up(ref_points)], [up(src_feats, src_feats.shape[-1])],
                                   [up(ref_feats, ref_feats.shape[-1])], distance_threshold, ransac_n, num_iterations, mutual_filter, seed)
     return out['transforms'][0].cpu().numpy().astype(np.float64)
 
@@ -207,8 +199,6 @@ def register_pairs(cfg, outs, method, num_corr=None, seed=0):
         r = cfg.ransac
         return ransac_pairs([c[1] for c in cut], [c[0] for c in cut], r.distance_threshold, r.num_points, r.num_iterations,
                             seed)['transforms']
-    dev = cut[0][0].device
-    lengths = [int(c[2].shape[0]) for c in cut]
-    offsets = _ops.to_device(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64).tolist(), torch.int64, dev)
+    offsets = device_offsets(lengths([c[2] for c in cut]), cut[0][0].device)
     return _ops.weighted_procrustes(torch.cat([c[1] for c in cut], 0), torch.cat([c[0] for c in cut], 0),
                                     torch.cat([c[2] for c in cut], 0), offsets, eps=1e-5)

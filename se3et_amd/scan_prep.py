@@ -47,27 +47,10 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from .pair_geometry import _device, _stack, _upload
+from .stacking import chunks, device_of, gpu_rows_each, identities, lengths, stack, upload
 
+_FAMILY = 'scan preparation'
 _STATUS = {1: 'a point (or normal) is not finite', 2: 'an axis would need 2^21 voxels or more at this voxel size'}
-
-
-def _clouds(lst, dev, what):
-    out = []
-    for i, x in enumerate(lst):
-        name = '%s: cloud %d' % (what, i)
-        if not torch.is_tensor(x):
-            raise RuntimeError('%s must be a tensor on the device (the single-cloud numpy wrappers upload)' % name)
-        if not x.is_cuda:
-            raise RuntimeError('%s must be a GPU tensor (scan preparation has no CPU implementation)' % name)
-        if (dev.index is not None and x.device != dev) or x.dtype not in (torch.float32, torch.float64) or x.dim() != 2 or x.shape[1] != 3:
-            raise RuntimeError('%s must be (n, 3) float32 or float64 on %s' % (name, dev))
-        out.append(x.contiguous())
-    return out
-
-
-def _eyes(n):
-    return torch.eye(4, dtype=torch.float64).repeat(n, 1, 1)
 
 
 @torch.no_grad()
@@ -79,19 +62,18 @@ def voxel_downsample_clouds(points_list, voxel_size, normals_list=None, device=N
         raise ValueError('voxel_downsample_clouds: voxel size %r is not a positive finite number' % (voxel_size,))
     if normals_list is not None and len(normals_list) != len(points_list):
         raise ValueError('voxel_downsample_clouds: one normals array per cloud')
-    dev = _device(device, points_list)
-    pts = _clouds(points_list, dev, 'voxel_downsample_clouds')
-    nrs = _clouds(normals_list, dev, 'voxel_downsample_clouds: normals') if normals_list is not None else None
+    dev = device_of(device, points_list)
+    pts = gpu_rows_each(points_list, dev, 'voxel_downsample_clouds: cloud', _FAMILY)
+    nrs = gpu_rows_each(normals_list, dev, 'voxel_downsample_clouds: normals: cloud', _FAMILY) if normals_list is not None else None
     out_p, out_n = [], []
-    for a in range(0, len(pts), _ops.PAIR_MAX_PAIRS):
-        b = min(len(pts), a + _ops.PAIR_MAX_PAIRS)
-        p, lengths = _stack(pts[a:b])
+    for a, b in chunks(len(pts)):
+        p, pl = stack(pts[a:b]), lengths(pts[a:b])
         nr = None
         if nrs is not None:
             if any(x.shape != y.shape for x, y in zip(pts[a:b], nrs[a:b])):
                 raise ValueError('voxel_downsample_clouds: normals must have the shape of their points')
             nr = torch.cat([x.to(p.dtype) for x in nrs[a:b]], 0)
-        means, nmeans, words = _ops.voxel_downsample_stack(p, lengths, v, nr)
+        means, nmeans, words = _ops.voxel_downsample_stack(p, pl, v, nr)
         words = words.cpu().tolist()                                   # the ONE synchronisation of the chunk: counts and status
         counts = words[:-1]
         if words[-1]:                                                  # (a refused cloud's count is minus its status bits)
@@ -109,15 +91,14 @@ def knn_clouds(support_list, k, queries_list=None, device=None):
     indices, list of (n, k) float64 squared distances)."""
     if queries_list is not None and len(queries_list) != len(support_list):
         raise ValueError('knn_clouds: one query cloud per support cloud')
-    dev = _device(device, support_list, queries_list or [])
-    ss = _clouds(support_list, dev, 'knn_clouds')
-    qs = _clouds(queries_list, dev, 'knn_clouds: queries') if queries_list is not None else ss
+    dev = device_of(device, support_list, queries_list or [])
+    ss = gpu_rows_each(support_list, dev, 'knn_clouds: cloud', _FAMILY)
+    qs = gpu_rows_each(queries_list, dev, 'knn_clouds: queries: cloud', _FAMILY) if queries_list is not None else ss
     idxs, d2s = [], []
-    for a in range(0, len(ss), _ops.PAIR_MAX_PAIRS):
-        b = min(len(ss), a + _ops.PAIR_MAX_PAIRS)
-        s, sl = _stack(ss[a:b])
-        q, ql = (s, sl) if queries_list is None else _stack(qs[a:b])
-        grid = _ops.pair_grid_build(s, sl, _eyes(b - a), 0.0)
+    for a, b in chunks(len(ss)):
+        s, sl = stack(ss[a:b]), lengths(ss[a:b])
+        q, ql = (s, sl) if queries_list is None else (stack(qs[a:b]), lengths(qs[a:b]))
+        grid = _ops.pair_grid_build(s, sl, identities(b - a), 0.0)
         idx, d2 = _ops.knn_stack(grid, q, ql, k)
         idxs += list(torch.split(idx, ql))
         d2s += list(torch.split(d2, ql))
@@ -128,8 +109,8 @@ def knn_clouds(support_list, k, queries_list=None, device=None):
 def estimate_normals_clouds(points_list, knn=33, viewpoints=None, device=None):
     """utils/open3d.py:49-54 estimate_normals for a list of clouds: (n, 3) float64 unit normals with the canonical sign, or, with
     viewpoints ((clouds, 3), or one (3,) for all), oriented towards them."""
-    dev = _device(device, points_list)
-    pts = _clouds(points_list, dev, 'estimate_normals_clouds')
+    dev = device_of(device, points_list)
+    pts = gpu_rows_each(points_list, dev, 'estimate_normals_clouds: cloud', _FAMILY)
     view = None
     if viewpoints is not None:
         view = torch.as_tensor(np.asarray(viewpoints.detach().cpu() if torch.is_tensor(viewpoints) else viewpoints, np.float64))
@@ -137,11 +118,10 @@ def estimate_normals_clouds(points_list, knn=33, viewpoints=None, device=None):
         if view.shape[0] != len(pts) or not bool(torch.isfinite(view).all()):
             raise ValueError('estimate_normals_clouds: one finite (3,) viewpoint per cloud')
     out = []
-    for a in range(0, len(pts), _ops.PAIR_MAX_PAIRS):
-        b = min(len(pts), a + _ops.PAIR_MAX_PAIRS)
-        p, lengths = _stack(pts[a:b])
-        grid = _ops.pair_grid_build(p, lengths, _eyes(b - a), 0.0)
-        out += list(torch.split(_ops.knn_normals_stack(grid, p, lengths, knn, None if view is None else view[a:b]), lengths))
+    for a, b in chunks(len(pts)):
+        p, pl = stack(pts[a:b]), lengths(pts[a:b])
+        grid = _ops.pair_grid_build(p, pl, identities(b - a), 0.0)
+        out += list(torch.split(_ops.knn_normals_stack(grid, p, pl, knn, None if view is None else view[a:b]), pl))
     return out
 
 
@@ -161,11 +141,11 @@ def regularize_normals(points, normals, positive=True):
 def voxel_downsample(points, voxel_size, normals=None, device=None):
     """geotransformer.utils.open3d.voxel_downsample: points (and normals) as float64 numpy arrays."""
     if normals is None:
-        return voxel_downsample_clouds([_upload(points, device)], voxel_size)[0].cpu().numpy()
-    p, n = voxel_downsample_clouds([_upload(points, device)], voxel_size, [_upload(normals, device)])
+        return voxel_downsample_clouds([upload(points, device)], voxel_size)[0].cpu().numpy()
+    p, n = voxel_downsample_clouds([upload(points, device)], voxel_size, [upload(normals, device)])
     return p[0].cpu().numpy(), n[0].cpu().numpy()
 
 
 def estimate_normals(points, knn=33, device=None):
     """geotransformer.utils.open3d.estimate_normals: (n, 3) float64 numpy."""
-    return estimate_normals_clouds([_upload(points, device)], knn)[0].cpu().numpy()
+    return estimate_normals_clouds([upload(points, device)], knn)[0].cpu().numpy()
