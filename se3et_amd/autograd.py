@@ -170,11 +170,12 @@ def group_norm_rows(x, weight, bias, residual, x_bias, groups, eps, leaky_slope,
 
 
 def neighbor_max_pool(x, idx):
-    """blocks.py:93-110: max over the gathered neighbour rows, the zero row included for padded entries."""
+    """blocks.py:93-110: max over the gathered neighbour rows, the zero row included for padded entries.  torch.max(dim) as in the
+    reference: on ties the gradient goes to ONE entry, the first in table order (amax would split it evenly among the tied ones)."""
     rows = _padded_rows(x, idx)
     if bool((idx < 0).any()):                      # width markers of stacked pairs are skipped, not zero rows
         rows = rows.masked_fill((idx < 0).reshape(idx.shape + (1,) * (rows.dim() - 2)), float('-inf'))
-    return rows.amax(1)
+    return rows.max(1)[0]
 
 
 def gather_rows_padded(x, idx):
@@ -277,7 +278,7 @@ def log_optimal_transport(scores, alpha, row_masks, col_masks, num_iterations, i
     al = alpha.reshape(1, 1, 1)
     z = torch.cat((torch.cat((scores, al.expand(B, R, 1)), -1), al.expand(B, 1, C + 1)), 1)
     z = z.masked_fill(prm[:, :, None] | pcm[:, None, :], -inf)
-    nvr, nvc = row_masks.float().sum(1), col_masks.float().sum(1)
+    nvr, nvc = row_masks.to(scores.dtype).sum(1), col_masks.to(scores.dtype).sum(1)
     norm = -torch.log(nvr + nvc)
     log_mu = norm[:, None].repeat(1, R + 1)
     log_mu[:, R] = torch.log(nvc) + norm

@@ -170,10 +170,15 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float* __restr
 
 // ---- backward (training step) ------------------------------------------------------------------------------------------------------------
 // Reverse-mode differentiation of the iteration above, one workgroup per patch pair, same thread mapping (a row-owner and a column-owner
-// register copy of Z).  Phase 1 repeats the forward iterations and keeps every u_t, v_t in LDS (iterations x (R1 + C1) floats); phase 2
-// walks them backwards:   v_t = log_nu - LSE_i(Z + u_t):  P2 = exp((Z_ij + u_t[i]) - (log_nu[j] - v_t[j])),  dZ -= dv[j] P2,  du[i] -= sum_j dv[j] P2
-//                         u_t = log_mu - LSE_j(Z + v_{t-1}): P1 = exp((Z_ij + v_{t-1}[j]) - (log_mu[i] - u_t[i])), dZ -= du[i] P1,  dv[j]  = -sum_i du[i] P1
-// (the softmax weights from the saved LSE, as torch.logsumexp's backward).  The row pass accumulates its dZ terms in the row-owner copy, the
+// register copy of Z).  Phase 1 repeats the forward iterations and keeps every logsumexp in LDS (iterations x (R1 + C1) floats: LU_t[i] =
+// LSE_j(Z + v_{t-1}), LV_t[j] = LSE_i(Z + u_t); the duals follow from them by the forward's own subtraction, bit for bit: u_t = log_mu - LU_t,
+// v_t = log_nu - LV_t); phase 2 walks them backwards:
+//                         v_t = log_nu - LSE_i(Z + u_t):  P2 = exp((Z_ij + u_t[i]) - LV_t[j]),  dZ -= dv[j] P2,  du[i] -= sum_j dv[j] P2
+//                         u_t = log_mu - LSE_j(Z + v_{t-1}): P1 = exp((Z_ij + v_{t-1}[j]) - LU_t[i]), dZ -= du[i] P1,  dv[j]  = -sum_i du[i] P1
+// (the softmax weights from the saved LSE, as torch.logsumexp's backward.  The saved LSE itself: recovered as log_nu - v_t it carries the
+// rounding of v_t, one factor e^delta shared by a whole column of P2 and the same in every iteration once the duals have converged --
+// over 100 iterations of scores 30 wide the gradient was 3.4e-4 off where the float32 restatement is 2.8e-5 off,
+// profiles/backward_edges_probe.txt).  The row pass accumulates its dZ terms in the row-owner copy, the
 // column pass in the column-owner copy; they meet in the output.  grad_scores (B, R, C) (masked entries 0), grad_alpha_partial (B): the
 // bin entries' sum per patch pair (the caller adds them up).
 template <int LANES, int EPL>
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
                                                                 const uint8_t* __restrict__ col_masks, const float* __restrict__ alpha_p,
                                                                 const float* __restrict__ grad_out, int R, int C, int iters, float inf,
                                                                 float* __restrict__ grad_scores, float* __restrict__ grad_alpha_partial) {
-  extern __shared__ float hist[];                        // u_t: [iters][R1], then v_t: [iters][C1]
+  extern __shared__ float hist[];                        // LU_t: [iters][R1], then LV_t: [iters][C1]
   __shared__ float u[160], v[160], log_mu[160], log_nu[160], du[160], dv[160];
   __shared__ float s_alpha[kThreads / 64];
   const int b = blockIdx.x;
@@ -241,9 +246,9 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
       for (int e = 0; e < EPL; e++) s += __expf(t[e] - m);
       s = group_sum<LANES>(s);
       if (sub == 0 && owner < R1) {
-        const float un = log_mu[owner] - (logf(s) + m);
-        u[owner] = un;
-        uh[(size_t)it * R1 + owner] = un;
+        const float lse = logf(s) + m;
+        u[owner] = log_mu[owner] - lse;
+        uh[(size_t)it * R1 + owner] = lse;
       }
     }
     __syncthreads();
@@ -261,9 +266,9 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
       for (int e = 0; e < EPL; e++) s += __expf(t[e] - m);
       s = group_sum<LANES>(s);
       if (sub == 0 && owner < C1) {
-        const float vn = log_nu[owner] - (logf(s) + m);
-        v[owner] = vn;
-        vh[(size_t)it * C1 + owner] = vn;
+        const float lse = logf(s) + m;
+        v[owner] = log_nu[owner] - lse;
+        vh[(size_t)it * C1 + owner] = lse;
       }
     }
     __syncthreads();
@@ -286,16 +291,16 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
   }
   __syncthreads();
   for (int it = iters - 1; it >= 0; it--) {
-    const float* ut = uh + (size_t)it * R1;
-    const float* vt = vh + (size_t)it * C1;
+    const float* lut = uh + (size_t)it * R1;
+    const float* lvt = vh + (size_t)it * C1;
     {  // through v_t (row-owner): needs dv, adds to du
       float acc = 0.f;
-      const float ui = owner < R1 ? ut[owner] : 0.f;
+      const float ui = owner < R1 ? log_mu[owner] - lut[owner] : 0.f;
 #pragma unroll
       for (int e = 0; e < EPL; e++) {
         const int j = sub + e * LANES;
         if (owner < R1 && j < C1) {
-          const float p = __expf((zr[e] + ui) - (log_nu[j] - vt[j]));
+          const float p = __expf((zr[e] + ui) - lvt[j]);
           const float c = dv[j] * p;
           gr[e] -= c;
           acc += c;
@@ -307,12 +312,12 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_bwd_kernel(const float* __r
     __syncthreads();
     {  // through u_t (column-owner): needs du, replaces dv
       float acc = 0.f;
-      const float vj = (it > 0 && owner < C1) ? vh[(size_t)(it - 1) * C1 + owner] : 0.f;
+      const float vj = (it > 0 && owner < C1) ? log_nu[owner] - vh[(size_t)(it - 1) * C1 + owner] : 0.f;
 #pragma unroll
       for (int e = 0; e < EPL; e++) {
         const int i = sub + e * LANES;
         if (owner < C1 && i < R1) {
-          const float p = __expf((zc[e] + vj) - (log_mu[i] - ut[i]));
+          const float p = __expf((zc[e] + vj) - lut[i]);
           const float c = du[i] * p;
           gc[e] -= c;
           acc += c;
