@@ -1040,6 +1040,27 @@ int se3_debug_icp_host(const void* src_points, int64_t n, const void* ref_points
                        int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace);
 int se3_debug_icp_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos);
 
+/* ---- keypoint selection: radius non-maximum suppression in score order (csrc/keypoint_nms.hip) -------------------------------------------------
+ * The loop of the reference's sample_keypoints_with_nms / random_sample_keypoints_with_nms (utils/pointcloud.py:191-248) in an exact parallel
+ * form, for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, one workgroup per cloud; the contract is the header comment of
+ * csrc/keypoint_nms.hip.  Cloud c owns rows [offsets_host[c], offsets_host[c + 1]) (HOST int64, num_clouds + 1 entries from 0 to n_total).
+ *   se3_keypoint_nms_stack  grid_workspace: se3_pair_grid_build over the clouds themselves with identity transforms and cell_hint = radius
+ *                           (n_total rows; the points are read from it).  order: DEVICE int64 per stacked row, cloud-local, rank -> index
+ *                           (score descending, then index ascending: the caller's ranking).  max_keep: the number of keypoints wanted per
+ *                           cloud, <= 0 for all survivors.  out_indices: DEVICE int64 sized n_total; cloud c's kept indices, cloud-local and
+ *                           in rank order, start at offsets_host[c]; out_counts[c] (DEVICE int) of them are written.  status (DEVICE int): 0,
+ *                           or bit 1 = a non-finite point, bit 2 = an order that is not a permutation of its cloud's rows (the clouds
+ *                           concerned give no rows, and out_counts[c] holds MINUS their bits); read it with the counts.  radius must be
+ *                           positive and finite; fewer than 2^31 rows per call.  A radius far above the point spacing is correct, slow.
+ *   se3_debug_keypoint_nms_host   the same tile step for one cloud on HOST memory, no GPU: every pointer a host pointer, out_indices sized
+ *                           n, *status as above (then *out_count = 0). */
+size_t se3_keypoint_nms_workspace_bytes(int64_t n_total, int num_clouds);
+int se3_keypoint_nms_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t n_total, const int64_t* order,
+                           const int64_t* offsets_host, int num_clouds, double radius, int max_keep, int64_t* out_indices, int* out_counts,
+                           int* status, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_keypoint_nms_host(const void* points, int64_t n, int elem, const int64_t* order, double radius, int max_keep,
+                                int64_t* out_indices, int64_t* out_count, int* status);
+
 #ifdef __cplusplus
 }
 #endif

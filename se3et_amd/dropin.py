@@ -15,7 +15,11 @@ What is replaced: geotransformer.modules.{ops, e2pn, e2pn.blocks_epn, kpconv, tr
 from the reference tree when it is importable: sub-modules the hot path does not contain (`geotransformer.modules.loss`,
 `...registration.metrics`, `...ops.vector_angle`, `geotransformer.utils.*`) are found through the reference's directories appended to the
 mirrored packages' `__path__`, and single names of a mirrored package that the mirror does not define (e.g. `rodrigues_rotation_matrix`)
-through `reference_attribute`.  Nothing here is on the forward's path."""
+through `reference_attribute`.  Nothing here is on the forward's path.
+
+One family of `geotransformer.utils` is exported as well: the five keypoint sampling functions of `geotransformer.utils.pointcloud`
+(KEYPOINT_NAMES, se3et_amd.keypoints) are set on that module -- the reference's own when it is importable, so that every other name of it
+stays the reference's, otherwise a module that holds these five alone."""
 import importlib
 import importlib.util
 import os
@@ -26,6 +30,8 @@ import types
 PREFIX = 'geotransformer.modules.'
 OPERATOR_PACKAGES = ('ops', 'e2pn', 'e2pn.blocks_epn', 'kpconv', 'transformer', 'geotransformer', 'sinkhorn', 'registration')
 VGTK_NAMES = ('vgtk', 'vgtk.functional', 'vgtk.so3conv')
+KEYPOINT_NAMES = ('random_sample_keypoints', 'sample_keypoints_with_scores', 'random_sample_keypoints_with_scores',
+                  'sample_keypoints_with_nms', 'random_sample_keypoints_with_nms')
 _state = {'installed': False, 'reference_modules': None}
 
 
@@ -45,7 +51,31 @@ def _reference_modules_dir():
     return _state['reference_modules'] or None
 
 
-def install_aliases(vgtk=True, ext=True):
+def _install_keypoints(root, ref):
+    """The keypoint sampling functions of se3et_amd.keypoints under geotransformer.utils.pointcloud; returns that module's name."""
+    from . import keypoints
+    name = 'geotransformer.utils.pointcloud'
+    mod = None
+    if ref:
+        try:
+            mod = importlib.import_module(name)
+        except ImportError:
+            mod = None
+    else:
+        utils = sys.modules.setdefault('geotransformer.utils', types.ModuleType('geotransformer.utils'))
+        if not hasattr(utils, '__path__'):
+            utils.__path__ = []
+        root.utils = utils
+    if mod is None:
+        mod = sys.modules.setdefault(name, types.ModuleType(name))
+        if not ref:
+            sys.modules['geotransformer.utils'].pointcloud = mod
+    for fn in KEYPOINT_NAMES:
+        setattr(mod, fn, getattr(keypoints, fn))
+    return name
+
+
+def install_aliases(vgtk=True, ext=True, keypoints=True):
     """Registers the mirrors under the reference's module names (idempotent).  Call before the experiment's `import model`.  Returns the
     list of module names that were registered."""
     done = []
@@ -82,6 +112,8 @@ def install_aliases(vgtk=True, ext=True):
         sys.modules['geotransformer.ext'] = host_ext
         done.append('geotransformer.ext')
         parents[0].ext = host_ext
+    if keypoints:
+        done.append(_install_keypoints(parents[0], ref))
     if vgtk:
         from . import vgtk as toolkit
         pkg = types.ModuleType('vgtk')

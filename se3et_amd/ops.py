@@ -2533,3 +2533,28 @@ def icp_stack(grid, src_points, src_lengths, init_transforms, max_correspondence
     if corr is not None:
         out['correspondences'] = corr
     return out
+
+
+# ---- keypoint selection: radius NMS in score order (csrc/keypoint_nms.hip) -----------------------------------------------------------------------
+_ws_keypoint_nms = Workspace(1 << 20)
+
+
+def keypoint_nms_stack(grid, order, lengths, radius, max_keep=0):
+    """HIP: greedy radius NMS of up to PAIR_MAX_PAIRS stacked clouds, one workgroup per cloud.  grid: pair_grid_build over the clouds
+    themselves with identity transforms and cell_hint = radius; order (total,) int64 on the device, cloud-local, rank -> index; max_keep:
+    keypoints wanted per cloud, <= 0 for all survivors.  Returns (out (total,) int64: cloud c's kept indices in rank order from its row
+    offset on, words (len(lengths) + 1,) int32 on the DEVICE: the counts and, last, the status word (0; bit 1: a non-finite point, bit 2:
+    an order that is no permutation; the count of a refused cloud is minus its bits) -- one copy fetches both."""
+    o = _req(order, torch.int64, 'order', 1)
+    C = len(lengths)
+    if o.device != grid.device or C != grid.num_pairs or o.shape[0] != grid.ns_total:
+        raise RuntimeError('keypoint_nms_stack: an order of %d rows for %d clouds on %s expected' % (grid.ns_total, grid.num_pairs, grid.device))
+    offsets = _pair_offsets(lengths, o.shape[0], 'keypoint_nms_stack')
+    out = torch.empty((o.shape[0],), dtype=torch.int64, device=o.device)
+    words = torch.empty((C + 1,), dtype=torch.int32, device=o.device)
+    nbytes = lib().se3_keypoint_nms_workspace_bytes(o.shape[0], C)
+    stream = _stream()
+    ws = _ws_keypoint_nms.get(o.device, stream.value, nbytes)
+    check(lib().se3_keypoint_nms_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(o), offsets, C, float(radius), int(max_keep), _dp(out),
+                                       words.data_ptr(), words[C:].data_ptr(), ws.data_ptr(), nbytes, stream), 'se3_keypoint_nms_stack')
+    return out, words
