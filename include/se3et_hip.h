@@ -502,7 +502,9 @@ int se3_rpe_self_attention_stack_bf16_fwd(const float* q, const float* k, const 
  * se3_cross_eq_stats writes partial[(a*A+e) * P + i] whose sum over i is sum_{n,m} (mean_h q_a.k_e * scale)^2
  * (*num_partials_per_pair = P = ceil(N/32)); the caller turns g = sum / (N M) into the (A, A) mixing weights `mix`
  * (a_soft: g / sum_e g; r_soft: the 24 rotation weights collapsed onto anchor pairs) and se3_cross_eq_apply computes
- * out[a] = sum_e mix[a, e] softmax_m(q_a.k_e * scale) v_e (vt: transposed key-padded values (A, C, key_stride)). */
+ * out[a] = sum_e mix[a, e] softmax_m(q_a.k_e * scale) v_e (vt: transposed key-padded values (A, C, key_stride)).
+ * se3_cross_eq_stats and se3_cross_eq_apply run the f32 kernels of se3_cross_eq_stack_fwd on one pair (a wave per key anchor for
+ * A <= 6). */
 int se3_cross_eq_stats(const float* q, const float* k, int A, int N, int M, int C, int H, float scale, float* partial,
                        int* num_partials_per_pair, void* stream);
 /* mode 0 = a_soft (weights: A*A values = mix), mode 1 = r_soft (weights: num_rotations values; trace_idx (R, A) int64) */
@@ -592,7 +594,7 @@ int se3_geo_embedding_bf16_fwd(const float* points, const int64_t* knn, int N, i
  * point_to_node (N) int64 = nearest node of every point; node_masks (M) uint8 = node owns at least one point;
  * node_knn_indices (M, limit) int64 = the `limit` nearest of the node's OWN points in ascending distance, padded with N;
  * node_knn_masks (M, limit) uint8.  Distances as pairwise_distance (modules/ops/pairwise_distance.py:4-30), ties by index.
- * limit <= 128. */
+ * limit <= 128.  se3_knn3 and se3_point_to_node_partition run the kernels of their stack forms on one cloud. */
 int se3_knn3(const float* points, int N, int64_t* knn, void* stream);
 /* se3_knn3 for num_clouds (<= 16) stacked clouds in one launch: points (sum lengths, 3), lengths HOST array; knn (sum lengths, 3)
  * holds indices LOCAL to the point's own cloud. */
@@ -619,7 +621,8 @@ int se3_pairwise_distance(const float* x, const float* y, int64_t batch, int N, 
 /* ---- E2: superpoint matching scores --------------------------------------------------------------------------------
  * Replaces the score part of SuperPointMatching.forward (geotransformer/modules/geotransformer/superpoint_matching.py:31-39):
  * scores[n, m] = exp(-clamp(2 - 2 ref[n].src[m], 0)), optionally dual-normalised (S / rowsum * S / colsum).
- * ref (N, C), src (M, C) L2-normalised; workspace: N + M floats. */
+ * ref (N, C), src (M, C) L2-normalised; workspace: N + M floats.  The kernels of the stack form on one pair with every node
+ * present; ref and src may be separate allocations. */
 int se3_superpoint_scores(const float* ref_feats, const float* src_feats, int N, int M, int C, int dual_normalization,
                           float* scores, float* workspace, void* stream);
 /* Stack mode: the score matrices of num_pairs (<= 16) registration pairs in one launch per kernel.  feats (rows, C): the

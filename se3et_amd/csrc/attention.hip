@@ -16,6 +16,8 @@
 //                      sums per workgroup (deterministic two-stage reduction).
 //   cross_eq_apply     out[a] = sum_e W[a, e] softmax_m(S[a, e]) v_e (vanilla_transformer.py:812-818; r_soft collapsed from
 //                      24 rotations to the (A, A) anchor pairs, :506-577,839-845).
+//                      Both are the *_stack_kernel of their name: one set of kernels takes all pairs of a batch from a descriptor,
+//                      and the single-pair entry points pass a descriptor of one pair.
 #include <hip/hip_ext.h>
 #include <mutex>
 #include <type_traits>
@@ -394,21 +396,17 @@ struct FlashState {
 template <int D>
 struct TileRegs {
   float4 kf[FlashState<D>::KU];
-  float4 b4[4];
   float vv[FlashState<D>::DT * 16];
 };
 
 template <int D>
-__device__ __forceinline__ void flash_load(TileRegs<D>& r, const float* __restrict__ k, const float* __restrict__ v,
-                                           const float* __restrict__ bias_row, int m0, int M, int k_rs, int v_rs) {
+__device__ __forceinline__ void flash_load(TileRegs<D>& r, const float* __restrict__ k, const float* __restrict__ v, int m0, int M,
+                                           int k_rs, int v_rs) {
   constexpr int DT = FlashState<D>::DT, KU = FlashState<D>::KU;
   const int lane = threadIdx.x & 63, half = lane >> 5, c32 = lane & 31;
   const float* kr = k + (size_t)min(m0 + c32, M - 1) * k_rs + 4 * half;
 #pragma unroll
   for (int u = 0; u < KU; u++) r.kf[u] = ld4(kr + 8 * u);
-#pragma unroll
-  for (int g = 0; g < 4; g++)
-    r.b4[g] = bias_row ? ld4(bias_row + m0 + 8 * g + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int dt = 0; dt < DT; dt++) {
     const int dd = 32 * dt + c32;
@@ -423,33 +421,23 @@ __device__ __forceinline__ void flash_load(TileRegs<D>& r, const float* __restri
   }
 }
 
-// q/k point at the (anchor, head) slice (row strides q_rs / k_rs floats: they may be column blocks of a wider projection); v points at the TRANSPOSED values of the slice, vt[dd * Mp + key]
-// (keys zero-padded to Mp, a multiple of 32).  bias (may be null) points at the (ah) slice, row stride Mp.
-// PREFETCH: the loads of tile t+step are issued before the MFMAs of tile t (two register sets); otherwise the loads of a tile
-// sit at the top of its iteration and latency is hidden by the other resident waves (fewer VGPRs, more waves per SIMD).
-template <int D, bool PREFETCH = true>
+// q/k point at the (anchor, head) slice (row strides q_rs / k_rs floats: they may be column blocks of a wider projection); v points at the TRANSPOSED values of the slice, vt[dd * v_rs + key]
+// (keys zero-padded to a multiple of 32).  All key tiles in order; the loads of a tile sit at the top of its iteration and latency is hidden
+// by the other resident waves.
+template <int D>
 __device__ __forceinline__ void flash_tiles(FlashState<D>& st, const float* __restrict__ q, const float* __restrict__ k,
-                                            const float* __restrict__ v, const float* __restrict__ bias, int n0, int N, int M,
-                                            int q_rs, int k_rs, int v_rs, int Mp, float scale, int tile_begin, int tile_step) {
+                                            const float* __restrict__ v, int n0, int N, int M, int q_rs, int k_rs, int v_rs, float scale) {
   constexpr int DT = FlashState<D>::DT, KU = FlashState<D>::KU;
   const int lane = threadIdx.x & 63, half = lane >> 5, c32 = lane & 31;
   const int nq = min(n0 + c32, N - 1);
   float4 qf[KU];
 #pragma unroll
   for (int u = 0; u < KU; u++) qf[u] = ld4(q + (size_t)nq * q_rs + 8 * u + 4 * half);
-  const float* bias_row = bias ? bias + (size_t)nq * Mp : nullptr;
   const int tiles = (M + 31) >> 5;
-  TileRegs<D> cur, nxt;
-  int tile = tile_begin;
-  if (PREFETCH && tile < tiles) flash_load<D>(cur, k, v, bias_row, tile << 5, M, k_rs, v_rs);
-  for (; tile < tiles; tile += tile_step) {
+  for (int tile = 0; tile < tiles; tile++) {
     const int m0 = tile << 5;
-    const bool more = PREFETCH && tile + tile_step < tiles;
-    if (PREFETCH) {
-      if (more) flash_load<D>(nxt, k, v, bias_row, (tile + tile_step) << 5, M, k_rs, v_rs);
-    } else {
-      flash_load<D>(cur, k, v, bias_row, m0, M, k_rs, v_rs);
-    }
+    TileRegs<D> cur;
+    flash_load<D>(cur, k, v, m0, M, k_rs, v_rs);
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; r++) s[r] = 0.f;
@@ -465,7 +453,7 @@ __device__ __forceinline__ void flash_tiles(FlashState<D>& st, const float* __re
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const int key = m0 + 8 * g + 4 * half + j;
-        float val = (s[4 * g + j] + f4get(cur.b4[g], j)) * scale;
+        float val = s[4 * g + j] * scale;
         val = key < M ? val : -INFINITY;
         s[4 * g + j] = val;
         mx = fmaxf(mx, val);
@@ -490,7 +478,6 @@ __device__ __forceinline__ void flash_tiles(FlashState<D>& st, const float* __re
 #pragma unroll
       for (int r = 0; r < 16; r++) st.o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.vv[dt * 16 + r], s[r], st.o[dt], 0, 0, 0);
     }
-    if (PREFETCH && more) cur = nxt;
   }
 }
 
@@ -695,7 +682,7 @@ struct AttnArgs {
 // One workgroup per (cloud, anchor, head, 32-query tile); its 4 waves split the key tiles and merge through LDS.
 // XCD-aware flat grid: workgroup i runs on XCD i % 8 (round-robin dispatch), so group g = (cloud, anchor, head) is pinned
 // to XCD g % 8 and the K / V^T of a group (re-read by all of its query tiles) stay in ONE L2.
-// Measured in rounds 2 and 3 and removed with the tuning variants: K / V^T loads at the tile top or fully double buffered through flash_tiles
+// Measured in rounds 2 and 3 and removed with the tuning variants: K / V^T loads at the tile top or fully double buffered
 // (slower than Q in LDS + requests into just-consumed registers), 6 waves (2 workgroups per CU), 2 and 1 waves per workgroup (no / smaller merge
 // through LDS: 160-171 us against 160 per equivariant call at the bench shape), and the f16 hi / lo split of every operand inside the loop
 // (171-183 us: the ~400 split instructions per tile cost what the matrix pipe saves -- attention_x6_kernel below splits K / V^T once per call).
@@ -734,103 +721,10 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnArgs p) {
   flash_merge_store<D, NW>(st, sm, sl, so, p.out + a * p.o_sa + (size_t)cl.q_start * p.C + h * D, n0, cl.N, p.C);
 }
 
-// Never called: a second caller of flash_tiles<32, true>, which cross_eq_apply_kernel<32> needs in this file.  The helpers have internal linkage,
-// so with cross_eq_apply_kernel as the only caller the compiler propagates its constant arguments (no logits, tile 0, step 1) into flash_tiles
-// BEFORE inlining, and the kernel comes out with 168 instead of 152 registers: 2 instead of 3 waves per SIMD.  (Until the tuning variants were
-// removed, attention_kernel's double-buffered form was that caller.  D = 8 / 16 / 64 move by 3 / 6 / 17 registers without crossing an
-// occupancy step and are left alone: profiles/variants_removed_kernels.txt.)
-__device__ __attribute__((used, noinline)) void flash_tiles_second_caller(FlashState<32>& st, const AttnArgs& p, int n0, int tile_begin, int tile_step) {
-  flash_tiles<32, true>(st, p.q, p.k, p.v, p.bias, n0, p.S.c[0].N, p.S.c[0].M, p.q_rs, p.k_rs, p.v_rs, p.S.c[0].Mp, p.scale, tile_begin, tile_step);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // equivariant cross attention
 // ---------------------------------------------------------------------------------------------------------------------
-// grid (ceil(N/32), A*A): partial[blockIdx] = sum over the tile's (n, m) of (mean_h S[a,e,h,n,m])^2
-template <int D>
-__global__ __launch_bounds__(256) void cross_eq_stats_kernel(const float* __restrict__ q, const float* __restrict__ k, int A,
-                                                             int N, int M, int C, int H, float scale,
-                                                             float* __restrict__ partial) {
-  constexpr int KU = D / 8;
-  __shared__ float red[4];
-  const int n0 = blockIdx.x * 32, ae = blockIdx.y, a = ae / A, e = ae - a * A;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, c32 = lane & 31;
-  const int nq = min(n0 + c32, N - 1);
-  const int tiles = (M + 31) >> 5;
-  float total = 0.f;
-  for (int tile = wave; tile < tiles; tile += 4) {
-    const int m0 = tile << 5;
-    const int kr = min(m0 + c32, M - 1);
-    f32x16 mean;
-#pragma unroll
-    for (int r = 0; r < 16; r++) mean[r] = 0.f;
-    for (int h = 0; h < H; h++) {
-      const float* qh = q + ((size_t)a * N + nq) * C + h * D;
-      const float* kh = k + ((size_t)e * M + kr) * C + h * D;
-#pragma unroll
-      for (int u = 0; u < KU; u++) {
-        const float4 kf = ld4(kh + 8 * u + 4 * half), qf = ld4(qh + 8 * u + 4 * half);
-#pragma unroll
-        for (int i = 0; i < 4; i++) mean = __builtin_amdgcn_mfma_f32_32x32x2f32(f4get(kf, i), f4get(qf, i), mean, 0, 0, 0);
-      }
-    }
-    const float f = scale / (float)H;
-    const bool qok = n0 + c32 < N;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const int key = m0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float val = mean[r] * f;
-      total += (qok && key < M) ? val * val : 0.f;
-    }
-  }
-  total = se3_wave_sum(total);
-  if (lane == 0) red[wave] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// grid (ceil(N/32), H, A): out[a, n, h] = sum_e mix[a, e] softmax_m(q_a.k_e * scale) v_e ; waves split the key anchors e
-template <int D>
-__global__ __launch_bounds__(256) void cross_eq_apply_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                             const float* __restrict__ vt, const float* __restrict__ mix,
-                                                             int A, int N, int M, int C, int Mp, float scale, float* __restrict__ out) {
-  constexpr int DT = FlashState<D>::DT;
-  __shared__ float so[4 * DT * 16 * 64];
-  const int n0 = blockIdx.x * 32, h = blockIdx.y, a = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  FlashState<D> tot;
-  flash_init(tot);
-  for (int e = wave; e < A; e += 4) {
-    FlashState<D> st;
-    flash_init(st);
-    flash_tiles<D>(st, q + (size_t)a * N * C + h * D, k + (size_t)e * M * C + h * D, vt + ((size_t)e * C + h * D) * Mp, nullptr,
-                   n0, N, M, C, C, Mp, Mp, scale, 0, 1);
-    const float w = mix[a * A + e] / st.l;
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) tot.o[dt][r] += st.o[dt][r] * w;
-  }
-#pragma unroll
-  for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) so[((wave * DT + dt) * 16 + r) * 64 + lane] = tot.o[dt][r];
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        float acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) acc += so[((w * DT + dt) * 16 + r) * 64 + lane];
-        tot.o[dt][r] = acc;
-      }
-    flash_store<D>(tot, out + (size_t)a * N * C + h * D, n0, N, C, 1.f, false);
-  }
-}
-
-// ---- stack mode of the equivariant cross attention: all pairs of a batch per launch ------------------------------------------
+// All pairs of a batch per launch; the single-pair entry points (se3_cross_eq_stats, se3_cross_eq_apply) pass a descriptor of one pair.
 struct CrossEqArgs {
   const float *q, *k, *vt;     // q (A, Rq, C), k (A, Rk, C) packed rows; vt (A, C, v_rs) transposed values addressed by key column
   Stack S;                     // per pair: q_start, k_start, N, M (Mp = ceil32(M))
@@ -894,8 +788,8 @@ __global__ __launch_bounds__(256) void cross_eq_stats_stack_kernel(CrossEqArgs p
   if (threadIdx.x == 0) *dst = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// grid (QT, H, A * pairs), 64 NW threads: wave e handles key anchor e (NW = A = 6: no imbalance, half the serial chain of the
-// 4-wave version); out[a, n, h] = sum_e mix[pair, a, e] softmax_m(q_a.k_e * scale) v_e
+// grid (QT, H, A * pairs), 64 NW threads: wave e handles key anchor e (NW = A = 6: no imbalance, half the serial chain of four
+// waves with up to two anchors each, which is what NW = 4 does for A > 6); out[a, n, h] = sum_e mix[pair, a, e] softmax_m(q_a.k_e * scale) v_e
 template <int D, int NW>
 __global__ __launch_bounds__(64 * NW) void cross_eq_apply_stack_kernel(CrossEqArgs p, const float* __restrict__ mix,
                                                                        float* __restrict__ out) {
@@ -912,9 +806,8 @@ __global__ __launch_bounds__(64 * NW) void cross_eq_apply_stack_kernel(CrossEqAr
   for (int e = wave; e < A; e += NW) {
     FlashState<D> st;
     flash_init(st);
-    flash_tiles<D, false>(st, p.q + a * p.q_sa + (size_t)cl.q_start * C + h * D, p.k + e * p.k_sa + (size_t)cl.k_start * C + h * D,
-                          p.vt + e * p.v_sa + (size_t)h * D * p.v_rs + cl.k_start, nullptr, n0, cl.N, cl.M, C, C, p.v_rs, cl.Mp,
-                          p.scale, 0, 1);
+    flash_tiles<D>(st, p.q + a * p.q_sa + (size_t)cl.q_start * C + h * D, p.k + e * p.k_sa + (size_t)cl.k_start * C + h * D,
+                   p.vt + e * p.v_sa + (size_t)h * D * p.v_rs + cl.k_start, n0, cl.N, cl.M, C, C, p.v_rs, p.scale);
     const float w = mix[((size_t)pair * A + a) * A + e] / st.l;
 #pragma unroll
     for (int dt = 0; dt < DT; dt++)
@@ -1437,6 +1330,30 @@ int dispatch_head_dim(int D, F&& f, const char* what) {
       se3_set_error("%s: head dim %d not in {8, 16, 32, 64}", what, D);
       return SE3_ERR_UNSUPPORTED;
   }
+}
+
+// the descriptor of the cross_eq kernels short of its pairs, which cross_eq_add_pair appends
+CrossEqArgs cross_eq_args(const float* q, const float* k, const float* vt, int A, int C, int H, int64_t q_sa, int64_t k_sa, int v_rs,
+                          int64_t v_sa, float scale) {
+  CrossEqArgs p{};
+  p.q = q; p.k = k; p.vt = vt;
+  p.A = A; p.C = C; p.H = H; p.QT = 1;
+  p.q_sa = q_sa; p.k_sa = k_sa; p.v_sa = v_sa; p.v_rs = v_rs;
+  p.scale = scale;
+  return p;
+}
+void cross_eq_add_pair(CrossEqArgs& p, int64_t q_start, int64_t k_start, int N, int M) {
+  p.S.c[p.S.n++] = StackCloud{nullptr, nullptr, (int)q_start, (int)k_start, N, M, ((M + 31) / 32) * 32, 0, 0};
+  p.QT = (N + 31) / 32 > p.QT ? (N + 31) / 32 : p.QT;
+}
+// the f32 apply kernel: a wave per key anchor up to six anchors, four waves taking turns above
+template <int D>
+void cross_eq_apply_launch(const CrossEqArgs& p, const float* mix, float* out, hipStream_t st) {
+  const dim3 grid((unsigned)p.QT, (unsigned)p.H, (unsigned)(p.A * p.S.n));
+  if (p.A <= 6)
+    cross_eq_apply_stack_kernel<D, 6><<<grid, 384, 0, st>>>(p, mix, out);
+  else
+    cross_eq_apply_stack_kernel<D, 4><<<grid, 256, 0, st>>>(p, mix, out);
 }
 
 }  // namespace
@@ -2015,11 +1932,12 @@ extern "C" int se3_cross_eq_stats(const float* q, const float* k, int A, int N, 
                                   float* partial, int* num_partials_per_pair, void* stream) {
   SE3_REQUIRE(q && k && partial && num_partials_per_pair, SE3_ERR_INVALID_ARG, "cross_eq_stats: null pointer");
   SE3_REQUIRE(A >= 1 && N >= 1 && M >= 1 && H >= 1 && C % H == 0, SE3_ERR_INVALID_ARG, "cross_eq_stats: bad sizes");
-  dim3 grid((unsigned)((N + 31) / 32), (unsigned)(A * A));
-  *num_partials_per_pair = (int)grid.x;
+  CrossEqArgs p = cross_eq_args(q, k, nullptr, A, C, H, (int64_t)N * C, (int64_t)M * C, 0, 0, scale);
+  cross_eq_add_pair(p, 0, 0, N, M);
+  *num_partials_per_pair = p.QT;
   hipStream_t st = (hipStream_t)stream;
   int rc = dispatch_head_dim(C / H, [&](auto d) {
-    cross_eq_stats_kernel<decltype(d)::value><<<grid, 256, 0, st>>>(q, k, A, N, M, C, H, scale, partial);
+    cross_eq_stats_stack_kernel<decltype(d)::value><<<dim3((unsigned)p.QT, (unsigned)(A * A), 1), 256, 0, st>>>(p, partial);
   }, "cross_eq_stats");
   if (rc != SE3_OK) return rc;
   SE3_CHECK_LAUNCH("cross_eq_stats");
@@ -2250,20 +2168,15 @@ extern "C" int se3_cross_eq_stack_fwd(const float* q, const float* k, const floa
   SE3_REQUIRE(A >= 1 && A * A <= 64 && H >= 1 && C % H == 0 && v_row_stride % 4 == 0, SE3_ERR_INVALID_ARG, "cross_eq_stack: bad sizes");
   SE3_REQUIRE(mode == 0 || (mode == 1 && trace_idx && num_rotations >= 1 && num_rotations <= 64), SE3_ERR_UNSUPPORTED,
               "cross_eq_stack: mode %d rotations %d", mode, num_rotations);
-  CrossEqArgs p{};
-  p.q = q; p.k = k; p.vt = vt;
-  p.S.n = num_pairs;
-  int qt = 1;
+  CrossEqArgs p = cross_eq_args(q, k, vt, A, C, H, q_anchor_stride, k_anchor_stride, v_row_stride, v_anchor_stride,
+                                1.0f / sqrtf((float)(C / H)));
   for (int c = 0; c < num_pairs; c++) {
     const int N = (int)q_lengths[c], M = (int)k_lengths[c], Mp = ((M + 31) / 32) * 32;
     SE3_REQUIRE(N >= 1 && M >= 1 && q_starts[c] >= 0 && k_starts[c] >= 0 && k_starts[c] % 4 == 0 && k_starts[c] + Mp <= v_row_stride,
                 SE3_ERR_INVALID_ARG, "cross_eq_stack: pair %d descriptor", c);
-    p.S.c[c] = StackCloud{nullptr, nullptr, (int)q_starts[c], (int)k_starts[c], N, M, Mp, 0, 0};
-    qt = (N + 31) / 32 > qt ? (N + 31) / 32 : qt;
+    cross_eq_add_pair(p, q_starts[c], k_starts[c], N, M);
   }
-  p.A = A; p.C = C; p.H = H; p.QT = qt;
-  p.q_sa = q_anchor_stride; p.k_sa = k_anchor_stride; p.v_sa = v_anchor_stride; p.v_rs = v_row_stride;
-  p.scale = 1.0f / sqrtf((float)(C / H));
+  const int qt = p.QT;
   hipStream_t st = (hipStream_t)stream;
   int rc = dispatch_head_dim(C / H, [&](auto d) {
     constexpr int D = decltype(d)::value;
@@ -2273,10 +2186,7 @@ extern "C" int se3_cross_eq_stack_fwd(const float* q, const float* k, const floa
       cross_eq_stats_stack_kernel<D><<<dim3((unsigned)qt, (unsigned)(A * A), (unsigned)num_pairs), 256, 0, st>>>(p, partial_workspace);
     cross_eq_mix_kernel<<<(unsigned)num_pairs, 64, 0, st>>>(partial_workspace, sums_given ? 1 : qt, 0.f, A, num_rotations, trace_idx, mode, mix,
                                                          weights, nullptr, p.S, 1);
-    if (A <= 6)
-      cross_eq_apply_stack_kernel<D, 6><<<dim3((unsigned)qt, (unsigned)H, (unsigned)(A * num_pairs)), 384, 0, st>>>(p, mix, out);
-    else
-      cross_eq_apply_stack_kernel<D, 4><<<dim3((unsigned)qt, (unsigned)H, (unsigned)(A * num_pairs)), 256, 0, st>>>(p, mix, out);
+    cross_eq_apply_launch<D>(p, mix, out, st);
   }, "cross_eq_stack");
   if (rc != SE3_OK) return rc;
   SE3_CHECK_LAUNCH("cross_eq_stack");
@@ -2315,21 +2225,16 @@ extern "C" int se3_cross_eq_stack_x6_fwd(const float* q, const float* k, const f
               "cross_eq_stack_x6: workspace too small");
   SE3_REQUIRE(mode == 0 || (mode == 1 && trace_idx && num_rotations >= 1 && num_rotations <= 64), SE3_ERR_UNSUPPORTED,
               "cross_eq_stack_x6: mode %d rotations %d", mode, num_rotations);
-  CrossEqArgs p{};
-  p.q = q; p.k = k; p.vt = vt;
-  p.S.n = num_pairs;
-  int qt = 1;
+  CrossEqArgs p = cross_eq_args(q, k, vt, A, C, H, q_anchor_stride, k_anchor_stride, v_row_stride, v_anchor_stride,
+                                1.0f / sqrtf((float)(C / H)));
   for (int c = 0; c < num_pairs; c++) {
     const int N = (int)q_lengths[c], M = (int)k_lengths[c], Mp = ((M + 31) / 32) * 32;
     SE3_REQUIRE(N >= 1 && M >= 1 && q_starts[c] >= 0 && k_starts[c] >= 0 && q_starts[c] + N <= q_rows && k_starts[c] + M <= k_rows &&
                     k_starts[c] + Mp <= v_row_stride,
                 SE3_ERR_INVALID_ARG, "cross_eq_stack_x6: pair %d descriptor", c);
-    p.S.c[c] = StackCloud{nullptr, nullptr, (int)q_starts[c], (int)k_starts[c], N, M, Mp, 0, 0};
-    qt = (N + 31) / 32 > qt ? (N + 31) / 32 : qt;
+    cross_eq_add_pair(p, q_starts[c], k_starts[c], N, M);
   }
-  p.A = A; p.C = C; p.H = H; p.QT = qt;
-  p.q_sa = q_anchor_stride; p.k_sa = k_anchor_stride; p.v_sa = v_anchor_stride; p.v_rs = v_row_stride;
-  p.scale = 1.0f / sqrtf((float)(C / H));
+  const int qt = p.QT;
   p.G = out_groups; p.out_rs = out_groups * C; p.out_sa = out_anchor_stride;
   hipStream_t st = (hipStream_t)stream;
   const size_t nq = (size_t)A * q_rows * C / 8, nk = (size_t)A * k_rows * C / 8, nv = (size_t)A * C * v_row_stride / 8;     // uint4 per piece
@@ -2371,11 +2276,10 @@ extern "C" int se3_cross_eq_apply(const float* q, const float* k, const float* v
   SE3_REQUIRE(key_stride >= ((M + 31) / 32) * 32 && key_stride % 4 == 0, SE3_ERR_INVALID_ARG, "cross_eq_apply: key stride");
   SE3_REQUIRE(q && k && vt && mix && out, SE3_ERR_INVALID_ARG, "cross_eq_apply: null pointer");
   SE3_REQUIRE(A >= 1 && N >= 1 && M >= 1 && H >= 1 && C % H == 0, SE3_ERR_INVALID_ARG, "cross_eq_apply: bad sizes");
-  dim3 grid((unsigned)((N + 31) / 32), (unsigned)H, (unsigned)A);
+  CrossEqArgs p = cross_eq_args(q, k, vt, A, C, H, (int64_t)N * C, (int64_t)M * C, key_stride, (int64_t)C * key_stride, scale);
+  cross_eq_add_pair(p, 0, 0, N, M);
   hipStream_t st = (hipStream_t)stream;
-  int rc = dispatch_head_dim(C / H, [&](auto d) {
-    cross_eq_apply_kernel<decltype(d)::value><<<grid, 256, 0, st>>>(q, k, vt, mix, A, N, M, C, key_stride, scale, out);
-  }, "cross_eq_apply");
+  int rc = dispatch_head_dim(C / H, [&](auto d) { cross_eq_apply_launch<decltype(d)::value>(p, mix, out, st); }, "cross_eq_apply");
   if (rc != SE3_OK) return rc;
   SE3_CHECK_LAUNCH("cross_eq_apply");
   return SE3_OK;

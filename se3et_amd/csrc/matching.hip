@@ -1,12 +1,14 @@
 // E2: superpoint matching scores (SuperPointMatching.forward, geotransformer/modules/geotransformer/superpoint_matching.py:31-39):
 //   S[n, m] = exp(-clamp(2 - 2 f_ref[n].f_src[m], 0))  on L2-normalised features, then the dual normalisation
 //   S / rowsum(S) * S / colsum(S).  Three small launches (scores + row sums, column sums, normalise); deterministic.
+// One set of kernels: they take the superpoint pairs of a batch from a descriptor, and the single-pair entry point passes one pair
+// with every node present.
 #include "common.h"
 
 namespace {
 
-// one K4-step of a feature dot product and the score of a finished one, with the roundings spelled out: the per-pair kernel and the stack
-// kernel (eight rows per workgroup) must agree bit for bit, whatever the compiler would contract in either loop
+// one K4-step of a feature dot product and the score of a finished one, with the roundings spelled out: every dot product has one
+// order of operations, whatever the compiler would contract in the eight-row loop
 __device__ __forceinline__ float sp_dot_step(float acc, const float* f, const float4& v) {
   const float a = __fmaf_rn(f[0], v.x, __fmul_rn(f[1], v.y));
   const float b = __fmaf_rn(f[2], v.z, __fmul_rn(f[3], v.w));
@@ -14,59 +16,10 @@ __device__ __forceinline__ float sp_dot_step(float acc, const float* f, const fl
 }
 __device__ __forceinline__ float sp_score(float dot) { return __expf(-fmaxf(__fmaf_rn(-2.f, dot, 2.f), 0.f)); }
 
-// one workgroup per reference row n; thread t handles columns t, t + 256, ...
-__global__ __launch_bounds__(256) void sp_scores_kernel(const float* __restrict__ ref, const float* __restrict__ src, int N,
-                                                        int M, int C, float* __restrict__ S, float* __restrict__ rowsum) {
-  extern __shared__ float rf[];          // C floats of the reference row + 4 partials
-  __shared__ float part[4];
-  const int n = blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += 256) rf[c] = ref[(size_t)n * C + c];
-  __syncthreads();
-  float rs = 0.f;
-  for (int m = threadIdx.x; m < M; m += 256) {
-    const float4* sp = reinterpret_cast<const float4*>(src + (size_t)m * C);
-    float acc = 0.f;
-    for (int c4 = 0; c4 < C / 4; c4++) {
-      const float4 v = sp[c4];
-      acc = sp_dot_step(acc, rf + 4 * c4, v);
-    }
-    const float s = sp_score(acc);
-    S[(size_t)n * M + m] = s;
-    rs += s;
-  }
-  rs = se3_wave_sum(rs);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = rs;
-  __syncthreads();
-  if (threadIdx.x == 0) rowsum[n] = (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// column sums: 64 columns x 4 row lanes per workgroup (the single-thread-per-column version was one serial pass over N rows on
-// ceil(M / 256) workgroups: 89 us at N = M = 382); fixed summation order -> deterministic
-__global__ __launch_bounds__(256) void sp_colsum_kernel(const float* __restrict__ S, int N, int M, float* __restrict__ colsum) {
-  __shared__ float part[4][64];
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int m = blockIdx.x * 64 + cl;
-  float cs = 0.f;
-  if (m < M)
-    for (int n = rl; n < N; n += 4) cs += S[(size_t)n * M + m];
-  part[rl][cl] = cs;
-  __syncthreads();
-  if (rl == 0 && m < M) colsum[m] = (part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl]);
-}
-
-__global__ void sp_normalize_kernel(float* __restrict__ S, const float* __restrict__ rowsum,
-                                    const float* __restrict__ colsum, int N, int M) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)N * M) return;
-  const int n = (int)(i / M), m = (int)(i - (int64_t)n * M);
-  const float s = S[i];
-  S[i] = (s / rowsum[n]) * (s / colsum[m]);
-}
-
-// ---- stack mode: the superpoint pairs of several registration pairs in one launch per kernel -----------------------------
+// ---- the superpoint pairs of a launch (one, or those of several registration pairs in stack mode) ----------------------------
 constexpr int kMaxMatchPairs = 16;
 struct MatchPairs {
-  int ref_row[kMaxMatchPairs], src_row[kMaxMatchPairs];       // first row of the pair's ref / src superpoints in `feats`
+  int ref_row[kMaxMatchPairs], src_row[kMaxMatchPairs];       // first row of the pair's superpoints in `ref` / `src` (stack mode: one array)
   int N[kMaxMatchPairs], M[kMaxMatchPairs];
   int ref_mask[kMaxMatchPairs], src_mask[kMaxMatchPairs];     // first entry of the pair's node masks in `node_masks`
   int row0[kMaxMatchPairs + 1];                               // prefix sums of N (flat ref-row index -> pair)
@@ -75,13 +28,14 @@ struct MatchPairs {
 };
 
 // one workgroup per (pair, 8 reference rows); raw scores into the pair's rows of the padded (B, stride) output, row sums over the
-// valid columns into the workspace.  Nodes with mask 0 (no fine point) are absent, as the reference drops them beforehand.
+// valid columns into the workspace.  Nodes with mask 0 (no fine point) are absent, as the reference drops them beforehand; without
+// masks (null) every node is present.
 // (Late round 5: eight rows per workgroup instead of one -- a thread's source row (1 KB, one lane per row: 64 cache lines per load
 // instruction) is fetched once for eight dot products instead of once per dot product; every dot product keeps its order of operations.)
-template <int kSpRows>              // 8; 1 for feature widths whose eight rows would not fit 64 KB of LDS
-__global__ __launch_bounds__(256) void sp_scores_stack_kernel(const float* __restrict__ feats, const unsigned char* __restrict__ masks,
-                                                              MatchPairs T, int C, int64_t stride, float* __restrict__ S,
-                                                              float* __restrict__ rowsum) {
+template <int kSpRows>              // 8; 1 for feature widths whose eight rows would not fit 64 KB of LDS, and for one pair alone
+__global__ __launch_bounds__(256) void sp_scores_stack_kernel(const float* __restrict__ ref, const float* __restrict__ src,
+                                                              const unsigned char* __restrict__ masks, MatchPairs T, int C,
+                                                              int64_t stride, float* __restrict__ S, float* __restrict__ rowsum) {
   extern __shared__ float rf[];                                 // kSpRows x C
   __shared__ float part[kSpRows][4];
   const int p = blockIdx.y, N = T.N[p], M = T.M[p];
@@ -90,19 +44,19 @@ __global__ __launch_bounds__(256) void sp_scores_stack_kernel(const float* __res
   const int nr = min(kSpRows, N - n0);
   for (int e = threadIdx.x; e < kSpRows * C; e += 256) {
     const int r = e / C, c = e - r * C;
-    rf[e] = r < nr ? feats[(size_t)(T.ref_row[p] + n0 + r) * C + c] : 0.f;
+    rf[e] = r < nr ? ref[(size_t)(T.ref_row[p] + n0 + r) * C + c] : 0.f;
   }
   __syncthreads();
-  const unsigned char* cm = masks + T.src_mask[p];
-  const unsigned char* rmk = masks + T.ref_mask[p] + n0;
+  const unsigned char* cm = masks ? masks + T.src_mask[p] : nullptr;
+  const unsigned char* rmk = masks ? masks + T.ref_mask[p] + n0 : nullptr;
   bool present[kSpRows];
 #pragma unroll
-  for (int r = 0; r < kSpRows; r++) present[r] = r < nr && rmk[r < nr ? r : 0] != 0;
+  for (int r = 0; r < kSpRows; r++) present[r] = r < nr && (!rmk || rmk[r < nr ? r : 0] != 0);
   float rs[kSpRows];
 #pragma unroll
   for (int r = 0; r < kSpRows; r++) rs[r] = 0.f;
   for (int m = threadIdx.x; m < M; m += 256) {
-    const float4* sp = reinterpret_cast<const float4*>(feats + (size_t)(T.src_row[p] + m) * C);
+    const float4* sp = reinterpret_cast<const float4*>(src + (size_t)(T.src_row[p] + m) * C);
     float acc[kSpRows];
 #pragma unroll
     for (int r = 0; r < kSpRows; r++) acc[r] = 0.f;
@@ -113,7 +67,7 @@ __global__ __launch_bounds__(256) void sp_scores_stack_kernel(const float* __res
         acc[r] = sp_dot_step(acc[r], rf + r * C + 4 * c4, v);
       }
     }
-    const bool cv = cm[m] != 0;
+    const bool cv = !cm || cm[m] != 0;
 #pragma unroll
     for (int r = 0; r < kSpRows; r++) {
       if (!present[r]) continue;
@@ -128,7 +82,7 @@ __global__ __launch_bounds__(256) void sp_scores_stack_kernel(const float* __res
     if ((threadIdx.x & 63) == 0) part[r][threadIdx.x >> 6] = w;
   }
   __syncthreads();
-  if ((int)threadIdx.x < nr && rmk[threadIdx.x])
+  if ((int)threadIdx.x < nr && (!rmk || rmk[threadIdx.x]))
     rowsum[T.row0[p] + n0 + threadIdx.x] = (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]);
 }
 
@@ -140,10 +94,14 @@ __global__ __launch_bounds__(256) void sp_colsum_stack_kernel(const float* __res
   const int m = blockIdx.x * 64 + cl;
   if (blockIdx.x * 64 >= M) return;
   const float* Sp = S + (size_t)p * stride;
-  const unsigned char* rm = masks + T.ref_mask[p];
+  const unsigned char* rm = masks ? masks + T.ref_mask[p] : nullptr;
   float cs = 0.f;
-  if (m < M)
-    for (int n = rl; n < N; n += 4) cs += rm[n] ? Sp[(size_t)n * M + m] : 0.f;
+  if (m < M) {          // (two loops: with the test on rm inside, the loads of the unmasked form wait for it -- 28 against 25 us at N = 381, M = 307)
+    if (rm)
+      for (int n = rl; n < N; n += 4) cs += rm[n] ? Sp[(size_t)n * M + m] : 0.f;
+    else
+      for (int n = rl; n < N; n += 4) cs += Sp[(size_t)n * M + m];
+  }
   part[rl][cl] = cs;
   __syncthreads();
   if (rl == 0 && m < M) colsum[T.col0[p] + m] = (part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl]);
@@ -163,7 +121,7 @@ __global__ void sp_normalize_stack_kernel(float* __restrict__ S, const unsigned 
     return;
   }
   const int n = (int)(i / M), m = (int)(i - (int64_t)n * M);
-  if (!masks[T.ref_mask[p] + n] || !masks[T.src_mask[p] + m]) {
+  if (masks && (!masks[T.ref_mask[p] + n] || !masks[T.src_mask[p] + m])) {
     Sp[i] = -1.f;
     return;
   }
@@ -171,6 +129,39 @@ __global__ void sp_normalize_stack_kernel(float* __restrict__ S, const unsigned 
     const float s = Sp[i];
     Sp[i] = (s / rowsum[T.row0[p] + n]) * (s / colsum[T.col0[p] + m]);
   }
+}
+
+// T.row0 / T.col0 from T.N / T.M, then the launches.  masks may be null (every node present).  Without dual normalisation, masks and
+// padding (stride = N * M of the one pair) the normalise kernel has nothing to write and is not launched.  eight_rows: reference rows per
+// workgroup of the scores kernel, eight or one (the results are the same bit for bit).
+int sp_launch(const float* ref, const float* src, const unsigned char* masks, MatchPairs& T, int C, int dual, int64_t stride, float* scores,
+              float* workspace, bool eight_rows, hipStream_t st, const char* what) {
+  int rows = 0, cols = 0, max_n = 0, max_m = 0;
+  for (int p = 0; p < T.n; p++) {
+    T.row0[p] = rows;
+    T.col0[p] = cols;
+    rows += T.N[p];
+    cols += T.M[p];
+    max_n = T.N[p] > max_n ? T.N[p] : max_n;
+    max_m = T.M[p] > max_m ? T.M[p] : max_m;
+  }
+  T.row0[T.n] = rows;
+  T.col0[T.n] = cols;
+  float* rowsum = workspace;               // rows floats
+  float* colsum = workspace + rows;        // cols floats
+  if (eight_rows && C <= 1024)
+    sp_scores_stack_kernel<8><<<dim3((unsigned)((max_n + 7) / 8), (unsigned)T.n), 256, (size_t)8 * C * sizeof(float), st>>>(
+        ref, src, masks, T, C, stride, scores, rowsum);
+  else
+    sp_scores_stack_kernel<1><<<dim3((unsigned)max_n, (unsigned)T.n), 256, (size_t)C * sizeof(float), st>>>(ref, src, masks, T, C, stride,
+                                                                                                           scores, rowsum);
+  if (dual)
+    sp_colsum_stack_kernel<<<dim3((unsigned)((max_m + 63) / 64), (unsigned)T.n), 256, 0, st>>>(scores, masks, T, stride, colsum);
+  if (dual || masks || T.n > 1 || stride != (int64_t)T.N[0] * T.M[0])
+    sp_normalize_stack_kernel<<<dim3((unsigned)((stride + 255) / 256), (unsigned)T.n), 256, 0, st>>>(scores, masks, T, stride, rowsum, colsum,
+                                                                                                   dual ? 1 : 0);
+  SE3_CHECK_LAUNCH(what);
+  return SE3_OK;
 }
 
 }  // namespace
@@ -186,8 +177,6 @@ extern "C" int se3_superpoint_scores_stack(const float* feats, const uint8_t* no
               "superpoint_scores_stack: %d pairs (1..%d), C %d", num_pairs, kMaxMatchPairs, C);
   MatchPairs T{};
   T.n = num_pairs;
-  int64_t rows = 0, cols = 0;
-  int max_m = 0;
   for (int p = 0; p < num_pairs; p++) {
     SE3_REQUIRE(ref_lengths[p] >= 1 && src_lengths[p] >= 1 && ref_lengths[p] * src_lengths[p] <= score_stride &&
                     ref_rows[p] >= 0 && src_rows[p] >= 0 && ref_mask_offsets[p] >= 0 && src_mask_offsets[p] >= 0,
@@ -198,50 +187,24 @@ extern "C" int se3_superpoint_scores_stack(const float* feats, const uint8_t* no
     T.M[p] = (int)src_lengths[p];
     T.ref_mask[p] = (int)ref_mask_offsets[p];
     T.src_mask[p] = (int)src_mask_offsets[p];
-    T.row0[p] = (int)rows;
-    T.col0[p] = (int)cols;
-    rows += ref_lengths[p];
-    cols += src_lengths[p];
-    max_m = T.M[p] > max_m ? T.M[p] : max_m;
   }
-  T.row0[num_pairs] = (int)rows;
-  T.col0[num_pairs] = (int)cols;
   SE3_REQUIRE(score_stride < (1ll << 31), SE3_ERR_UNSUPPORTED, "superpoint_scores_stack: %lld scores per pair", (long long)score_stride);
-  hipStream_t st = (hipStream_t)stream;
-  float* rowsum = workspace;               // rows floats
-  float* colsum = workspace + rows;        // cols floats
-  int max_n = 0;
-  for (int p = 0; p < num_pairs; p++) max_n = T.N[p] > max_n ? T.N[p] : max_n;
-  if (C <= 1024)
-    sp_scores_stack_kernel<8><<<dim3((unsigned)((max_n + 7) / 8), (unsigned)num_pairs), 256, (size_t)8 * C * sizeof(float), st>>>(
-        feats, node_masks, T, C, score_stride, scores, rowsum);
-  else
-    sp_scores_stack_kernel<1><<<dim3((unsigned)max_n, (unsigned)num_pairs), 256, (size_t)C * sizeof(float), st>>>(feats, node_masks, T, C,
-                                                                                                                score_stride, scores, rowsum);
-  if (dual_normalization)
-    sp_colsum_stack_kernel<<<dim3((unsigned)((max_m + 63) / 64), (unsigned)num_pairs), 256, 0, st>>>(scores, node_masks, T,
-                                                                                                  score_stride, colsum);
-  sp_normalize_stack_kernel<<<dim3((unsigned)((score_stride + 255) / 256), (unsigned)num_pairs), 256, 0, st>>>(
-      scores, node_masks, T, score_stride, rowsum, colsum, dual_normalization ? 1 : 0);
-  SE3_CHECK_LAUNCH("superpoint_scores_stack");
-  return SE3_OK;
+  return sp_launch(feats, feats, node_masks, T, C, dual_normalization, score_stride, scores, workspace, true, (hipStream_t)stream,
+                   "superpoint_scores_stack");
 }
 
 extern "C" int se3_superpoint_scores(const float* ref_feats, const float* src_feats, int N, int M, int C,
                                      int dual_normalization, float* scores, float* workspace, void* stream) {
   SE3_REQUIRE(ref_feats && src_feats && scores && workspace, SE3_ERR_INVALID_ARG, "superpoint_scores: null pointer");
   SE3_REQUIRE(N >= 1 && M >= 1 && C >= 4 && C % 4 == 0 && C <= 4096, SE3_ERR_UNSUPPORTED, "superpoint_scores: N %d M %d C %d", N, M, C);
-  hipStream_t st = (hipStream_t)stream;
-  float* rowsum = workspace;
-  float* colsum = workspace + N;
-  sp_scores_kernel<<<N, 256, C * sizeof(float), st>>>(ref_feats, src_feats, N, M, C, scores, rowsum);
-  if (dual_normalization) {
-    sp_colsum_kernel<<<(M + 63) / 64, 256, 0, st>>>(scores, N, M, colsum);
-    const int64_t total = (int64_t)N * M;
-    sp_normalize_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(scores, rowsum, colsum, N, M);
-  }
-  SE3_CHECK_LAUNCH("superpoint_scores");
-  return SE3_OK;
+  MatchPairs T{};          // one pair from row 0 of both arrays
+  T.n = 1;
+  T.N[0] = N;
+  T.M[0] = M;
+  // one pair alone: a workgroup per row (381 at the superpoint level of a 5k-point pair) fills the chip, 48 workgroups of eight rows do not
+  // (56 against 80 us at N = 381, M = 307, C = 256: profiles/single_entry_points_parent_vs_pr.txt)
+  return sp_launch(ref_feats, src_feats, nullptr, T, C, dual_normalization, (int64_t)N * M, scores, workspace, false, (hipStream_t)stream,
+                   "superpoint_scores");
 }
 
 

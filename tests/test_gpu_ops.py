@@ -397,16 +397,11 @@ def test_cross_attention_matches_oracle(A, N, M, C, H):
     assert_close(got, want, 1e-4, 'cross attention')
 
 
-@pytest.mark.parametrize('N,M,C,mode', [(59, 53, 32, 'a_soft'), (59, 53, 32, 'r_soft'), (382, 304, 256, 'a_soft'),
-                                        (304, 382, 256, 'r_soft'), (100, 37, 128, 'r_soft')])
-def test_cross_attention_eq_matches_oracle(N, M, C, mode):
-    from oracle import se3et_oracle as O
-    from se3et_amd import functional as SF
-    from se3et_amd import tables
-    g = torch.Generator().manual_seed(7)
-    H = 4
-    trace = torch.from_numpy(tables.trace_indices()[0])
-    q, k, v = torch.randn(6, N, C, generator=g), torch.randn(6, M, C, generator=g), torch.randn(6, M, C, generator=g)
+def _cross_eq_restatement(q, k, v, H, mode, trace):
+    """The equivariant cross attention restated in float64 torch (vanilla_transformer.py:380-389,425-426,812-818): q (A, N, C), k and v
+    (A, M, C) -> (hidden (A, N, C), weights: g / sum_e g (A, A) for 'a_soft', the rotation weights (R,) for 'r_soft')."""
+    q, k, v = q.double().cpu(), k.double().cpu(), v.double().cpu()
+    A, C = q.shape[0], q.shape[2]
     hs = lambda t: t.reshape(*t.shape[:-1], H, -1).transpose(-2, -3)
     qh, kh, vh = hs(q), hs(k), hs(v)
     s = torch.einsum('ahnc,ehmc->aehnm', qh, kh) / (C // H) ** 0.5
@@ -415,21 +410,83 @@ def test_cross_attention_eq_matches_oracle(N, M, C, mode):
     if mode == 'a_soft':
         w = gg / gg.sum(1, keepdim=True)
         hidden = torch.einsum('aehnm,ehmc->ahnc', p * w[:, :, None, None, None], vh)
-        want_w = w
     else:
-        ar = torch.arange(6)
+        trace = trace.cpu()
+        ar = torch.arange(A)
         w = gg[ar[None, :], trace].mean(1)
         w = w / w.sum()
         hidden = torch.zeros_like(qh)
-        for r in range(24):
+        for r in range(trace.shape[0]):
             hidden = hidden + w[r] * torch.einsum('ahnm,ahmc->ahnc', p[ar, trace[r]], vh[trace[r]])
-        want_w = w
-    want = hidden.transpose(-2, -3).reshape(6, N, C)
+    return hidden.transpose(-2, -3).reshape(A, q.shape[1], C), w
+
+
+def _key_padded_transposed(v):
+    """(A, M, C) values -> (A, C, Mp), the keys zero-padded to the key stride: the operand layout of the cross_eq kernels."""
+    M = v.shape[1]
+    return torch.nn.functional.pad(v, (0, 0, 0, (M + 31) // 32 * 32 - M)).transpose(1, 2).contiguous()
+
+
+@pytest.mark.parametrize('N,M,C,mode', [(59, 53, 32, 'a_soft'), (59, 53, 32, 'r_soft'), (382, 304, 256, 'a_soft'),
+                                        (304, 382, 256, 'r_soft'), (100, 37, 128, 'r_soft')])
+def test_cross_attention_eq_matches_oracle(N, M, C, mode):
+    from se3et_amd import functional as SF
+    from se3et_amd import tables
+    g = torch.Generator().manual_seed(7)
+    H = 4
+    trace = torch.from_numpy(tables.trace_indices()[0])
+    q, k, v = torch.randn(6, N, C, generator=g), torch.randn(6, M, C, generator=g), torch.randn(6, M, C, generator=g)
+    want, want_w = _cross_eq_restatement(q, k, v, H, mode, trace)
     eye, zero = torch.eye(C).cuda(), torch.zeros(C).cuda()
     got, got_w, got_mix = SF.cross_attention_eq(q.cuda(), k.cuda(), SF.project_values_transposed(v.cuda(), eye, zero), H, mode,
                                        trace.cuda())
     assert_close(got_w.cpu(), want_w, 1e-4, 'global weights')
     assert_close(got.cpu(), want, 1e-4, 'eq cross attention')
+
+
+@pytest.mark.parametrize('D', [8, 16, 32, 64])
+@pytest.mark.parametrize('A,mode', [(6, 'a_soft'), (6, 'r_soft'), (4, 'a_soft'), (8, 'a_soft')])
+def test_cross_attention_eq_single_pair_edges_match_the_float64_restatement(D, A, mode):
+    """The single-pair entry points (se3_cross_eq_stats / _mix / _apply: one-pair descriptors of the stack kernels) at every head dimension
+    behind dispatch_head_dim and at the tile edges -- one query and one key, a second query tile of one row under one key tile, exact
+    tiles, a third key tile of one key.  A = 4: waves 4 and 5 of the six-wave apply kernel have no key anchor and must contribute
+    zeros; A = 8: the four-wave kernel, two key anchors per wave."""
+    from se3et_amd import ops, tables
+    H, C = 4, 4 * D
+    trace = torch.from_numpy(tables.trace_indices()[0]) if A == 6 else torch.zeros(1, A, dtype=torch.int64)     # (a_soft never reads it)
+    g = torch.Generator().manual_seed(100 * D + A)
+    for N, M in ((1, 1), (33, 31), (32, 32), (5, 65)):
+        q, k, v = torch.randn(A, N, C, generator=g), torch.randn(A, M, C, generator=g), torch.randn(A, M, C, generator=g)
+        want, want_w = _cross_eq_restatement(q, k, v, H, mode, trace)
+        got, got_w, got_mix = ops.cross_attention_eq(q.cuda(), k.cuda(), _key_padded_transposed(v.cuda()), H, mode, trace.cuda())
+        assert_close(got_w.cpu(), want_w, 1e-4, 'N %d M %d: global weights' % (N, M))
+        assert_close(got.cpu(), want, 1e-4, 'N %d M %d: eq cross attention' % (N, M))
+
+
+def test_cross_attention_eq_stack_f32_matches_the_float64_restatement():
+    """The f32 kernels behind se3_cross_eq_stack_fwd on two pairs of unequal sizes -- (33, 31) and (1, 65): the second pair has fewer
+    query tiles than the grid and one more key tile -- against the restatement, pair by pair."""
+    from se3et_amd import ops, tables
+    A, C, H = 6, 64, 4
+    lengths, q_starts, k_starts = ((33, 31), (1, 65)), (0, 64), (0, 32)
+    trace = torch.from_numpy(tables.trace_indices()[0])
+    g = torch.Generator().manual_seed(11)
+    q, k, v = torch.zeros(A, 96, C), torch.zeros(A, 128, C), torch.zeros(A, 128, C)
+    for (n, m), s0, t0 in zip(lengths, q_starts, k_starts):
+        q[:, s0:s0 + n], k[:, t0:t0 + m], v[:, t0:t0 + m] = (torch.randn(A, r, C, generator=g) for r in (n, m, m))
+    vt = v.transpose(1, 2).contiguous().cuda()
+    for mode in ('a_soft', 'r_soft'):
+        out = torch.zeros(A, 96, C, device='cuda')
+        flag, ops.CROSS_EQ_BF16X6 = ops.CROSS_EQ_BF16X6, False
+        try:
+            mix, w = ops.cross_attention_eq_stack(q.cuda(), k.cuda(), vt, list(q_starts), [n for n, _ in lengths], list(k_starts),
+                                                  [m for _, m in lengths], H, mode, trace.cuda(), out)
+        finally:
+            ops.CROSS_EQ_BF16X6 = flag
+        for p, ((n, m), s0, t0) in enumerate(zip(lengths, q_starts, k_starts)):
+            want, want_w = _cross_eq_restatement(q[:, s0:s0 + n], k[:, t0:t0 + m], v[:, t0:t0 + m], H, mode, trace)
+            assert_close(w[p].cpu().reshape(want_w.shape), want_w, 1e-4, '%s pair %d: global weights' % (mode, p))
+            assert_close(out[:, s0:s0 + n].cpu(), want, 1e-4, '%s pair %d: eq cross attention' % (mode, p))
 
 
 @pytest.mark.parametrize('N,C,eq', [(59, 32, True), (382, 256, True), (304, 256, False), (100, 128, True), (4, 64, True), (5, 256, False),
@@ -817,8 +874,8 @@ def test_knn3_matches_oracle(N):
 
 @pytest.mark.parametrize('lengths,mode', [(((70, 61), (45, 90)), 'a_soft'), (((382, 304),), 'r_soft'), (((33, 40), (64, 64), (17, 100)), 'a_soft')])
 def test_cross_attention_eq_stack_bf16x6_matches_the_single_pair_kernels(lengths, mode):
-    """se3_cross_eq_stack_x6_fwd (bf16 matrix cores, six piece products) against the f32 single-pair kernels (se3_cross_eq_stats / _apply)
-    pair by pair at 2e-5, and against its own f32 stack form (SE3_CROSS_EQ=f32)."""
+    """se3_cross_eq_stack_x6_fwd (bf16 matrix cores, six piece products) against the f32 kernels, one pair at a time (se3_cross_eq_stats /
+    _apply), at 2e-5, and against its own f32 stack form (SE3_CROSS_EQ=f32)."""
     from se3et_amd import functional as SF
     from se3et_amd import ops, tables
     g = torch.Generator().manual_seed(len(lengths) * 7 + lengths[0][0])

@@ -207,18 +207,24 @@ def _unit_features(rows, C, seed):
     return torch.nn.functional.normalize(torch.randn(rows, C, generator=g) + base[torch.randint(0, 7, (rows,), generator=g)], dim=1)
 
 
-@pytest.mark.parametrize('N,M', [(1, 1), (1, 65), (65, 1), (64, 257)])
+@pytest.mark.parametrize('N,M', [(1, 1), (1, 65), (65, 1), (64, 257), (9, 40)])
 def test_superpoint_scores_smallest_shapes_equal_the_float64_restatement(N, M):
-    """One row, one column, and M > 256 (a thread strides to a second column); the stack form with every node present gives the same."""
+    """One row, one column, M > 256 (a thread strides to a second column) and N = 9 (a second workgroup of eight rows holding one row),
+    each at C = 32, at the smallest C, at C > 1024 (one row per workgroup) and without the dual normalisation (raw scores: the single
+    form launches no normalise kernel).  The single form takes ref and src features from two allocations; the stack form, with every
+    node present, takes them from one array and gives the same bit for bit."""
     from se3et_amd import ops
-    C = 32
-    f = _unit_features(N + M, C, 90 + N + M)
-    want = T.superpoint_scores(f[:N].numpy(), f[N:].numpy())
-    got = ops.superpoint_scores(f[:N].cuda().contiguous(), f[N:].cuda().contiguous(), True).cpu()
-    assert_close(got, want, 1e-4, 'superpoint scores (%d, %d)' % (N, M))
-    S = ops.superpoint_scores_stack(f.cuda(), torch.ones(N + M, dtype=torch.bool).cuda(), [0], [N], [N], [M], [0], [N], True).cpu()
-    assert S.shape == (1, N * M)
-    assert_close(S.view(N, M), want, 1e-4, 'stack form (%d, %d)' % (N, M))
+    for C, dual in ((32, True), (4, True), (1028, True), (32, False)):
+        f = _unit_features(N + M, C, 90 + N + M)
+        want = T.superpoint_scores(f[:N].numpy(), f[N:].numpy(), dual=dual)
+        ref, src = f[:N].clone().cuda(), f[N:].clone().cuda()
+        assert ref.untyped_storage().data_ptr() != src.untyped_storage().data_ptr()
+        got = ops.superpoint_scores(ref, src, dual).cpu()
+        assert_close(got, want, 1e-4, 'superpoint scores (%d, %d), C %d, dual %s' % (N, M, C, dual))
+        S = ops.superpoint_scores_stack(f.cuda(), torch.ones(N + M, dtype=torch.bool).cuda(), [0], [N], [N], [M], [0], [N], dual).cpu()
+        assert S.shape == (1, N * M)
+        assert_close(S.view(N, M), want, 1e-4, 'stack form (%d, %d), C %d, dual %s' % (N, M, C, dual))
+        assert torch.equal(S.view(N, M), got), 'single and stack form differ (%d, %d), C %d, dual %s' % (N, M, C, dual)
 
 
 def test_superpoint_scores_stack_with_masked_rows_and_blocks():
