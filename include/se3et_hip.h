@@ -1064,6 +1064,35 @@ int se3_keypoint_nms_stack(const void* grid_workspace, size_t grid_workspace_byt
 int se3_debug_keypoint_nms_host(const void* points, int64_t n, int elem, const int64_t* order, double radius, int max_keep,
                                 int64_t* out_indices, int64_t* out_count, int* status);
 
+/* ---- FPFH descriptors of stacked clouds (csrc/fpfh.hip, csrc/fpfh_core.h) ----------------------------------------------------------------------
+ * Open3D's compute_fpfh_feature (33 bins from point-pair angles over a point's neighbourhood) for up to SE3_PAIR_MAX_PAIRS stacked clouds per
+ * call, all float64; the contract is the header comment of csrc/fpfh.hip.  Points and normals are (rows, 3) on the device, float32 (elem 0) or
+ * float64 (elem 1), promoted on load; cloud c owns rows [offsets_host[c], offsets_host[c + 1]) (HOST int64, num_clouds + 1 entries from 0).
+ * The neighbour list is the caller's, from the searches above: for the row slice [row_begin, row_begin + row_count) of the stacked rows,
+ * row_offsets (row_count + 1) int64 on the DEVICE, from 0 to total, and pairs (total, 2) int64 on the DEVICE as se3_pair_ball_fill_stack
+ * leaves them: slice row r owns pairs[row_offsets[r] .. row_offsets[r + 1]), column 1 the neighbour's cloud-local index, ascending within a
+ * row; an entry equal to the row's own index is skipped.  A slice bounds the list's memory; the output arrays are those of the whole call.
+ *   se3_fpfh_check_stack    status (num_clouds + 1) DEVICE int: zeroed, then bit 1 of word c for a non-finite point or normal of cloud c, and
+ *                           of the last word for any.  (A list entry outside its cloud, or row offsets outside the list, are skipped by
+ *                           both passes: nothing is read through them.)
+ *   se3_spfh_stack          out_spfh (n_total, 33) float64: the slice's rows, bin count x (100 / m); theta at 0-10, f1 at 11-21, f2 at 22-32.
+ *   se3_fpfh_stack          out_fpfh (n_total, 33) float64: the slice's rows from spfh (n_total, 33), which must hold every row of the clouds
+ *                           the slice touches.
+ *   se3_debug_fpfh_host     the same text for one cloud on HOST memory, no GPU, in the same summation order: every pointer a host pointer,
+ *                           the list over all n rows; *status: bit 1 as above (nothing is computed), bit 2 for a list entry or row offsets that were skipped.
+ *   se3_debug_fpfh_sectors_host   the twenty constants of the sector rule: out[2 (k - 1)] = cos, out[2 (k - 1) + 1] = sin of
+ *                           -pi + 2 pi k / 11, k = 1 .. 10. */
+int se3_fpfh_check_stack(const void* points, int elem, const void* normals, int normals_elem, const int64_t* offsets_host, int num_clouds,
+                         int* status, void* stream);
+int se3_spfh_stack(const void* points, int elem, const void* normals, int normals_elem, const int64_t* offsets_host, int num_clouds,
+                   int64_t row_begin, int64_t row_count, const int64_t* row_offsets, const int64_t* pairs, int64_t total, double* out_spfh,
+                   void* stream);
+int se3_fpfh_stack(const void* points, int elem, const double* spfh, const int64_t* offsets_host, int num_clouds, int64_t row_begin,
+                   int64_t row_count, const int64_t* row_offsets, const int64_t* pairs, int64_t total, double* out_fpfh, void* stream);
+int se3_debug_fpfh_host(const void* points, const void* normals, int64_t n, int elem, int normals_elem, const int64_t* row_offsets,
+                        const int64_t* pairs, int64_t total, double* out_spfh, double* out_fpfh, int* status);
+int se3_debug_fpfh_sectors_host(double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,234 @@
+"""FPFH descriptors on the device: Open3D's compute_fpfh_feature (33 bins from the point-pair angles over a point's neighbourhood), the
+weights-free descriptor that the reference's make_open3d_registration_feature / registration_with_ransac_from_feats (utils/open3d.py) are
+fed with, as batched HIP kernels (csrc/fpfh.hip, csrc/fpfh_core.h) on the searches of csrc/pair_grid.h.
+
+  compute_fpfh_clouds(points_list, normals_list, radius=None, max_nn=None, dtype=torch.float64)   list of (n_c, 33) tensors on the device
+  spfh_clouds(points_list, normals_list, radius=None, max_nn=None)                                the first pass alone, float64
+  compute_fpfh_feature(points, normals, radius=None, max_nn=None)                                 one cloud, numpy in, (n, 33) numpy out
+  global_registration_pairs(src_list, ref_list, voxel_size, ...)                                  downsample, normals, FPFH, RANSAC, ICP
+
+The batched calls take GPU tensors only (there is no CPU path): points and normals (n, 3) float32 or float64, promoted on load; any number
+of clouds per call, chunked at the library's SE3_PAIR_MAX_PAIRS clouds and, within a chunk, at PAIR_BUDGET neighbour-list entries (16
+bytes each) per launch sequence.  One host synchronisation per chunk (the list's size and the status words in one copy); a chunk above the
+budget adds one.  dtype=torch.float32 rounds the finished float64 row once: the form feature_matching takes.
+
+Search modes, as Open3D's three KDTreeSearchParams:
+  radius only       every point with d^2 < r^2 (strict, as the project's other ball queries), r^2 = r r in float64; no cap on the count
+  max_nn = K only   the K nearest INCLUDING the row itself, K in [1, SE3_KNN_MAX = 64]; membership and ties at the K-th place are
+                    knn_clouds' rule: (d^2, index) ascending, the lower index wins
+  both (hybrid)     the K nearest, then of those the ones with d^2 < r^2
+Neither given is a ValueError.  Open3D's tutorial value max_nn = 100 is above the library's limit and is refused.
+
+Contract (csrc/fpfh.hip carries the same text).  The structure is Open3D's (Feature.cpp: ComputePairFeatures, ComputeSPFHFeature,
+ComputeFPFHFeature); the arithmetic is the project's own, chosen so that host and device agree bit for bit: float64, contraction off, no
+libm call other than the square root and division.
+  Neighbours.  The neighbours of row i are the members of its search result other than row i itself, chosen by index; m is their number.
+    A duplicate point at d = 0 is a neighbour.
+  Pair feature of (p1, n1) and (p2, n2), normals as given (not normalised).  Dot products are (a b + c d) + e f.
+    1. dp = p2 - p1, d = sqrt((dx dx + dy dy) + dz dz).          2. d == 0: degenerate.
+    3. a1 = n1 . dp / d, a2 = n2 . dp / d.
+    4. |a1| < |a2| (strict; Open3D writes acos|a1| > acos|a2|): swap the normals, negate dp, f2 = -a2.  Otherwise f2 = a1.
+    5. v = dp x n1; |v| == 0: degenerate.                         6. v /= |v|; w = n1 x v; f1 = v . n2; y = (w . n2) + 0.0; x = n1 . n2.
+    A degenerate pair has f1 = f2 = 0 and x = y = 0.
+  Bins.  f1 and f2: clamp(floor(11 (f + 1) 0.5), 0, 10).  theta = atan2(y, x) is binned without computing it: with beta_k = -pi +
+    2 pi k / 11 and (c_k, s_k) = (cos, sin) beta_k for k = 1..10 as float64 literals, the bin is 5 if x == 0 and y == 0; the number of k
+    in 1..5 with c_k y - s_k x >= 0 if y < 0; otherwise 5 plus the number of k in 6..10 with c_k y - s_k x >= 0.  This is
+    clamp(floor(11 (theta + pi) / 2 pi), 0, 10) away from the edges; theta = pi gives bin 10; a degenerate pair gives bins 5, 5, 5 and is
+    counted, as in Open3D.
+  SPFH row.  bin count x (100.0 / m): integer counts and one product, so the order of the neighbours does not matter.  theta at 0-10, f1
+    at 11-21, f2 at 22-32.  m == 0 gives a zero row.
+  FPFH row.  A_j = sum_k spfh(j, k) / d2_k, a sequential sum over the neighbours k with d2_k != 0 in ascending neighbour index;
+    S_g = the sequential sum of the group's eleven A_j in ascending j; F_j = spfh(j, i) + (S_g != 0 ? A_j (100 / S_g) : A_j).  A row with
+    a neighbour at d > 0 therefore sums to 600.
+  Refusals.  A non-finite point or normal raises ValueError naming the cloud (a device flag, read in the chunk's one synchronisation).  A
+    zero normal is not refused: its pairs are degenerate.  n = 0 gives an empty output.
+  Determinism.  No float atomics: a cloud's rows are bit-identical alone, anywhere in a batch, and from run to run.
+
+Where this departs from Open3D: the strict radius test and the tie rule of the searches; the swap test on |a| instead of acos|a|; the
+sector rule in place of atan2 and a floor; the fixed summation order.  None of them moves a value beyond rounding, or a count except for a
+pair within rounding of a bin edge."""
+import numpy as np
+import torch
+
+from . import ops as _ops
+from .stacking import chunks, device_of, exclusive_offsets, gpu_rows_each, identities, lengths, stack, to_device, upload
+
+_FAMILY = 'FPFH'
+DIM = _ops.FPFH_DIM
+PAIR_BUDGET = 1 << 23          # neighbour-list entries per launch sequence: 16 bytes each, 128 MiB
+
+
+def _search_mode(radius, max_nn, what):
+    """(r or None, K or None) of a call, or ValueError."""
+    if radius is None and max_nn is None:
+        raise ValueError('%s: give radius, max_nn or both (a radius, k-nearest or hybrid search)' % what)
+    r = K = None
+    if radius is not None:
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError('%s: radius %r is not a positive finite number' % (what, radius))
+    if max_nn is not None:
+        if int(max_nn) != max_nn or int(max_nn) < 1:
+            raise ValueError('%s: max_nn %r is not an integer >= 1' % (what, max_nn))
+        K = int(max_nn)
+        if K > _ops.KNN_MAX:
+            raise ValueError("%s: max_nn %d is above the library's limit SE3_KNN_MAX = %d (Open3D's tutorial value 100 among them): give "
+                             'max_nn <= %d, or the radius alone, which has no cap' % (what, K, _ops.KNN_MAX, _ops.KNN_MAX))
+    return r, K
+
+
+def _partial(offsets, s, e):
+    """The rows of [s, e) that each cloud owns."""
+    return [max(0, min(e, offsets[c + 1]) - max(s, offsets[c])) for c in range(len(offsets) - 1)]
+
+
+def _refuse(what, a, words):
+    if words[-1]:
+        raise ValueError('%s: ' % what + '; '.join('cloud %d: %s' % (a + c, ', '.join(t for bit, t in _ops.FPFH_STATUS.items() if w & bit))
+                                                   for c, w in enumerate(words[:-1]) if w))
+
+
+def _radius_lists(p, pl, r, words, what, a):
+    """The chunk's neighbour lists from the ball query: a function that yields (row_begin, row_offsets, pairs) per slice of at most
+    PAIR_BUDGET entries (half of it plus one row's, where a chunk is cut), and whether there is more than one slice."""
+    n, offsets = p.shape[0], exclusive_offsets(pl)
+    grid = _ops.pair_grid_build(p, pl, identities(len(pl)), r)
+    ro = _ops.pair_ball_count_stack(grid, p, pl, r)
+    host = torch.cat([ro[-1:], words.to(torch.int64)]).cpu().tolist()           # the ONE synchronisation of the chunk: the total, the status
+    _refuse(what, a, host[1:])
+    total = host[0]
+    if total <= PAIR_BUDGET:
+        cuts, at = [0, n], [0, total]
+    else:
+        half = max(1, PAIR_BUDGET // 2)
+        targets = torch.arange(half, total, half, dtype=torch.int64, device=p.device)
+        rows = (torch.searchsorted(ro, targets, right=True) - 1).clamp(1, n)
+        rows = torch.unique(torch.cat([rows.new_zeros(1), rows, rows.new_full((1,), n)]))
+        both = torch.stack([rows, ro[rows]]).cpu().tolist()                      # (a chunk above the budget: its cuts, one more copy)
+        cuts, at = both
+
+    def slices():
+        for k in range(len(cuts) - 1):
+            s, e = cuts[k], cuts[k + 1]
+            ro_s = ro if (s, e) == (0, n) else ro[s:e + 1] - at[k]
+            yield s, ro_s, _ops.pair_ball_fill_stack(grid, p[s:e], _partial(offsets, s, e), r, ro_s, at[k + 1] - at[k])
+    return slices, len(cuts) > 2
+
+
+def _knn_lists(p, pl, r, K):
+    """The same from the k nearest: every row owns K entries; the columns a small cloud leaves empty, or the radius masks, hold the row's
+    own index, which the kernels skip as they skip the row itself."""
+    n, offsets, dev = p.shape[0], exclusive_offsets(pl), p.device
+    grid = _ops.pair_grid_build(p, pl, identities(len(pl)), 0.0)
+    per = max(1, PAIR_BUDGET // K)
+    cloud = torch.repeat_interleave(torch.arange(len(pl), device=dev), to_device(pl, torch.int64, dev), output_size=n)
+    local = torch.arange(n, dtype=torch.int64, device=dev) - to_device(offsets[:-1], torch.int64, dev)[cloud]
+
+    def slices():
+        for s in range(0, n, per):
+            e = min(n, s + per)
+            idx, d2 = _ops.knn_stack(grid, p[s:e], _partial(offsets, s, e), K)
+            keep = idx >= 0
+            if r is not None:
+                keep &= d2 < r * r
+            own = local[s:e, None].expand(e - s, K)
+            j = torch.where(keep, idx, own).sort(dim=1).values
+            ro = torch.arange(0, (e - s + 1) * K, K, dtype=torch.int64, device=dev)
+            yield s, ro, torch.stack([own, j], 2).reshape(-1, 2)
+    return slices, n > per
+
+
+@torch.no_grad()
+def _descriptor_clouds(points_list, normals_list, radius, max_nn, device, what, second_pass):
+    r, K = _search_mode(radius, max_nn, what)
+    if len(points_list) != len(normals_list):
+        raise ValueError('%s: one normals tensor per cloud: %d for %d clouds' % (what, len(normals_list), len(points_list)))
+    dev = device_of(device, points_list, normals_list)
+    pts = gpu_rows_each(points_list, dev, what + ': cloud', _FAMILY)
+    nrs = gpu_rows_each(normals_list, dev, what + ': normals: cloud', _FAMILY)
+    for c, (p, nr) in enumerate(zip(pts, nrs)):
+        if nr.shape != p.shape or nr.device != p.device:
+            raise ValueError('%s: cloud %d: normals %s on %s for points %s on %s' % (what, c, tuple(nr.shape), nr.device, tuple(p.shape), p.device))
+    out = []
+    for a, b in chunks(len(pts)):
+        p, nr, pl = stack(pts[a:b]), stack(nrs[a:b]), lengths(pts[a:b])
+        words = _ops.fpfh_check_stack(p, nr, pl)
+        if K is None:
+            slices, several = _radius_lists(p, pl, r, words, what, a)
+        else:
+            _refuse(what, a, words.cpu().tolist())                               # the ONE synchronisation of the chunk: the status
+            slices, several = _knn_lists(p, pl, r, K)
+        spfh = torch.empty((p.shape[0], DIM), dtype=torch.float64, device=p.device)
+        res = torch.empty_like(spfh) if second_pass else spfh
+        for s, ro, pairs in slices():
+            _ops.spfh_stack(p, nr, pl, ro, pairs, spfh, s)
+            if second_pass and not several:
+                _ops.fpfh_stack(p, spfh, pl, ro, pairs, res, s)
+        if second_pass and several:                                              # (every SPFH row first: the lists are searched again)
+            for s, ro, pairs in slices():
+                _ops.fpfh_stack(p, spfh, pl, ro, pairs, res, s)
+        out += list(torch.split(res, pl))
+    return out
+
+
+def compute_fpfh_clouds(points_list, normals_list, radius=None, max_nn=None, dtype=torch.float64, device=None):
+    """FPFH of a list of clouds: points and normals (n, 3) float32 or float64 GPU tensors.  radius, max_nn or both choose the search (see
+    the module text).  Returns the list of (n_c, 33) tensors on the device, float64, or float32 (the float64 row rounded once)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError('compute_fpfh_clouds: dtype must be torch.float32 or torch.float64, got %r' % (dtype,))
+    out = _descriptor_clouds(points_list, normals_list, radius, max_nn, device, 'compute_fpfh_clouds', True)
+    return out if dtype == torch.float64 else [f.to(torch.float32) for f in out]
+
+
+def spfh_clouds(points_list, normals_list, radius=None, max_nn=None, device=None):
+    """The first pass alone (tests and diagnostics): the list of (n_c, 33) float64 SPFH rows, bin count x (100 / m)."""
+    return _descriptor_clouds(points_list, normals_list, radius, max_nn, device, 'spfh_clouds', False)
+
+
+def compute_fpfh_feature(points, normals, radius=None, max_nn=None, device=None):
+    """One cloud, numpy in and out: (n, 33) float64, rows are points -- the layout utils/open3d.py's make_open3d_registration_feature takes
+    (Open3D's own Feature.data is the transpose)."""
+    _search_mode(radius, max_nn, 'compute_fpfh_feature')
+    return compute_fpfh_clouds([upload(points, device)], [upload(normals, device)], radius, max_nn)[0].cpu().numpy()
+
+
+@torch.no_grad()
+def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpfh_radius=None, fpfh_max_nn=None, distance_threshold=None,
+                              ransac_n=3, num_iterations=50000, mutual_filter=True, edge_length_similarity=0.9, check_distance=True,
+                              icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None):
+    """The classical global registration of P pairs, a composition of the batched tools (no kernel of its own): voxel_downsample_clouds at
+    voxel_size, estimate_normals_clouds (normal_knn), compute_fpfh_clouds (float32), ransac_from_feats_pairs, and with icp_distance
+    icp_pairs from the RANSAC result on the downsampled clouds.  src_list / ref_list: (n, 3) float32 or float64 GPU tensors.
+    Defaults, as multiples of voxel_size: fpfh_radius None = 5 voxel_size when fpfh_max_nn is None too (a radius search; give fpfh_max_nn
+    alone for the k nearest, both for the hybrid); distance_threshold None = 1.5 voxel_size.  icp_distance None: no refinement.
+    Returns a dict: transforms (P, 4, 4) float64 on the device (ref ~ T src), ransac_transforms, src_points / ref_points / src_normals /
+    ref_normals / src_feats / ref_feats (the intermediate lists), ransac (the dict of ransac_from_feats_pairs) and icp (that of icp_pairs,
+    or None)."""
+    from .icp import icp_pairs
+    from .ransac import ransac_from_feats_pairs
+    from .scan_prep import estimate_normals_clouds, voxel_downsample_clouds
+    what = 'global_registration_pairs'
+    P = len(src_list)
+    if len(ref_list) != P:
+        raise ValueError('%s: one source and one reference cloud per pair' % what)
+    v = float(voxel_size)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError('%s: voxel size %r is not a positive finite number' % (what, voxel_size))
+    if fpfh_radius is None and fpfh_max_nn is None:
+        fpfh_radius = 5.0 * v
+    if distance_threshold is None:
+        distance_threshold = 1.5 * v
+    dev = device_of(device, src_list, ref_list)
+    clouds = voxel_downsample_clouds(list(src_list) + list(ref_list), v, device=dev)
+    normals = estimate_normals_clouds(clouds, normal_knn, device=dev)
+    feats = compute_fpfh_clouds(clouds, normals, fpfh_radius, fpfh_max_nn, torch.float32, device=dev)
+    src, ref = clouds[:P], clouds[P:]
+    ransac = ransac_from_feats_pairs([c.to(torch.float32) for c in src], [c.to(torch.float32) for c in ref], feats[:P], feats[P:],
+                                     distance_threshold, ransac_n, num_iterations, mutual_filter, seed, edge_length_similarity, check_distance)
+    coarse = ransac['transforms'].to(torch.float64)
+    icp = None
+    if icp_distance is not None:
+        icp = icp_pairs(src, ref, coarse, icp_distance, icp_estimation, normals[P:] if icp_estimation == 'point_to_plane' else None,
+                        max_iteration=icp_max_iteration, device=dev)
+    return {'transforms': icp['transforms'] if icp is not None else coarse, 'ransac_transforms': coarse, 'src_points': src, 'ref_points': ref,
+            'src_normals': normals[:P], 'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'icp': icp}

@@ -2558,3 +2558,61 @@ def keypoint_nms_stack(grid, order, lengths, radius, max_keep=0):
     check(lib().se3_keypoint_nms_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(o), offsets, C, float(radius), int(max_keep), _dp(out),
                                        words.data_ptr(), words[C:].data_ptr(), ws.data_ptr(), nbytes, stream), 'se3_keypoint_nms_stack')
     return out, words
+
+
+# ---- FPFH descriptors of stacked clouds (csrc/fpfh.hip) --------------------------------------------------------------------------------------------
+FPFH_DIM = 33
+FPFH_STATUS = {1: 'a point or normal is not finite'}
+
+
+def _fpfh_cloud(points, normals, lengths, what):
+    p, elem = _pair_points(points, 'points')
+    nr, nelem = _pair_points(normals, 'normals')
+    if nr.shape != p.shape or nr.device != p.device:
+        raise RuntimeError('%s: normals must have the shape and device of the points' % what)
+    return p, elem, nr, nelem, _pair_offsets(lengths, p.shape[0], what)
+
+
+def fpfh_check_stack(points, normals, lengths):
+    """HIP: the finite check of stacked clouds.  Returns words (len(lengths) + 1,) int32 on the DEVICE: bit 1 of word c for a non-finite
+    point or normal of cloud c, the last word the OR of all (FPFH_STATUS)."""
+    p, elem, nr, nelem, offsets = _fpfh_cloud(points, normals, lengths, 'fpfh_check_stack')
+    words = torch.empty((len(lengths) + 1,), dtype=torch.int32, device=p.device)
+    check(lib().se3_fpfh_check_stack(_dp(p), elem, _dp(nr), nelem, offsets, len(lengths), words.data_ptr(), _stream()), 'se3_fpfh_check_stack')
+    return words
+
+
+def _fpfh_list(row_offsets, pairs, row_begin, n_total, dev, what):
+    ro = _req(row_offsets, torch.int64, 'row_offsets', 1)
+    pr = _req(pairs, torch.int64, 'pairs', 2)
+    rows = ro.shape[0] - 1
+    if rows < 0 or row_begin < 0 or row_begin + rows > n_total or pr.shape[1] != 2 or ro.device != dev or pr.device != dev:
+        raise RuntimeError('%s: row_offsets (rows + 1,) and pairs (total, 2) on %s for a slice of the %d rows expected' % (what, dev, n_total))
+    return ro, pr, rows
+
+
+def spfh_stack(points, normals, lengths, row_offsets, pairs, out, row_begin=0):
+    """HIP: the SPFH rows [row_begin, row_begin + len(row_offsets) - 1) of stacked clouds into out (total rows, 33) float64, from the
+    neighbour list (row_offsets from 0, pairs (total, 2) int64 with the neighbour's cloud-local index in column 1, as pair_ball_fill_stack
+    leaves them).  A list entry outside its cloud is skipped."""
+    p, elem, nr, nelem, offsets = _fpfh_cloud(points, normals, lengths, 'spfh_stack')
+    ro, pr, rows = _fpfh_list(row_offsets, pairs, row_begin, p.shape[0], p.device, 'spfh_stack')
+    if tuple(out.shape) != (p.shape[0], FPFH_DIM) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != p.device:
+        raise RuntimeError('spfh_stack: out must be (%d, %d) float64 on %s' % (p.shape[0], FPFH_DIM, p.device))
+    check(lib().se3_spfh_stack(_dp(p), elem, _dp(nr), nelem, offsets, len(lengths), int(row_begin), rows, ro.data_ptr(), _dp(pr), pr.shape[0],
+                               _dp(out), _stream()), 'se3_spfh_stack')
+    return out
+
+
+def fpfh_stack(points, spfh, lengths, row_offsets, pairs, out, row_begin=0):
+    """HIP: the FPFH rows of the same slice into out (total rows, 33) float64 from spfh (total rows, 33), which holds every row of the
+    clouds the slice touches."""
+    p, elem = _pair_points(points, 'points')
+    offsets = _pair_offsets(lengths, p.shape[0], 'fpfh_stack')
+    ro, pr, rows = _fpfh_list(row_offsets, pairs, row_begin, p.shape[0], p.device, 'fpfh_stack')
+    for t in (spfh, out):
+        if tuple(t.shape) != (p.shape[0], FPFH_DIM) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != p.device:
+            raise RuntimeError('fpfh_stack: spfh and out must be (%d, %d) float64 on %s' % (p.shape[0], FPFH_DIM, p.device))
+    check(lib().se3_fpfh_stack(_dp(p), elem, _dp(spfh), offsets, len(lengths), int(row_begin), rows, ro.data_ptr(), _dp(pr), pr.shape[0], _dp(out),
+                               _stream()), 'se3_fpfh_stack')
+    return out
