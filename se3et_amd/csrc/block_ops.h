@@ -1,6 +1,6 @@
 // The building blocks the geometry kernels share (common.h includes this file): the wave sum, the single-workgroup prefix scan, the
-// block-wide bounding box and the host-side workspace carver.  Everything is a template or an inline function, so a file that includes
-// its headers inside an anonymous namespace (csrc/voxel_downsample.hip, csrc/knn_normals.hip) sees the same text through common.h.
+// block-wide bounding box and the host-side workspace carver.  Everything is a template or an inline function, so every file
+// that includes common.h sees the same text and the link sees no duplicate.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -44,10 +44,9 @@
 #include <vector>
 
 #include "common.h"
+#include "fpfh_core.h"          // (and through it pair_grid.h: pg_dist2 here, pg_sqrt there -- stack_rows.h alone is not enough)
 
 namespace {
-#include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
-#include "fpfh_core.h"
 
 constexpr int kFpfhWaves = 4;           // rows per workgroup, of both kernels
 constexpr int kFpfhAhead = 4;           // SPFH rows loaded ahead of their adds
@@ -66,10 +65,6 @@ struct FpfhCall {
   int64_t total;
 };
 
-PG_HD void fpfh_load3(const void* a, int elem, int64_t row, double* out) {
-  out[0] = pg_load(a, elem, 3 * row), out[1] = pg_load(a, elem, 3 * row + 1), out[2] = pg_load(a, elem, 3 * row + 2);
-}
-
 PG_HD bool fpfh_finite3(const double* v) { return fabs(v[0]) < INFINITY && fabs(v[1]) < INFINITY && fabs(v[2]) < INFINITY; }
 
 // the list range of slice row r, or an empty range and *bad when the offsets do not belong to the list
@@ -84,8 +79,8 @@ __global__ __launch_bounds__(256) void fpfh_check_kernel(const void* __restrict_
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_total) return;
   double p[3], n[3];
-  fpfh_load3(points, elem, i, p);
-  fpfh_load3(normals, normals_elem, i, n);
+  pg_load3(points, elem, i, p);
+  pg_load3(normals, normals_elem, i, n);
   if (fpfh_finite3(p) && fpfh_finite3(n)) return;
   atomicOr(status + pg_pair_of_row(rows, i), kFpfhNonFinite);
   atomicOr(status + rows.n, kFpfhNonFinite);
@@ -102,8 +97,8 @@ __global__ __launch_bounds__(kFpfhWaves* SE3_WAVE) void spfh_kernel(FpfhCall c, 
   bool bad;
   fpfh_row_range(c, r, &b, &e, &bad);
   double p1[3], n1[3];
-  fpfh_load3(c.points, c.elem, row, p1);
-  fpfh_load3(c.normals, c.normals_elem, row, n1);
+  pg_load3(c.points, c.elem, row, p1);
+  pg_load3(c.normals, c.normals_elem, row, n1);
   int count = 0, m = 0;                                    // lane b < 33: the count of bin b
   for (int64_t t0 = b; t0 < e; t0 += SE3_WAVE) {
     const int64_t t = t0 + lane;
@@ -113,8 +108,8 @@ __global__ __launch_bounds__(kFpfhWaves* SE3_WAVE) void spfh_kernel(FpfhCall c, 
     int bins[3] = {-1, -1, -1};
     if (use) {
       double p2[3], n2[3];
-      fpfh_load3(c.points, c.elem, s0 + j, p2);
-      fpfh_load3(c.normals, c.normals_elem, s0 + j, n2);
+      pg_load3(c.points, c.elem, s0 + j, p2);
+      pg_load3(c.normals, c.normals_elem, s0 + j, n2);
       fpfh_pair_bins(p1, n1, p2, n2, bins);
     }
     m += __popcll(__ballot(use));
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(kFpfhWaves* SE3_WAVE) void fpfh_kernel(FpfhCall c, 
   bool bad;
   fpfh_row_range(c, r, &b, &e, &bad);
   double p1[3];
-  fpfh_load3(c.points, c.elem, row, p1);
+  pg_load3(c.points, c.elem, row, p1);
   double acc = 0.0;
   for (int64_t t0 = b; t0 < e; t0 += SE3_WAVE) {
     // the tile: lane t holds neighbour t0 + t and its d^2
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(kFpfhWaves* SE3_WAVE) void fpfh_kernel(FpfhCall c, 
     double d2 = 0.0;
     if (inside && j != self) {
       double p2[3];
-      fpfh_load3(c.points, c.elem, s0 + j, p2);
+      pg_load3(c.points, c.elem, s0 + j, p2);
       d2 = pg_dist2(p1, p2);
     }
     const int jl = (int)j;                                 // (inside: j < n < 2^31)
@@ -261,8 +256,8 @@ extern "C" int se3_debug_fpfh_host(const void* points, const void* normals, int6
   *status = 0;
   for (int64_t i = 0; i < n; i++) {
     double p[3], nr[3];
-    fpfh_load3(points, elem, i, p);
-    fpfh_load3(normals, normals_elem, i, nr);
+    pg_load3(points, elem, i, p);
+    pg_load3(normals, normals_elem, i, nr);
     if (!fpfh_finite3(p) || !fpfh_finite3(nr)) *status |= kFpfhNonFinite;
   }
   if (*status) return SE3_OK;
@@ -271,8 +266,8 @@ extern "C" int se3_debug_fpfh_host(const void* points, const void* normals, int6
     bool bad;
     fpfh_row_range(c, i, &b, &e, &bad);
     double p1[3], n1[3];
-    fpfh_load3(points, elem, i, p1);
-    fpfh_load3(normals, normals_elem, i, n1);
+    pg_load3(points, elem, i, p1);
+    pg_load3(normals, normals_elem, i, n1);
     int counts[kFpfhDim] = {0}, m = 0;
     for (int64_t t = b; t < e; t++) {
       const int64_t j = pairs[2 * t + 1];
@@ -283,8 +278,8 @@ extern "C" int se3_debug_fpfh_host(const void* points, const void* normals, int6
       if (j == i) continue;
       double p2[3], n2[3];
       int bins[3];
-      fpfh_load3(points, elem, j, p2);
-      fpfh_load3(normals, normals_elem, j, n2);
+      pg_load3(points, elem, j, p2);
+      pg_load3(normals, normals_elem, j, n2);
       fpfh_pair_bins(p1, n1, p2, n2, bins);
       for (int f = 0; f < 3; f++) counts[f * kFpfhBins + bins[f]]++;
       m++;
@@ -297,12 +292,12 @@ extern "C" int se3_debug_fpfh_host(const void* points, const void* normals, int6
     bool bad;
     fpfh_row_range(c, i, &b, &e, &bad);
     double p1[3], acc[kFpfhDim] = {0.0};
-    fpfh_load3(points, elem, i, p1);
+    pg_load3(points, elem, i, p1);
     for (int64_t t = b; t < e; t++) {
       const int64_t j = pairs[2 * t + 1];
       if (j < 0 || j >= n || j == i) continue;
       double p2[3];
-      fpfh_load3(points, elem, j, p2);
+      pg_load3(points, elem, j, p2);
       const double d2 = pg_dist2(p1, p2);
       if (d2 == 0.0) continue;
       for (int k = 0; k < kFpfhDim; k++) acc[k] = fpfh_weighted_add(acc[k], out_spfh[j * kFpfhDim + k], d2);

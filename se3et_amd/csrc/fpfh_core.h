@@ -1,8 +1,9 @@
 // The arithmetic of the FPFH descriptor (csrc/fpfh.hip): the pair feature, its three bins, the SPFH value and the FPFH value, as
-// __host__ __device__ text that the kernels and se3_debug_fpfh_host both run.  Included after pair_grid.h (PG_HD, pg_sqrt, pg_dist2).
+// __host__ __device__ text that the kernels and se3_debug_fpfh_host both run, on PG_HD, pg_sqrt and pg_dist2 of pair_grid.h.
 // Everything is float64 with contraction off; the only libm call is the square root inside pg_sqrt.  The contract is the header comment
 // of csrc/fpfh.hip.
 #pragma once
+#include "pair_grid.h"
 
 constexpr int kFpfhBins = 11;                 // bins per feature
 constexpr int kFpfhDim = 3 * kFpfhBins;       // a row: theta at 0-10, f1 at 11-21, f2 at 22-32

@@ -43,11 +43,9 @@
 #include <vector>
 
 #include "common.h"
-#include "kabsch.h"
+#include "icp_core.h"          // (and through it pair_grid.h and kabsch.h)
 
 namespace {
-#include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
-#include "icp_core.h"
 
 constexpr int kIcpNnWaves = 4;          // source rows per nearest-neighbour workgroup
 
@@ -117,15 +115,10 @@ __global__ __launch_bounds__(kIcpNnWaves* SE3_WAVE) void icp_nearest_kernel(Pair
   if (c.ws.done[p]) return;                                // (one word per pair: uniform over the wave)
   double T[12], qv[3];
   for (int k = 0; k < 12; k++) T[k] = c.T[16 * p + k];
-  pg_transform(T, pg_load(c.src, c.elem, 3 * i), pg_load(c.src, c.elem, 3 * i + 1), pg_load(c.src, c.elem, 3 * i + 2), qv);
+  pg_transform_row(T, c.src, c.elem, i, qv);
   double d2;
   int j;
-  pg_nearest(g, p, qv, se3_lane(), SE3_WAVE,
-             [](double* best, int* best_j) {
-#pragma unroll
-               for (int o = 32; o > 0; o >>= 1) pg_nearest_update(__shfl_xor(*best, o), __shfl_xor(*best_j, o), best, best_j);
-             },
-             &d2, &j);
+  pg_wave_nearest(g, p, qv, &d2, &j);
   if (se3_lane() == 0) {
     c.ws.nn_idx[i] = j;
     c.ws.nn_d2[i] = d2;
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(kIcpLanes) void icp_step_kernel(IcpCall c, const Pa
 }
 
 bool icp_criteria(IcpCriteria* crit, double r, int mode, double relative_fitness, double relative_rmse, int max_iteration) {
-  if (!(isfinite(r) && r >= 0.0) || (mode != SE3_ICP_POINT_TO_POINT && mode != SE3_ICP_POINT_TO_PLANE)) return false;
+  if (!pg_radius_ok(r) || (mode != SE3_ICP_POINT_TO_POINT && mode != SE3_ICP_POINT_TO_PLANE)) return false;
   if (!(relative_fitness >= 0.0) || !(relative_rmse >= 0.0) || max_iteration < 0 || max_iteration > SE3_ICP_MAX_ITERATION) return false;
   crit->r2 = r * r, crit->relative_fitness = relative_fitness, crit->relative_rmse = relative_rmse;
   crit->max_iteration = max_iteration, crit->mode = mode;
@@ -169,13 +162,15 @@ extern "C" int se3_icp_stack(const void* grid_workspace, size_t grid_workspace_b
               "icp_stack: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode, relative_fitness,
               relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
   SE3_REQUIRE(mode != SE3_ICP_POINT_TO_PLANE || ref_normals, SE3_ERR_INVALID_ARG, "icp_stack: point-to-plane needs the reference normals");
-  IcpCall c;
-  SE3_REQUIRE(pg_fill_rows(&c.rows, src_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "icp_stack: offsets must start at 0 and not decrease");
-  const int64_t n_total = c.rows.start[num_pairs];
+  PairGridCall gc;                // (the count above and the row bound below are worded by this entry: the call makes the other checks)
+  if (const int rc = pg_grid_call("icp_stack", "pairs", true, grid_workspace, grid_workspace_bytes, nref_total, elem, src_offsets_host, num_pairs,
+                                  INT64_MAX, &gc))
+    return rc;
+  const int64_t n_total = gc.n_total;
   SE3_REQUIRE(n_total < (1ll << 31), SE3_ERR_UNSUPPORTED, "icp_stack: %lld source rows in one call", (long long)n_total);
-  PairGridLayout G;
-  SE3_REQUIRE(pg_carve(nref_total, num_pairs, (char*)grid_workspace, &G) <= grid_workspace_bytes, SE3_ERR_WORKSPACE,
-              "icp_stack: grid workspace of %zu bytes is too small", grid_workspace_bytes);
+  const PairGridLayout& G = gc.G;
+  IcpCall c;
+  c.rows = gc.rows;
   SE3_REQUIRE(icp_carve(n_total, num_pairs, (char*)workspace, &c.ws) <= workspace_bytes, SE3_ERR_WORKSPACE,
               "icp_stack: workspace of %zu bytes is too small", workspace_bytes);
   if (num_pairs == 0) return SE3_OK;
@@ -209,20 +204,13 @@ extern "C" int se3_debug_icp_host(const void* src_points, int64_t n, const void*
               "debug_icp_host: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode,
               relative_fitness, relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
   SE3_REQUIRE(mode != SE3_ICP_POINT_TO_PLANE || ref_normals, SE3_ERR_INVALID_ARG, "debug_icp_host: point-to-plane needs the reference normals");
-  std::vector<char> mem(pg_carve(nref, 1, nullptr, nullptr));
-  PairGridLayout G;
-  pg_carve(nref, 1, mem.data(), &G);
-  PairRows ref_rows;
-  ref_rows.n = 1, ref_rows.start[0] = 0;
-  for (int p = 1; p <= kPairMaxPairs; p++) ref_rows.start[p] = nref;
-  const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  pg_build_host(ref_points, elem, ref_rows, eye, max_correspondence_distance, G);
+  PairHostGrid H(ref_points, nref, elem, nullptr, max_correspondence_distance);
+  const PairGridLayout& G = H.G;
   std::vector<int> nn_idx((size_t)n + 1);
   std::vector<double> nn_d2((size_t)n + 1), sh((size_t)kIcpMaxSums * kIcpLanes);
   int done = 0;
   IcpCall c;
-  c.rows.n = 1, c.rows.start[0] = 0;
-  for (int p = 1; p <= kPairMaxPairs; p++) c.rows.start[p] = n;
+  c.rows = pg_single_rows(n);
   c.src = src_points, c.elem = elem, c.ref = G.moved, c.normals = ref_normals, c.normals_elem = normals_elem;
   c.ws.nn_idx = nn_idx.data(), c.ws.nn_d2 = nn_d2.data(), c.ws.done = &done;
   c.T = out_transform, c.fitness = out_fitness, c.rmse = out_rmse, c.iterations = out_iterations, c.converged = out_converged;

@@ -2,9 +2,12 @@
 // convergence test and update (icp_pair_step), with the summation order they share.  The kernels run it with one workgroup of kIcpLanes
 // threads per pair (each thread one lane, `barrier` = __syncthreads); se3_debug_icp_host runs the same text serially over all lanes with
 // a no-op barrier.  The contract is the header comment of icp.hip.
-#pragma once          // (after pair_grid.h and kabsch.h)
+#pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include "kabsch.h"
+#include "pair_grid.h"
 
 // Summation order of every sum over a pair's rows: lane l of kIcpLanes adds rows l, l + kIcpLanes, .. serially from zero, then the
 // lanes are added by the tree lane[l] += lane[l + o], o = kIcpLanes / 2 .. 1.  It depends on the pair's row count alone.
@@ -109,9 +112,7 @@ PG_HD bool icp_finite3(const void* a, int elem, int64_t i) {
 }
 
 // row i of the pair moved by T
-PG_HD void icp_moved(const IcpPair& v, const double* T, int64_t i, double* p) {
-  pg_transform(T, pg_load(v.src, v.elem, 3 * i), pg_load(v.src, v.elem, 3 * i + 1), pg_load(v.src, v.elem, 3 * i + 2), p);
-}
+PG_HD void icp_moved(const IcpPair& v, const double* T, int64_t i, double* p) { pg_transform_row(T, v.src, v.elem, i, p); }
 
 // J = [p x n, n] and the residual (p - q) . n of correspondence i (point-to-plane): p the moved row, q its reference row, n q's normal
 PG_HD void icp_plane_row(const IcpPair& v, const double* T, int64_t i, double* J, double* res) {

@@ -42,9 +42,9 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_grid.h"
 
 namespace {
-#include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
 
 constexpr int kKpTile = 256;            // ranks per tile = threads per workgroup
 constexpr int kKpNonFinite = 1;         // status bits
@@ -224,9 +224,11 @@ extern "C" int se3_keypoint_nms_stack(const void* grid_workspace, size_t grid_wo
   KpCall k;
   SE3_REQUIRE(pg_fill_rows(&k.rows, offsets_host, num_clouds) && k.rows.start[num_clouds] == n_total, SE3_ERR_INVALID_ARG,
               "keypoint_nms_stack: offsets must start at 0, not decrease and end at n_total = %lld", (long long)n_total);
-  PairGridLayout G;
-  SE3_REQUIRE(pg_carve(n_total, num_clouds, (char*)grid_workspace, &G) <= grid_workspace_bytes, SE3_ERR_WORKSPACE,
-              "keypoint_nms_stack: grid workspace of %zu bytes is too small", grid_workspace_bytes);
+  PairGridCall c;                 // (the count and the offsets are worded by this entry, above: the call adds the grid workspace's check)
+  if (const int rc = pg_grid_call("keypoint_nms_stack", "clouds", true, grid_workspace, grid_workspace_bytes, n_total, 0, offsets_host, num_clouds,
+                                  1ll << 31, &c))
+    return rc;
+  const PairGridLayout& G = c.G;
   KpLayout L;
   SE3_REQUIRE(kp_carve(n_total, (char*)workspace, &L) <= workspace_bytes, SE3_ERR_WORKSPACE,
               "keypoint_nms_stack: workspace of %zu bytes is too small", workspace_bytes);
@@ -249,14 +251,8 @@ extern "C" int se3_debug_keypoint_nms_host(const void* points, int64_t n, int el
               (long long)n, elem);
   SE3_REQUIRE(isfinite(radius) && radius > 0.0, SE3_ERR_INVALID_ARG, "debug_keypoint_nms_host: radius %g is not a positive finite number", radius);
   *out_count = 0, *status = 0;
-  std::vector<char> mem(pg_carve(n, 1, nullptr, nullptr));
-  PairGridLayout G;
-  pg_carve(n, 1, mem.data(), &G);
-  PairRows rows;
-  rows.n = 1, rows.start[0] = 0;
-  for (int p = 1; p <= kPairMaxPairs; p++) rows.start[p] = n;
-  const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  pg_build_host(points, elem, rows, eye, radius, G);
+  PairHostGrid H(points, n, elem, nullptr, radius);
+  const PairGridLayout& G = H.G;
   std::vector<int> rank((size_t)n + 1, -1);
   std::vector<unsigned char> kept((size_t)n + 1);
   for (int64_t i = 0; i < n; i++)

@@ -23,15 +23,14 @@
 //   No float atomics; a row's result does not depend on the batch it is in, nor on the run.
 #include <math.h>
 
-#include <vector>
-
 #include "common.h"
+#include "pair_grid.h"
 
 namespace {
-#include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
 
 static_assert(kPairKnnMax == SE3_KNN_MAX, "pair_grid.h and include/se3et_hip.h name one limit");
 constexpr int kKnnWaves = 4;          // query rows per workgroup
+constexpr int64_t kKnnMaxRows = (1ll << 31) / kPairKnnMax;          // out_idx and out_d2 index row * k + column below 2^31
 constexpr int kJacobiSweeps = 10;     // (a 3x3 matrix is diagonal to rounding after 5 or 6)
 
 // ---- the normal of a neighbour list: the same text on the host and on the device --------------------------------------------------------------
@@ -157,7 +156,8 @@ __global__ __launch_bounds__(kKnnWaves* SE3_WAVE) void knn_kernel(PairGridView g
                                                                   double* __restrict__ out_d2) {
   const int64_t i = (int64_t)blockIdx.x * kKnnWaves + (threadIdx.x >> 6);
   if (i >= nq_total) return;                               // (uniform over the wave)
-  const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
+  double qv[3];
+  pg_load3(q, elem, i, qv);
   WaveKnnList list;
   list.init(k);
   pg_knn(g, pg_pair_of_row(rows, i), qv, se3_lane(), SE3_WAVE, list);
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(kKnnWaves* SE3_WAVE) void knn_normals_kernel(PairGr
   const int64_t i = (int64_t)blockIdx.x * kKnnWaves + (threadIdx.x >> 6);
   if (i >= nq_total) return;
   const int p = pg_pair_of_row(rows, i);
-  const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
+  double qv[3];
+  pg_load3(q, elem, i, qv);
   WaveKnnList list;
   list.init(k);
   pg_knn(g, p, qv, se3_lane(), SE3_WAVE, list);
@@ -193,44 +194,18 @@ __global__ __launch_bounds__(kKnnWaves* SE3_WAVE) void knn_normals_kernel(PairGr
   if (se3_lane() == 0) out[3 * i] = n[0], out[3 * i + 1] = n[1], out[3 * i + 2] = n[2];
 }
 
-// what both search entries check: pointers, cloud count, offsets, k, the grid workspace's size
-#define KNN_SEARCH_ARGS(name, extra)                                                                                                        \
-  SE3_REQUIRE(grid_workspace && q_points && q_offsets_host && (extra), SE3_ERR_INVALID_ARG, name ": null pointer");                          \
-  SE3_REQUIRE(num_clouds >= 0 && num_clouds <= kPairMaxPairs && ns_total >= 0 && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,              \
-              name ": %d clouds (at most %d), ns_total %lld, elem %d", num_clouds, kPairMaxPairs, (long long)ns_total, elem);               \
-  SE3_REQUIRE(k >= 1 && k <= kPairKnnMax, SE3_ERR_INVALID_ARG, name ": k %d not in [1, %d]", k, kPairKnnMax);                                \
-  PairRows rows;                                                                                                                             \
-  SE3_REQUIRE(pg_fill_rows(&rows, q_offsets_host, num_clouds), SE3_ERR_INVALID_ARG, name ": offsets must start at 0 and not decrease");      \
-  PairGridLayout G;                                                                                                                          \
-  SE3_REQUIRE(pg_carve(ns_total, num_clouds, (char*)grid_workspace, &G) <= workspace_bytes, SE3_ERR_WORKSPACE,                               \
-              name ": grid workspace of %zu bytes is too small", workspace_bytes);                                                          \
-  const int64_t nq_total = rows.start[num_clouds];                                                                                           \
-  SE3_REQUIRE(nq_total < (1ll << 31) / kPairKnnMax, SE3_ERR_UNSUPPORTED, name ": %lld query rows in one call", (long long)nq_total)
-
-// one cloud's grid on host memory, identity transform, the density cell size
-struct HostCloudGrid {
-  std::vector<char> mem;
-  PairGridLayout G;
-  HostCloudGrid(const void* s, int64_t ns, int elem) {
-    mem.resize(pg_carve(ns, 1, nullptr, nullptr));
-    pg_carve(ns, 1, mem.data(), &G);
-    PairRows rows;
-    rows.n = 1;
-    rows.start[0] = 0;
-    for (int p = 1; p <= kPairMaxPairs; p++) rows.start[p] = ns;
-    const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    pg_build_host(s, elem, rows, eye, 0.0, G);
-  }
-};
-
 }  // namespace
 
 extern "C" int se3_knn_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                              const int64_t* q_offsets_host, int num_clouds, int k, int64_t* out_idx, double* out_d2, void* stream) {
-  KNN_SEARCH_ARGS("knn_stack", out_idx && out_d2);
-  if (nq_total == 0) return SE3_OK;
-  knn_kernel<<<(unsigned)se3_cdiv(nq_total, kKnnWaves), kKnnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(G.view(), q_points, elem, rows, nq_total, k,
-                                                                                                      out_idx, out_d2);
+  SE3_REQUIRE(k >= 1 && k <= kPairKnnMax, SE3_ERR_INVALID_ARG, "knn_stack: k %d not in [1, %d]", k, kPairKnnMax);
+  PairGridCall c;
+  if (const int rc = pg_grid_call("knn_stack", "clouds", q_points && out_idx && out_d2, grid_workspace, workspace_bytes, ns_total, elem,
+                                  q_offsets_host, num_clouds, kKnnMaxRows, &c))
+    return rc;
+  if (c.n_total == 0) return SE3_OK;
+  knn_kernel<<<(unsigned)se3_cdiv(c.n_total, kKnnWaves), kKnnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(c.G.view(), q_points, elem, c.rows,
+                                                                                                        c.n_total, k, out_idx, out_d2);
   SE3_CHECK_LAUNCH("knn_stack");
   return SE3_OK;
 }
@@ -238,7 +213,11 @@ extern "C" int se3_knn_stack(const void* grid_workspace, size_t workspace_bytes,
 extern "C" int se3_knn_normals_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                                      const int64_t* q_offsets_host, int num_clouds, int k, const double* viewpoints_host, double* out_normals,
                                      void* stream) {
-  KNN_SEARCH_ARGS("knn_normals_stack", out_normals);
+  SE3_REQUIRE(k >= 1 && k <= kPairKnnMax, SE3_ERR_INVALID_ARG, "knn_normals_stack: k %d not in [1, %d]", k, kPairKnnMax);
+  PairGridCall c;
+  if (const int rc = pg_grid_call("knn_normals_stack", "clouds", q_points && out_normals, grid_workspace, workspace_bytes, ns_total, elem,
+                                  q_offsets_host, num_clouds, kKnnMaxRows, &c))
+    return rc;
   KnnViewpoints views;
   views.on = viewpoints_host != nullptr;
   for (int p = 0; p < kPairMaxPairs; p++)
@@ -246,9 +225,9 @@ extern "C" int se3_knn_normals_stack(const void* grid_workspace, size_t workspac
       views.v[p][d] = views.on && p < num_clouds ? viewpoints_host[3 * p + d] : 0.0;
       SE3_REQUIRE(isfinite(views.v[p][d]), SE3_ERR_INVALID_ARG, "knn_normals_stack: non-finite viewpoint");
     }
-  if (nq_total == 0) return SE3_OK;
-  knn_normals_kernel<<<(unsigned)se3_cdiv(nq_total, kKnnWaves), kKnnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(
-      G.view(), G.moved, q_points, elem, rows, nq_total, k, views, out_normals);
+  if (c.n_total == 0) return SE3_OK;
+  knn_normals_kernel<<<(unsigned)se3_cdiv(c.n_total, kKnnWaves), kKnnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(
+      c.G.view(), c.G.moved, q_points, elem, c.rows, c.n_total, k, views, out_normals);
   SE3_CHECK_LAUNCH("knn_normals_stack");
   return SE3_OK;
 }
@@ -260,10 +239,11 @@ extern "C" int se3_debug_knn_host(const void* q_points, int64_t nq, const void* 
   SE3_REQUIRE(nq >= 0 && ns >= 0 && ns < (1ll << 31) && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG, "debug_knn_host: nq %lld, ns %lld, elem %d",
               (long long)nq, (long long)ns, elem);
   SE3_REQUIRE(k >= 1 && k <= kPairKnnMax, SE3_ERR_INVALID_ARG, "debug_knn_host: k %d not in [1, %d]", k, kPairKnnMax);
-  HostCloudGrid H(s_points, ns, elem);
+  PairHostGrid H(s_points, ns, elem, nullptr, 0.0);
   const PairGridView g = H.G.view();
   for (int64_t i = 0; i < nq; i++) {
-    const double qv[3] = {pg_load(q_points, elem, 3 * i), pg_load(q_points, elem, 3 * i + 1), pg_load(q_points, elem, 3 * i + 2)};
+    double qv[3];
+    pg_load3(q_points, elem, i, qv);
     PairKnnSerialList list;
     list.init(k);
     pg_knn(g, 0, qv, 0, 1, list);
@@ -284,10 +264,11 @@ extern "C" int se3_debug_knn_normals_host(const void* points, int64_t n, int ele
   SE3_REQUIRE(k >= 1 && k <= kPairKnnMax, SE3_ERR_INVALID_ARG, "debug_knn_normals_host: k %d not in [1, %d]", k, kPairKnnMax);
   SE3_REQUIRE(!viewpoint || (isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])), SE3_ERR_INVALID_ARG,
               "debug_knn_normals_host: non-finite viewpoint");
-  HostCloudGrid H(points, n, elem);
+  PairHostGrid H(points, n, elem, nullptr, 0.0);
   const PairGridView g = H.G.view();
   for (int64_t i = 0; i < n; i++) {
-    const double qv[3] = {pg_load(points, elem, 3 * i), pg_load(points, elem, 3 * i + 1), pg_load(points, elem, 3 * i + 2)};
+    double qv[3];
+    pg_load3(points, elem, i, qv);
     PairKnnSerialList list;
     list.init(k);
     pg_knn(g, 0, qv, 0, 1, list);

@@ -2,9 +2,9 @@
 // get_nearest_neighbor (geotransformer/utils/pointcloud.py:11-22), compute_overlap and get_correspondences (utils/registration.py:149-173)
 // and calibrate_ground_truth (datasets/registration/threedmatch/utils.py:197-228: the overlap and 6x6 covariance of a gt.info record).
 // The query cloud of a pair is searched in the OTHER cloud of the pair after a rigid transform; csrc/pair_grid.h holds the grid and the
-// search core, se3et_amd/pair_geometry.py carries the same contract.
+// search core, this file the grid's device build, se3et_amd/pair_geometry.py carries the same contract.
 //
-//   pair_grid_*_kernel          (pair_grid.h) transform + exact bounding box, cell histogram, scan, scatter; batched over pairs.
+//   pair_grid_*_kernel          the build: transform + exact bounding box, cell histogram, scan, scatter; batched over pairs.
 //   pair_nearest_kernel         exact 1-NN, one wave per query row of the stacked rows: lanes stride the points of the cells of a ring,
 //                               the wave reduces on (d^2, index), the running best stays in registers, the rings stop by the shell rule.
 //   pair_ball_count_kernel      ball query, pass 1: hits per row, then se3_exclusive_scan_i64 over the stacked rows (block_ops.h).
@@ -38,18 +38,77 @@
 //            se3et_amd/pair_geometry.py.)
 #include <math.h>
 
-#include <vector>
-
 #include "common.h"
 #include "pair_grid.h"
 
 namespace {
 
-static_assert(kPairMaxPairs == SE3_PAIR_MAX_PAIRS, "pair_grid.h and include/se3et_hip.h name one limit");
+static_assert(kPairMaxPairs == SE3_PAIR_MAX_PAIRS, "stack_rows.h and include/se3et_hip.h name one limit");
 constexpr int kNnWaves = 4;          // query rows per nearest-neighbour workgroup
 constexpr int kBallThreads = 64;     // query rows per ball-query workgroup
 constexpr int kRowThreads = 256;
 constexpr int kSums = 10;            // n, x, y, z, zz+yy, zz+xx, yy+xx, xy, xz, yz
+
+// ---- the build as kernels, batched over pairs --------------------------------------------------------------------------------------------
+struct PairTransforms {
+  double T[kPairMaxPairs][12];
+};
+
+constexpr int kPairBoundsThreads = 256;
+
+// one workgroup per pair: transform the support into `moved`, exact bounding box, grid geometry
+__global__ __launch_bounds__(kPairBoundsThreads) void pair_grid_bounds_kernel(const void* __restrict__ s, int elem, PairRows rows, PairTransforms tf,
+                                                                double cell_hint, PairGridLayout G) {
+  __shared__ double sh[kPairBoundsThreads / 64];
+  const int p = blockIdx.x;
+  const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
+  double T[12];
+  for (int k = 0; k < 12; k++) T[k] = tf.T[p][k];
+  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int64_t i = s0 + threadIdx.x; i < s0 + n; i += kPairBoundsThreads) {
+    double w[3];        // (the loads written out: through pg_load3 hipcc 7.2 orders this loop's address arithmetic differently)
+    pg_transform(T, pg_load(s, elem, 3 * i), pg_load(s, elem, 3 * i + 1), pg_load(s, elem, 3 * i + 2), w);
+    for (int d = 0; d < 3; d++) {
+      G.moved[3 * i + d] = w[d];
+      mn[d] = fmin(mn[d], w[d]);
+      mx[d] = fmax(mx[d], w[d]);
+    }
+  }
+  se3_block_bounds<double, kPairBoundsThreads>(mn, mx, sh);
+  if (threadIdx.x == 0) {
+    PairGridMeta* m = G.meta + p;
+    for (int k = 0; k < 12; k++) m->T[k] = T[k];
+    m->s_start = s0, m->ns = n;
+    pg_make_grid(mn, mx, n, cell_hint, m);
+  }
+}
+
+// cell histogram (the only atomics of the build: integer adds, order-free)
+__global__ __launch_bounds__(256) void pair_grid_count_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ns_total) return;
+  const int p = pg_pair_of_row(rows, i);
+  atomicAdd(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1);
+}
+
+// one workgroup per pair: counts -> INCLUSIVE ends (the scatter counts each end down to its cell's start); cells[ncells] = ns
+__global__ __launch_bounds__(1024) void pair_grid_scan_kernel(PairGridLayout G) {
+  __shared__ int sh[1024];
+  const int n = G.meta[blockIdx.x].ncells;
+  int* a = G.cells + (size_t)blockIdx.x * (kPairCellCap + 1);
+  const int total = se3_block_scan<kSe3ScanInclusive>(a, n, sh);
+  if (threadIdx.x == 0) a[n] = total;
+}
+
+__global__ __launch_bounds__(256) void pair_grid_scatter_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ns_total) return;
+  const int p = pg_pair_of_row(rows, i);
+  const int64_t s0 = rows.start[p];
+  const int pos = atomicSub(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1) - 1;
+  for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
+  G.sorted_idx[s0 + pos] = (int)(i - s0);
+}
 
 __global__ __launch_bounds__(kNnWaves* SE3_WAVE) void pair_nearest_kernel(PairGridView g, const void* __restrict__ q, int elem, PairRows rows,
                                                                           int64_t nq_total, double* __restrict__ dist,
@@ -57,15 +116,10 @@ __global__ __launch_bounds__(kNnWaves* SE3_WAVE) void pair_nearest_kernel(PairGr
   const int64_t i = (int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6);
   if (i >= nq_total) return;                               // (uniform over the wave)
   const int p = pg_pair_of_row(rows, i);
-  const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
-  double d2;
+  double qv[3], d2;
   int j;
-  pg_nearest(g, p, qv, se3_lane(), SE3_WAVE,
-             [](double* best, int* best_j) {
-#pragma unroll
-               for (int o = 32; o > 0; o >>= 1) pg_nearest_update(__shfl_xor(*best, o), __shfl_xor(*best_j, o), best, best_j);
-             },
-             &d2, &j);
+  pg_load3(q, elem, i, qv);
+  pg_wave_nearest(g, p, qv, &d2, &j);
   if (se3_lane() == 0) {
     dist[i] = sqrt(d2);
     index[i] = j;
@@ -76,7 +130,8 @@ __global__ __launch_bounds__(kBallThreads) void pair_ball_count_kernel(PairGridV
                                                                        int64_t nq_total, double r, double r2, int64_t* __restrict__ row_offsets) {
   const int64_t i = (int64_t)blockIdx.x * kBallThreads + threadIdx.x;
   if (i >= nq_total) return;
-  const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
+  double qv[3];
+  pg_load3(q, elem, i, qv);
   row_offsets[i] = pg_ball_count(g, pg_pair_of_row(rows, i), qv, r, r2);
 }
 
@@ -88,7 +143,8 @@ __global__ __launch_bounds__(kBallThreads) void pair_ball_fill_kernel(PairGridVi
   const int64_t base = row_offsets[i], room = row_offsets[i + 1] - base;
   if (base < 0 || room <= 0 || base + room > total) return;           // (offsets that do not belong to `out`: nothing is written)
   const int p = pg_pair_of_row(rows, i);
-  const double qv[3] = {pg_load(q, elem, 3 * i), pg_load(q, elem, 3 * i + 1), pg_load(q, elem, 3 * i + 2)};
+  double qv[3];
+  pg_load3(q, elem, i, qv);
   pg_ball_fill(g, p, qv, r, r2, i - rows.start[p], out + 2 * base, room);
 }
 
@@ -134,7 +190,7 @@ __global__ __launch_bounds__(kRowThreads) void pair_covariance_kernel(const void
     const int64_t j = selected[k0 + k];
     if (j < 0 || j >= ns) continue;                                  // (refused on the host where the host sees the indices)
     double w[3];
-    pg_transform(T, pg_load(src, elem, 3 * (s0 + j)), pg_load(src, elem, 3 * (s0 + j) + 1), pg_load(src, elem, 3 * (s0 + j) + 2), w);
+    pg_transform_row(T, src, elem, s0 + j, w);
     const double x = w[0], y = w[1], z = w[2];
     acc[0] += 1.0, acc[1] += x, acc[2] += y, acc[3] += z;
     acc[4] += z * z + y * y, acc[5] += z * z + x * x, acc[6] += y * y + x * x;
@@ -167,19 +223,6 @@ void fill_transforms(PairTransforms* tf, const double* T, int num_pairs) {
     for (int k = 0; k < 12; k++) tf->T[p][k] = p < num_pairs ? T[16 * p + k] : 0.0;
 }
 
-// what every search entry checks: pointers, pair count, offsets, the grid workspace's size
-#define PAIR_SEARCH_ARGS(name, extra)                                                                                                       \
-  SE3_REQUIRE(grid_workspace && q_points && q_offsets_host && (extra), SE3_ERR_INVALID_ARG, name ": null pointer");                          \
-  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && ns_total >= 0 && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,                \
-              name ": %d pairs (at most %d), ns_total %lld, elem %d", num_pairs, kPairMaxPairs, (long long)ns_total, elem);                 \
-  PairRows rows;                                                                                                                             \
-  SE3_REQUIRE(pg_fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, name ": offsets must start at 0 and not decrease");          \
-  PairGridLayout G;                                                                                                                          \
-  SE3_REQUIRE(pg_carve(ns_total, num_pairs, (char*)grid_workspace, &G) <= workspace_bytes, SE3_ERR_WORKSPACE,                                \
-              name ": grid workspace of %zu bytes is too small", workspace_bytes);                                                          \
-  const int64_t nq_total = rows.start[num_pairs];                                                                                            \
-  SE3_REQUIRE(nq_total < (1ll << 31), SE3_ERR_UNSUPPORTED, name ": %lld query rows in one call", (long long)nq_total)
-
 }  // namespace
 
 extern "C" size_t se3_pair_grid_workspace_bytes(int64_t ns_total, int num_pairs) {
@@ -192,7 +235,7 @@ extern "C" int se3_pair_grid_build(const void* s_points, int elem, const int64_t
   SE3_REQUIRE(s_points && s_offsets_host && transforms_host && workspace, SE3_ERR_INVALID_ARG, "pair_grid_build: null pointer");
   SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,
               "pair_grid_build: %d pairs (at most %d), elem %d", num_pairs, kPairMaxPairs, elem);
-  SE3_REQUIRE(isfinite(cell_hint) && cell_hint >= 0.0, SE3_ERR_INVALID_ARG, "pair_grid_build: cell size hint %g", cell_hint);
+  SE3_REQUIRE(pg_radius_ok(cell_hint), SE3_ERR_INVALID_ARG, "pair_grid_build: cell size hint %g", cell_hint);
   SE3_REQUIRE(finite_transforms(transforms_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_grid_build: non-finite transform");
   PairRows rows;
   SE3_REQUIRE(pg_fill_rows(&rows, s_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_grid_build: offsets must start at 0 and not decrease");
@@ -219,23 +262,29 @@ extern "C" int se3_pair_grid_build(const void* s_points, int elem, const int64_t
 
 extern "C" int se3_pair_nearest_neighbor_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                                                const int64_t* q_offsets_host, int num_pairs, double* distances, int64_t* indices, void* stream) {
-  PAIR_SEARCH_ARGS("pair_nearest_neighbor_stack", distances && indices);
-  if (nq_total == 0) return SE3_OK;
-  pair_nearest_kernel<<<(unsigned)se3_cdiv(nq_total, kNnWaves), kNnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(G.view(), q_points, elem, rows,
-                                                                                                             nq_total, distances, indices);
+  PairGridCall c;
+  if (const int rc = pg_grid_call("pair_nearest_neighbor_stack", "pairs", q_points && distances && indices, grid_workspace, workspace_bytes,
+                                  ns_total, elem, q_offsets_host, num_pairs, 1ll << 31, &c))
+    return rc;
+  if (c.n_total == 0) return SE3_OK;
+  pair_nearest_kernel<<<(unsigned)se3_cdiv(c.n_total, kNnWaves), kNnWaves * SE3_WAVE, 0, (hipStream_t)stream>>>(c.G.view(), q_points, elem, c.rows,
+                                                                                                               c.n_total, distances, indices);
   SE3_CHECK_LAUNCH("pair_nearest_neighbor_stack");
   return SE3_OK;
 }
 
 extern "C" int se3_pair_ball_count_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                                          const int64_t* q_offsets_host, int num_pairs, double radius, int64_t* row_offsets, void* stream) {
-  PAIR_SEARCH_ARGS("pair_ball_count_stack", row_offsets);
-  SE3_REQUIRE(isfinite(radius) && radius >= 0.0, SE3_ERR_INVALID_ARG, "pair_ball_count_stack: radius %g", radius);
+  PairGridCall c;
+  if (const int rc = pg_grid_call("pair_ball_count_stack", "pairs", q_points && row_offsets, grid_workspace, workspace_bytes,
+                                  ns_total, elem, q_offsets_host, num_pairs, 1ll << 31, &c))
+    return rc;
+  SE3_REQUIRE(pg_radius_ok(radius), SE3_ERR_INVALID_ARG, "pair_ball_count_stack: radius %g", radius);
   hipStream_t st = (hipStream_t)stream;
-  if (nq_total > 0)
-    pair_ball_count_kernel<<<(unsigned)se3_cdiv(nq_total, kBallThreads), kBallThreads, 0, st>>>(G.view(), q_points, elem, rows, nq_total, radius,
-                                                                                               radius * radius, row_offsets);
-  se3_exclusive_scan_i64(row_offsets, nq_total, st);
+  if (c.n_total > 0)
+    pair_ball_count_kernel<<<(unsigned)se3_cdiv(c.n_total, kBallThreads), kBallThreads, 0, st>>>(c.G.view(), q_points, elem, c.rows, c.n_total,
+                                                                                                 radius, radius * radius, row_offsets);
+  se3_exclusive_scan_i64(row_offsets, c.n_total, st);
   SE3_CHECK_LAUNCH("pair_ball_count_stack");
   return SE3_OK;
 }
@@ -243,12 +292,15 @@ extern "C" int se3_pair_ball_count_stack(const void* grid_workspace, size_t work
 extern "C" int se3_pair_ball_fill_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                                         const int64_t* q_offsets_host, int num_pairs, double radius, const int64_t* row_offsets, int64_t total,
                                         int64_t* out, void* stream) {
-  PAIR_SEARCH_ARGS("pair_ball_fill_stack", row_offsets && (out || total == 0));
-  SE3_REQUIRE(isfinite(radius) && radius >= 0.0 && total >= 0, SE3_ERR_INVALID_ARG, "pair_ball_fill_stack: radius %g, total %lld", radius,
+  PairGridCall c;
+  if (const int rc = pg_grid_call("pair_ball_fill_stack", "pairs", q_points && row_offsets && (out || total == 0), grid_workspace, workspace_bytes,
+                                  ns_total, elem, q_offsets_host, num_pairs, 1ll << 31, &c))
+    return rc;
+  SE3_REQUIRE(pg_radius_ok(radius) && total >= 0, SE3_ERR_INVALID_ARG, "pair_ball_fill_stack: radius %g, total %lld", radius,
               (long long)total);
-  if (nq_total == 0 || total == 0) return SE3_OK;
-  pair_ball_fill_kernel<<<(unsigned)se3_cdiv(nq_total, kBallThreads), kBallThreads, 0, (hipStream_t)stream>>>(
-      G.view(), q_points, elem, rows, nq_total, radius, radius * radius, row_offsets, total, out);
+  if (c.n_total == 0 || total == 0) return SE3_OK;
+  pair_ball_fill_kernel<<<(unsigned)se3_cdiv(c.n_total, kBallThreads), kBallThreads, 0, (hipStream_t)stream>>>(
+      c.G.view(), q_points, elem, c.rows, c.n_total, radius, radius * radius, row_offsets, total, out);
   SE3_CHECK_LAUNCH("pair_ball_fill_stack");
   return SE3_OK;
 }
@@ -258,7 +310,7 @@ extern "C" int se3_pair_overlap_stack(const double* nn_distances, const int64_t*
   SE3_REQUIRE(nn_distances && q_offsets_host && out, SE3_ERR_INVALID_ARG, "pair_overlap_stack: null pointer");
   SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs, SE3_ERR_INVALID_ARG, "pair_overlap_stack: %d pairs (at most %d)", num_pairs,
               kPairMaxPairs);
-  SE3_REQUIRE(isfinite(radius) && radius >= 0.0, SE3_ERR_INVALID_ARG, "pair_overlap_stack: radius %g", radius);
+  SE3_REQUIRE(pg_radius_ok(radius), SE3_ERR_INVALID_ARG, "pair_overlap_stack: radius %g", radius);
   PairRows rows;
   SE3_REQUIRE(pg_fill_rows(&rows, q_offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "pair_overlap_stack: offsets must start at 0 and not decrease");
   if (num_pairs == 0) return SE3_OK;
@@ -287,32 +339,17 @@ extern "C" int se3_pair_info_covariance_stack(const void* src_points, int elem, 
 }
 
 // ---- the header's search core on host memory (tests/test_pair_geometry_cpu.py) -------------------------------------------------------------
-namespace {
-struct HostGrid {
-  std::vector<char> mem;
-  PairGridLayout G;
-  HostGrid(const void* s, int64_t ns, int elem, const double* transform, double cell_hint) {
-    mem.resize(pg_carve(ns, 1, nullptr, nullptr));
-    pg_carve(ns, 1, mem.data(), &G);
-    PairRows rows;
-    rows.n = 1;
-    rows.start[0] = 0;
-    for (int p = 1; p <= kPairMaxPairs; p++) rows.start[p] = ns;
-    pg_build_host(s, elem, rows, transform, cell_hint, G);
-  }
-};
-}  // namespace
-
 extern "C" int se3_debug_pair_nearest_neighbor_host(const void* q_points, int64_t nq, const void* s_points, int64_t ns, int elem,
                                                     const double* transform, double* distances, int64_t* indices) {
   SE3_REQUIRE(q_points && s_points && transform && distances && indices, SE3_ERR_INVALID_ARG, "debug_pair_nearest_neighbor_host: null pointer");
   SE3_REQUIRE(nq >= 0 && ns >= 0 && ns < (1ll << 31) && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,
               "debug_pair_nearest_neighbor_host: nq %lld, ns %lld, elem %d", (long long)nq, (long long)ns, elem);
   SE3_REQUIRE(finite_transforms(transform, 1), SE3_ERR_INVALID_ARG, "debug_pair_nearest_neighbor_host: non-finite transform");
-  HostGrid H(s_points, ns, elem, transform, 0.0);
+  PairHostGrid H(s_points, ns, elem, transform, 0.0);
   const PairGridView g = H.G.view();
   for (int64_t i = 0; i < nq; i++) {
-    const double qv[3] = {pg_load(q_points, elem, 3 * i), pg_load(q_points, elem, 3 * i + 1), pg_load(q_points, elem, 3 * i + 2)};
+    double qv[3];
+    pg_load3(q_points, elem, i, qv);
     double d2;
     int j;
     pg_nearest(g, 0, qv, 0, 1, [](double*, int*) {}, &d2, &j);
@@ -329,14 +366,15 @@ extern "C" int se3_debug_pair_ball_host(const void* q_points, int64_t nq, const 
   SE3_REQUIRE(q_points && s_points && transform && counts && total, SE3_ERR_INVALID_ARG, "debug_pair_ball_host: null pointer");
   SE3_REQUIRE(nq >= 0 && ns >= 0 && ns < (1ll << 31) && capacity >= 0 && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,
               "debug_pair_ball_host: nq %lld, ns %lld, capacity %lld, elem %d", (long long)nq, (long long)ns, (long long)capacity, elem);
-  SE3_REQUIRE(isfinite(radius) && radius >= 0.0, SE3_ERR_INVALID_ARG, "debug_pair_ball_host: radius %g", radius);
+  SE3_REQUIRE(pg_radius_ok(radius), SE3_ERR_INVALID_ARG, "debug_pair_ball_host: radius %g", radius);
   SE3_REQUIRE(finite_transforms(transform, 1), SE3_ERR_INVALID_ARG, "debug_pair_ball_host: non-finite transform");
-  HostGrid H(s_points, ns, elem, transform, radius);
+  PairHostGrid H(s_points, ns, elem, transform, radius);
   const PairGridView g = H.G.view();
   const double r2 = radius * radius;
   int64_t run = 0;
   for (int64_t i = 0; i < nq; i++) {
-    const double qv[3] = {pg_load(q_points, elem, 3 * i), pg_load(q_points, elem, 3 * i + 1), pg_load(q_points, elem, 3 * i + 2)};
+    double qv[3];
+    pg_load3(q_points, elem, i, qv);
     counts[i] = pg_ball_count(g, 0, qv, radius, r2);
     if (out && run + counts[i] <= capacity) pg_ball_fill(g, 0, qv, radius, r2, i, out + 2 * run, counts[i]);
     run += counts[i];

@@ -1,28 +1,29 @@
-// Uniform float64 grid over the TRANSFORMED support cloud of each pair of a stacked call, and the search core of csrc/pair_geometry.hip.
+// Uniform float64 grid over the TRANSFORMED support cloud of each pair of a stacked call, and the search core that every tool on it shares:
+// csrc/pair_geometry.hip (which also owns the device build, se3_pair_grid_build), knn_normals.hip, icp.hip, keypoint_nms.hip and fpfh.hip.
 //
 // The grid is only an accelerator: every answer is defined by the arithmetic contract in pair_geometry.hip (transform by the documented fma
 // chain, d^2 = (dx dx + dy dy) + dz dz unfused, strict tests, the lowest index among equal distances), and the walks below visit every
 // cell that can hold a point passing the test.
 //
-// The cell walk, the shell termination rule and the candidate test are __host__ __device__: the kernels run them with one wave per query
-// row (nearest neighbour: `lane` of 64) or one thread per row (ball query), and se3_debug_pair_nearest_neighbor_host /
-// se3_debug_pair_ball_host run the same text on host memory over a grid built by pg_build_host (tests/test_pair_geometry_cpu.py).
+// The header is host/device text alone, included at file scope: templates, __forceinline__ and inline functions.  The cell walk, the shell
+// termination rule and the candidate test are __host__ __device__: the kernels run them with one wave per query row (nearest neighbour, k
+// nearest: `lane` of 64) or one thread per row (ball query), and the se3_debug_*_host entries run the same text on host memory over a
+// PairHostGrid (the CPU tests).  Host side: pg_carve lays a workspace out, pg_grid_call is the one check of an entry that searches a grid.
 //
 // Layout of a grid workspace (pg_carve): meta[P], cells[P][kPairCellCap + 1] (cells[c] .. cells[c + 1] is cell c's run of `sorted`),
 // moved (3 float64 per support point, in input order: the transformed cloud), sorted (3 float64 per point, cell by cell), sorted_idx (the
 // pair-local index of each sorted point).  The order of the points INSIDE a cell follows the arrival of the scatter's integer atomics; no
 // result depends on it: the nearest neighbour reduces on (d^2, index), the ball query sorts each row, counts are integers.
-#pragma once          // (after common.h: the kernels use block_ops.h)
+#pragma once
 #include <math.h>
-#include <stdint.h>
 
 #include <vector>
 
-#define PG_HD __host__ __device__ __forceinline__
+#include "common.h"
+#include "stack_rows.h"
 
 constexpr int kPairGridCap = 64;                                       // cells per axis at most (kGridCap of radius_neighbors.hip)
 constexpr int kPairCellCap = kPairGridCap * kPairGridCap * kPairGridCap;
-constexpr int kPairMaxPairs = 32;                                      // pairs per stacked call (SE3_PAIR_MAX_PAIRS)
 constexpr double kPairSlack = 1e-14;                                   // relative safety of every pruning bound: ~90 float64 roundings
 
 struct PairGridMeta {
@@ -40,21 +41,6 @@ struct PairGridView {
   const int* sorted_idx;        // [ns_total]
 };
 
-// pair p's rows [start[p], start[p + 1]) of a stacked array; passed to kernels by value
-struct PairRows {
-  int64_t start[kPairMaxPairs + 1];
-  int n;
-};
-
-// the pair (or cloud) that owns row i of a stacked array
-PG_HD int pg_pair_of_row(const PairRows& rows, int64_t i) {
-  int p = 0;
-  while (p + 1 < rows.n && i >= rows.start[p + 1]) p++;
-  return p;
-}
-
-PG_HD double pg_load(const void* p, int elem, int64_t i) { return elem ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
-
 // (fma(R[k][2], z, fma(R[k][1], y, R[k][0] * x)) + t[k])_k
 PG_HD void pg_transform(const double* T, double x, double y, double z, double* out) {
 #pragma clang fp contract(off)
@@ -64,6 +50,12 @@ PG_HD void pg_transform(const double* T, double x, double y, double z, double* o
     const double c = __builtin_fma(T[4 * k + 2], z, b);
     out[k] = c + T[4 * k + 3];
   }
+}
+// row `row` of an (n, 3) array, transformed
+PG_HD void pg_transform_row(const double* T, const void* p, int elem, int64_t row, double* out) {
+  double s[3];
+  pg_load3(p, elem, row, s);
+  pg_transform(T, s[0], s[1], s[2], out);
 }
 
 // the candidate test's distance: (dx dx + dy dy) + dz dz, every product and sum rounded on its own
@@ -205,6 +197,16 @@ PG_HD void pg_nearest(const PairGridView& g, int p, const double* q, int lane, i
   *out_j = best_j;
 }
 
+// pg_nearest by one wave per query: the lanes stride the runs, a butterfly makes (d^2, index) the wave's minimum on every lane
+__device__ __forceinline__ void pg_wave_nearest(const PairGridView& g, int p, const double* q, double* out_d2, int* out_j) {
+  pg_nearest(g, p, q, se3_lane(), SE3_WAVE,
+             [](double* best, int* best_j) {
+#pragma unroll
+               for (int o = 32; o > 0; o >>= 1) pg_nearest_update(__shfl_xor(*best, o), __shfl_xor(*best_j, o), best, best_j);
+             },
+             out_d2, out_j);
+}
+
 // ---- ball query -------------------------------------------------------------------------------------------------------------------------
 // hit(j) for every support point of pair `m` with d^2 < r2, in cell order.  The block of cells comes from q -+ r widened by kPairSlack, so
 // a point whose rounded d^2 passes while its true distance is a rounding beyond r is still visited.
@@ -253,123 +255,6 @@ PG_HD int64_t pg_ball_fill(const PairGridView& g, int p, const double* q, double
   });
   return n;
 }
-
-// ---- workspace ----------------------------------------------------------------------------------------------------------------------------
-struct PairGridLayout {
-  PairGridMeta* meta;
-  int* cells;
-  double* moved;
-  double* sorted;
-  int* sorted_idx;
-  PairGridView view() const { return PairGridView{meta, cells, sorted, sorted_idx}; }
-};
-
-inline size_t pg_carve(int64_t ns_total, int num_pairs, char* base, PairGridLayout* L) {
-  Se3Carver c(base);
-  const size_t n = (size_t)(ns_total > 0 ? ns_total : 1), P = (size_t)(num_pairs > 0 ? num_pairs : 1);
-  PairGridLayout l;
-  l.meta = c.take<PairGridMeta>(P);
-  l.cells = c.take<int>(P * (kPairCellCap + 1));
-  l.moved = c.take<double>(3 * n);
-  l.sorted = c.take<double>(3 * n);
-  l.sorted_idx = c.take<int>(n);
-  if (L) *L = l;
-  return c.bytes();
-}
-
-// The grid build on host memory, serial, over a workspace laid out by pg_carve in `base` (the debug entries).
-inline void pg_build_host(const void* s_points, int elem, const PairRows& rows, const double* transforms, double cell_hint, PairGridLayout& G) {
-  for (int p = 0; p < rows.n; p++) {
-    PairGridMeta& m = G.meta[p];
-    const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
-    for (int k = 0; k < 12; k++) m.T[k] = transforms[16 * p + k];
-    m.s_start = s0, m.ns = n;
-    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = s0; i < s0 + n; i++) {
-      pg_transform(m.T, pg_load(s_points, elem, 3 * i), pg_load(s_points, elem, 3 * i + 1), pg_load(s_points, elem, 3 * i + 2), G.moved + 3 * i);
-      for (int d = 0; d < 3; d++) mn[d] = fmin(mn[d], G.moved[3 * i + d]), mx[d] = fmax(mx[d], G.moved[3 * i + d]);
-    }
-    pg_make_grid(mn, mx, n, cell_hint, &m);
-    int* cells = G.cells + (size_t)p * (kPairCellCap + 1);
-    for (int c = 0; c <= m.ncells; c++) cells[c] = 0;
-    for (int64_t i = s0; i < s0 + n; i++) cells[pg_cell_of(m, G.moved + 3 * i)]++;
-    int run = 0;
-    for (int c = 0; c <= m.ncells; c++) {
-      const int v = cells[c];
-      cells[c] = run;
-      run += v;
-    }
-    std::vector<int> cursor(cells, cells + m.ncells);
-    for (int64_t i = s0; i < s0 + n; i++) {
-      const int pos = cursor[(size_t)pg_cell_of(m, G.moved + 3 * i)]++;
-      for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
-      G.sorted_idx[s0 + pos] = (int)(i - s0);
-    }
-  }
-}
-
-#ifdef __HIPCC__
-// ---- the build as kernels, batched over pairs --------------------------------------------------------------------------------------------
-struct PairTransforms {
-  double T[kPairMaxPairs][12];
-};
-
-constexpr int kPairBoundsThreads = 256;
-
-// one workgroup per pair: transform the support into `moved`, exact bounding box, grid geometry
-__global__ __launch_bounds__(kPairBoundsThreads) void pair_grid_bounds_kernel(const void* __restrict__ s, int elem, PairRows rows, PairTransforms tf,
-                                                                double cell_hint, PairGridLayout G) {
-  __shared__ double sh[kPairBoundsThreads / 64];
-  const int p = blockIdx.x;
-  const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
-  double T[12];
-  for (int k = 0; k < 12; k++) T[k] = tf.T[p][k];
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int64_t i = s0 + threadIdx.x; i < s0 + n; i += kPairBoundsThreads) {
-    double w[3];
-    pg_transform(T, pg_load(s, elem, 3 * i), pg_load(s, elem, 3 * i + 1), pg_load(s, elem, 3 * i + 2), w);
-    for (int d = 0; d < 3; d++) {
-      G.moved[3 * i + d] = w[d];
-      mn[d] = fmin(mn[d], w[d]);
-      mx[d] = fmax(mx[d], w[d]);
-    }
-  }
-  se3_block_bounds<double, kPairBoundsThreads>(mn, mx, sh);
-  if (threadIdx.x == 0) {
-    PairGridMeta* m = G.meta + p;
-    for (int k = 0; k < 12; k++) m->T[k] = T[k];
-    m->s_start = s0, m->ns = n;
-    pg_make_grid(mn, mx, n, cell_hint, m);
-  }
-}
-
-// cell histogram (the only atomics of the build: integer adds, order-free)
-__global__ __launch_bounds__(256) void pair_grid_count_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= ns_total) return;
-  const int p = pg_pair_of_row(rows, i);
-  atomicAdd(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1);
-}
-
-// one workgroup per pair: counts -> INCLUSIVE ends (the scatter counts each end down to its cell's start); cells[ncells] = ns
-__global__ __launch_bounds__(1024) void pair_grid_scan_kernel(PairGridLayout G) {
-  __shared__ int sh[1024];
-  const int n = G.meta[blockIdx.x].ncells;
-  int* a = G.cells + (size_t)blockIdx.x * (kPairCellCap + 1);
-  const int total = se3_block_scan<kSe3ScanInclusive>(a, n, sh);
-  if (threadIdx.x == 0) a[n] = total;
-}
-
-__global__ __launch_bounds__(256) void pair_grid_scatter_kernel(PairRows rows, int64_t ns_total, PairGridLayout G) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= ns_total) return;
-  const int p = pg_pair_of_row(rows, i);
-  const int64_t s0 = rows.start[p];
-  const int pos = atomicSub(&G.cells[(size_t)p * (kPairCellCap + 1) + pg_cell_of(G.meta[p], G.moved + 3 * i)], 1) - 1;
-  for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
-  G.sorted_idx[s0 + pos] = (int)(i - s0);
-}
-#endif  // __HIPCC__
 
 // ---- k nearest neighbours (csrc/knn_normals.hip) ---------------------------------------------------------------------------------------------
 // The k support points of pair `m` with the smallest d^2 = pg_dist2, ascending by (d^2, index): among equal distances the lower index comes
@@ -427,14 +312,93 @@ struct PairKnnSerialList {
   }
 };
 
-// host-side offsets -> PairRows; false unless 0 = offsets[0] <= offsets[1] <= ...
-inline bool pg_fill_rows(PairRows* rows, const int64_t* offsets, int num_pairs) {
-  rows->n = num_pairs;
-  if (offsets[0] != 0) return false;
-  for (int p = 0; p <= num_pairs; p++) {
-    rows->start[p] = offsets[p];
-    if (p > 0 && offsets[p] < offsets[p - 1]) return false;
-  }
-  for (int p = num_pairs + 1; p <= kPairMaxPairs; p++) rows->start[p] = offsets[num_pairs];
-  return true;
+// ---- host side: the workspace, the entry check, the serial build ------------------------------------------------------------------------------
+struct PairGridLayout {
+  PairGridMeta* meta;
+  int* cells;
+  double* moved;
+  double* sorted;
+  int* sorted_idx;
+  PairGridView view() const { return PairGridView{meta, cells, sorted, sorted_idx}; }
+};
+
+inline size_t pg_carve(int64_t ns_total, int num_pairs, char* base, PairGridLayout* L) {
+  Se3Carver c(base);
+  const size_t n = (size_t)(ns_total > 0 ? ns_total : 1), P = (size_t)(num_pairs > 0 ? num_pairs : 1);
+  PairGridLayout l;
+  l.meta = c.take<PairGridMeta>(P);
+  l.cells = c.take<int>(P * (kPairCellCap + 1));
+  l.moved = c.take<double>(3 * n);
+  l.sorted = c.take<double>(3 * n);
+  l.sorted_idx = c.take<int>(n);
+  if (L) *L = l;
+  return c.bytes();
 }
+
+// What an entry that searches a built grid has after its checks: the rows of the stacked query, the grid, the number of query rows.
+struct PairGridCall {
+  PairRows rows;
+  PairGridLayout G;
+  int64_t n_total;
+};
+
+// The entry check of such a call, in this order: pointers (`pointers`: the entry's others are there), the pair count with ns_total and
+// elem, the offsets, the grid workspace's size, fewer than max_rows query rows.  `name` is the entry's, `unit` its word for a pair.  An
+// entry that words one of these refusals differently makes that check itself first; its other conditions are its own.
+inline int pg_grid_call(const char* name, const char* unit, bool pointers, const void* grid_workspace, size_t workspace_bytes, int64_t ns_total,
+                        int elem, const int64_t* offsets_host, int num_pairs, int64_t max_rows, PairGridCall* out) {
+  SE3_REQUIRE(pointers && grid_workspace && offsets_host, SE3_ERR_INVALID_ARG, "%s: null pointer", name);
+  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && ns_total >= 0 && (elem == 0 || elem == 1), SE3_ERR_INVALID_ARG,
+              "%s: %d %s (at most %d), ns_total %lld, elem %d", name, num_pairs, unit, kPairMaxPairs, (long long)ns_total, elem);
+  SE3_REQUIRE(pg_fill_rows(&out->rows, offsets_host, num_pairs), SE3_ERR_INVALID_ARG, "%s: offsets must start at 0 and not decrease", name);
+  SE3_REQUIRE(pg_carve(ns_total, num_pairs, (char*)grid_workspace, &out->G) <= workspace_bytes, SE3_ERR_WORKSPACE,
+              "%s: grid workspace of %zu bytes is too small", name, workspace_bytes);
+  out->n_total = out->rows.start[num_pairs];
+  SE3_REQUIRE(out->n_total < max_rows, SE3_ERR_UNSUPPORTED, "%s: %lld query rows in one call", name, (long long)out->n_total);
+  return SE3_OK;
+}
+
+inline bool pg_radius_ok(double radius) { return isfinite(radius) && radius >= 0.0; }
+
+// The grid build on host memory, serial, over a workspace laid out by pg_carve in `base` (the debug entries).
+inline void pg_build_host(const void* s_points, int elem, const PairRows& rows, const double* transforms, double cell_hint, PairGridLayout& G) {
+  for (int p = 0; p < rows.n; p++) {
+    PairGridMeta& m = G.meta[p];
+    const int64_t s0 = rows.start[p], n = rows.start[p + 1] - s0;
+    for (int k = 0; k < 12; k++) m.T[k] = transforms[16 * p + k];
+    m.s_start = s0, m.ns = n;
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = s0; i < s0 + n; i++) {
+      pg_transform_row(m.T, s_points, elem, i, G.moved + 3 * i);
+      for (int d = 0; d < 3; d++) mn[d] = fmin(mn[d], G.moved[3 * i + d]), mx[d] = fmax(mx[d], G.moved[3 * i + d]);
+    }
+    pg_make_grid(mn, mx, n, cell_hint, &m);
+    int* cells = G.cells + (size_t)p * (kPairCellCap + 1);
+    for (int c = 0; c <= m.ncells; c++) cells[c] = 0;
+    for (int64_t i = s0; i < s0 + n; i++) cells[pg_cell_of(m, G.moved + 3 * i)]++;
+    int run = 0;
+    for (int c = 0; c <= m.ncells; c++) {
+      const int v = cells[c];
+      cells[c] = run;
+      run += v;
+    }
+    std::vector<int> cursor(cells, cells + m.ncells);
+    for (int64_t i = s0; i < s0 + n; i++) {
+      const int pos = cursor[(size_t)pg_cell_of(m, G.moved + 3 * i)]++;
+      for (int d = 0; d < 3; d++) G.sorted[3 * (s0 + pos) + d] = G.moved[3 * i + d];
+      G.sorted_idx[s0 + pos] = (int)(i - s0);
+    }
+  }
+}
+
+// One cloud's grid on host memory (the debug entries): `transform` (4, 4) row-major, or NULL for the identity.
+struct PairHostGrid {
+  std::vector<char> mem;
+  PairGridLayout G;
+  PairHostGrid(const void* points, int64_t n, int elem, const double* transform, double cell_hint) : mem(pg_carve(n, 1, nullptr, nullptr)) {
+    pg_carve(n, 1, mem.data(), &G);
+    const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    pg_build_host(points, elem, pg_single_rows(n), transform ? transform : eye, cell_hint, G);
+  }
+  PairHostGrid(const PairHostGrid&) = delete;              // (G points into mem)
+};

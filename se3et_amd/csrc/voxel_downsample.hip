@@ -31,9 +31,9 @@
 #include <vector>
 
 #include "common.h"
+#include "stack_rows.h"
 
 namespace {
-#include "pair_grid.h"          // (inside the namespace: the grid kernels the header defines stay local to this file; csrc/pair_geometry.hip owns the build)
 
 constexpr int kVoxelThreads = 256;
 constexpr int kVoxelSerialMax = 64;                   // members that one thread orders; larger voxels are ordered by a workgroup
@@ -137,7 +137,8 @@ __global__ __launch_bounds__(kVoxelThreads) void voxel_insert_kernel(const void*
   if (!L.meta[c].ok) return;
   const int64_t s0 = rows.start[c], base = 2 * s0 + c;
   const unsigned long long cap = 2ull * (unsigned long long)(rows.start[c + 1] - s0) + 1ull;
-  const double p[3] = {pg_load(pts, elem, 3 * i), pg_load(pts, elem, 3 * i + 1), pg_load(pts, elem, 3 * i + 2)};
+  double p[3];
+  pg_load3(pts, elem, i, p);
   const unsigned long long key = vd_key(p, L.meta[c].org, voxel_size);
   unsigned long long h = ((key * 0x9E3779B97F4A7C15ull) >> 20) % cap;
   for (unsigned long long probe = 0; probe < cap; probe++) {             // (the table has more slots than the cloud has points: it ends)
@@ -335,7 +336,8 @@ extern "C" int se3_debug_voxel_downsample_host(const void* points, int64_t n, in
   std::unordered_map<unsigned long long, int> rank;
   std::vector<std::vector<int>> members;
   for (int64_t i = 0; i < n; i++) {
-    const double p[3] = {pg_load(points, elem, 3 * i), pg_load(points, elem, 3 * i + 1), pg_load(points, elem, 3 * i + 2)};
+    double p[3];
+    pg_load3(points, elem, i, p);
     const auto it = rank.emplace(vd_key(p, org, voxel_size), (int)members.size());
     if (it.second) members.emplace_back();
     members[(size_t)it.first->second].push_back((int)i);
