@@ -40,8 +40,8 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
   return ((unsigned long long)hi << 32) | lo;
 }
 // ascending bitonic sort of one 64-bit key per lane over the wave (21 compare-exchange steps)
-__device__ __forceinline__ unsigned long long wave_sort64(unsigned long long v) {
-  const int lane = threadIdx.x & 63;
+// (lane: the caller's lane number, see the drain of radius_grid_search_kernel)
+__device__ __forceinline__ unsigned long long wave_sort64(unsigned long long v, int lane) {
 #pragma unroll
   for (int k = 2; k <= 64; k <<= 1) {
 #pragma unroll
@@ -56,8 +56,7 @@ __device__ __forceinline__ unsigned long long wave_sort64(unsigned long long v) 
   return v;
 }
 // the 64 smallest of two ascending 64-key lists, ascending
-__device__ __forceinline__ unsigned long long wave_merge_lower(unsigned long long a, unsigned long long b) {
-  const int lane = threadIdx.x & 63;
+__device__ __forceinline__ unsigned long long wave_merge_lower(unsigned long long a, unsigned long long b, int lane) {
   const unsigned lo = __shfl((unsigned)(b & 0xffffffffull), 63 - lane), hi = __shfl((unsigned)(b >> 32), 63 - lane);
   const unsigned long long br = ((unsigned long long)hi << 32) | lo;        // b reversed: min(a, reverse(b)) is bitonic
   unsigned long long v = a < br ? a : br;
@@ -221,6 +220,7 @@ extern "C" int se3_radius_neighbors(const float* q_points, int64_t nq, const flo
 namespace {
 
 constexpr int kGridCap = 64;                       // cells per axis at most
+constexpr int kGridSearchMaxQPW = 8;               // queries one wave of the grid search takes, one after the other, at most
 constexpr int kCellCap = kGridCap * kGridCap * kGridCap;
 
 struct GridMeta {
@@ -261,6 +261,21 @@ __device__ __forceinline__ int query_cell(float v, float org, float inv_cell, in
   return (int)fminf(fmaxf(floorf((v - org) * inv_cell), -2.f), (float)(dim + 1));
 }
 
+// zeroes p[0, n) with the whole workgroup: single words up to the first 16-byte boundary and behind the last, 16-byte stores between
+__device__ __forceinline__ void block_zero_ints(int* p, int n) {
+  int head = (int)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2;
+  head = head < n ? head : n;
+  const int body = (n - head) >> 2;
+  int4* p4 = (int4*)(p + head);
+  for (int i = threadIdx.x; i < body; i += blockDim.x) p4[i] = make_int4(0, 0, 0, 0);
+  const int rest = n - head - 4 * body;                  // < 4
+  if ((int)threadIdx.x < head) p[threadIdx.x] = 0;
+  if ((int)threadIdx.x < rest) p[head + 4 * body + threadIdx.x] = 0;
+}
+
+// One workgroup per cloud: the bounding box, from it the cloud's GridMeta, and then the zeros the counting sort starts from -- cell_start[0, ncells]
+// and cell_fill[0, ncells) of THIS cloud and nothing else.  The workspace is uninitialised memory and a grid of this project has 6^3 .. 48^3
+// of the kCellCap cells, so no kernel may read a cell word at or beyond ncells (cell_start[ncells] itself is the scan's total).
 __global__ __launch_bounds__(1024) void grid_bounds_kernel(const float* __restrict__ s, BatchTable bt, float radius,
                                                            GridLayout G) {
   __shared__ float sh[16];
@@ -275,22 +290,23 @@ __global__ __launch_bounds__(1024) void grid_bounds_kernel(const float* __restri
       mx[d] = fmaxf(mx[d], v);
     }
   se3_block_bounds<float, 1024>(mn, mx, sh);
-  if (threadIdx.x == 0) {
-    GridMeta m;
-    float ext = 0.f;
-    for (int d = 0; d < 3; d++) ext = fmaxf(ext, mx[d] - mn[d]);
-    float cell = fmaxf(radius, ext / (float)(kGridCap - 1));
-    cell = fmaxf(cell, 1e-20f) * 1.0001f;          // strictly larger than the radius: the 3x3x3 block always covers the ball
-    m.inv_cell = 1.0f / cell;
-    m.ncells = 1;
-    for (int d = 0; d < 3; d++) {
-      m.org[d] = n > 0 ? mn[d] : 0.f;
-      int dim = n > 0 ? (int)floorf((mx[d] - mn[d]) * m.inv_cell) + 1 : 1;
-      m.dim[d] = dim < 1 ? 1 : (dim > kGridCap ? kGridCap : dim);
-      m.ncells *= m.dim[d];
-    }
-    G.meta[b] = m;
+  // (every thread holds the workgroup's box: all of them work out the same meta, thread 0 stores it)
+  GridMeta m;
+  float ext = 0.f;
+  for (int d = 0; d < 3; d++) ext = fmaxf(ext, mx[d] - mn[d]);
+  float cell = fmaxf(radius, ext / (float)(kGridCap - 1));
+  cell = fmaxf(cell, 1e-20f) * 1.0001f;          // strictly larger than the radius: the 3x3x3 block always covers the ball
+  m.inv_cell = 1.0f / cell;
+  m.ncells = 1;
+  for (int d = 0; d < 3; d++) {
+    m.org[d] = n > 0 ? mn[d] : 0.f;
+    int dim = n > 0 ? (int)floorf((mx[d] - mn[d]) * m.inv_cell) + 1 : 1;
+    m.dim[d] = dim < 1 ? 1 : (dim > kGridCap ? kGridCap : dim);
+    m.ncells *= m.dim[d];
   }
+  if (threadIdx.x == 0) G.meta[b] = m;
+  block_zero_ints(G.cell_start + (size_t)b * (kCellCap + 1), m.ncells + 1);
+  block_zero_ints(G.cell_fill + (size_t)b * kCellCap, m.ncells);
 }
 
 __global__ void grid_count_kernel(const float* __restrict__ s, BatchTable bt, GridLayout G) {
@@ -325,86 +341,127 @@ __global__ void grid_scatter_kernel(const float* __restrict__ s, BatchTable bt, 
   G.sorted[bt.s_start[b] + pos] = make_float4(s[3 * g], s[3 * g + 1], s[3 * g + 2], __int_as_float((int)g));
 }
 
-// one wavefront per query; the nine (y, z) rows of the 3x3x3 cell block are contiguous runs of `sorted`
+// Ascending order of the `fill` (< 64) distinct keys in stage[0, fill), one per lane, the lanes from `fill` on holding the sentinel ~0 -- what
+// wave_sort64 makes of them, by counting instead of compare-exchange stages: a key's place in the order is the number of staged keys below
+// it (the keys are distinct: the support index is the low word).  Every lane counts against all staged keys, read eight to a wait as broadcast
+// LDS reads; the keys then go to their places through the free half of the staging block, stage[64, 128).  At the 8..35 hits of a 3DMatch
+// pyramid that is 1..5 rounds of 8 compares in place of the 28 compare-exchange stages of sort + merge, each an LDS round trip.
+__device__ __forceinline__ unsigned long long wave_rank_sort(unsigned long long* stage, int fill) {
+  const int lane = threadIdx.x & 63;
+  if (lane >= fill) stage[lane] = ~0ull;                   // stale slots compare above every key
+  const unsigned long long key = stage[lane];
+  int rank = 0;
+  for (int i = 0; i < fill; i += 8) {
+    unsigned long long o[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) o[j] = stage[i + j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) rank += o[j] < key ? 1 : 0;
+  }
+  if (lane < fill) stage[64 + rank] = key;
+  return lane < fill ? stage[64 + lane] : ~0ull;
+}
+
+// One wavefront per query, `qpw` queries per wavefront one after the other (query j of wave w of a workgroup: first + 4 j + w); the nine
+// (y, z) rows of the 3x3x3 cell block are contiguous runs of `sorted`.
 __global__ __launch_bounds__(256) void radius_grid_search_kernel(const float* __restrict__ q, BatchTable bt, GridLayout G,
-                                                                 int64_t ns_total, float r2, int limit,
+                                                                 int64_t ns_total, float r2, int limit, int qpw,
                                                                  int64_t* __restrict__ out, int32_t* __restrict__ max_count,
                                                                  int32_t* __restrict__ tie_rows, int32_t* __restrict__ tie_count) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63;
-  const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (qi >= bt.q_count[b]) return;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // (uniform: the query comes as scalar loads, like the GridMeta)
+  const int64_t qn = bt.q_count[b], first = (int64_t)blockIdx.x * 4 * qpw;
+  if (first >= qn) return;                                                 // (the whole workgroup)
+  // in-radius candidates are compacted into a wave-private LDS buffer.  A query that ends with fewer than 64 of them (every query of a
+  // 3DMatch pyramid) orders them once, by rank (wave_rank_sort); whenever 64 have accumulated they are sorted across the wave (bitonic) and
+  // merged into the running 64 smallest -- ~230 instructions per 64 hits instead of ~15 per hit for the one-at-a-time sorted insertion
+  __shared__ unsigned long long stage_s[4][128];
+  __shared__ int wave_max_s[4];
+  unsigned long long* stage = stage_s[wave];
   const GridMeta m = G.meta[b];
-  const int64_t gq = bt.q_start[b] + qi;
-  const float qx = q[3 * gq], qy = q[3 * gq + 1], qz = q[3 * gq + 2];
-  const int cx = query_cell(qx, m.org[0], m.inv_cell, m.dim[0]), cy = query_cell(qy, m.org[1], m.inv_cell, m.dim[1]),
-            cz = query_cell(qz, m.org[2], m.inv_cell, m.dim[2]);
-  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, m.dim[0] - 1);
   const int* cs = G.cell_start + (size_t)b * (kCellCap + 1);
   const float4* pts = G.sorted + bt.s_start[b];
-  unsigned long long best = ~0ull;
-  int count = 0;
-  // in-radius candidates are compacted into a wave-private LDS buffer; whenever 64 have accumulated they are sorted across the
-  // wave (bitonic) and merged into the running 64 smallest -- ~230 instructions per 64 hits instead of ~15 per hit for the
-  // one-at-a-time sorted insertion
-  __shared__ unsigned long long stage_s[4][128];
-  unsigned long long* stage = stage_s[threadIdx.x >> 6];
-  int fill = 0;
-  // lanes 0..8 fetch the [begin, end) run of one (y, z) row each (all 18 loads in flight at once); the nine runs are then
-  // walked as ONE flat candidate list, 64 candidates per step
-  int beg = 0, len = 0;
-  if (lane < 9 && x0 <= x1) {
-    const int z = cz + lane / 3 - 1, y = cy + lane % 3 - 1;
-    if (z >= 0 && z < m.dim[2] && y >= 0 && y < m.dim[1]) {
-      const int rowc = m.dim[0] * (y + m.dim[1] * z);
-      beg = cs[rowc + x0];
-      len = cs[rowc + x1 + 1] - beg;
+  int wave_max = 0;
+  for (int j = 0; j < qpw; j++) {
+    const int64_t qi = first + (int64_t)j * 4 + wave;                      // (the same for all lanes of the wave)
+    if (qi >= qn) break;
+    const int64_t gq = bt.q_start[b] + qi;
+    const float qx = q[3 * gq], qy = q[3 * gq + 1], qz = q[3 * gq + 2];
+    const int cx = query_cell(qx, m.org[0], m.inv_cell, m.dim[0]), cy = query_cell(qy, m.org[1], m.inv_cell, m.dim[1]),
+              cz = query_cell(qz, m.org[2], m.inv_cell, m.dim[2]);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, m.dim[0] - 1);
+    unsigned long long best = ~0ull;
+    int count = 0, fill = 0;
+    // lanes 0..8 fetch the [begin, end) run of one (y, z) row each (all 18 loads in flight at once); the nine runs are then
+    // walked as ONE flat candidate list, 64 candidates per step
+    int beg = 0, len = 0;
+    if (lane < 9 && x0 <= x1) {
+      const int z = cz + lane / 3 - 1, y = cy + lane % 3 - 1;
+      if (z >= 0 && z < m.dim[2] && y >= 0 && y < m.dim[1]) {
+        const int rowc = m.dim[0] * (y + m.dim[1] * z);
+        beg = cs[rowc + x0];
+        len = cs[rowc + x1 + 1] - beg;
+      }
     }
-  }
-  int rb[9], ro[9], total = 0;
+    int ro[9], rd[9], total = 0;
 #pragma unroll
-  for (int r = 0; r < 9; r++) {
-    rb[r] = __builtin_amdgcn_readlane(beg, r);
-    ro[r] = total;                                       // exclusive offset of run r in the flat list
-    total += __builtin_amdgcn_readlane(len, r);
-  }
-  for (int base = 0; base < total; base += 64) {
-    const int t = base + lane;
-    const bool valid = t < total;
-    int p = 0;
+    for (int r = 0; r < 9; r++) {
+      ro[r] = total;                                       // exclusive offset of run r in the flat list
+      rd[r] = __builtin_amdgcn_readlane(beg, r) - total;   // flat position -> position in `sorted`, within run r
+      total += __builtin_amdgcn_readlane(len, r);
+    }
+    for (int base = 0; base < total; base += 64) {
+      const int t = base + lane;
+      const bool valid = t < total;
+      int d = 0;
 #pragma unroll
-    for (int r = 0; r < 9; r++) p = (t >= ro[r]) ? rb[r] + (t - ro[r]) : p;
-    const float4 c = valid ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float dx = __fsub_rn(qx, c.x), dyv = __fsub_rn(qy, c.y), dzv = __fsub_rn(qz, c.z);
-    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dyv, dyv)), __fmul_rn(dzv, dzv));
-    const bool hit = valid && (d2 < r2);
-    const unsigned long long mk = __ballot(hit);
-    if (mk == 0ull) continue;
-    const int nh = __popcll(mk);
-    count += nh;
-    if (hit) {
-      const int rank = __popcll(mk & ((1ull << lane) - 1ull));
-      stage[fill + rank] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(c.w);
+      for (int r = 0; r < 9; r++) d = (t >= ro[r]) ? rd[r] : d;
+      const float4 c = pts[valid ? t + d : 0];             // (past the end of the list: point 0, which exists as total > 0; masked by `valid`)
+      const float dx = __fsub_rn(qx, c.x), dyv = __fsub_rn(qy, c.y), dzv = __fsub_rn(qz, c.z);
+      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dyv, dyv)), __fmul_rn(dzv, dzv));
+      const bool hit = valid && (d2 < r2);
+      const unsigned long long mk = __ballot(hit);
+      if (mk == 0ull) continue;
+      const int nh = __popcll(mk);
+      count += nh;
+      if (hit) {
+        const int rank = __popcll(mk & ((1ull << lane) - 1ull));
+        stage[fill + rank] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(c.w);
+      }
+      fill += nh;
+      if (fill >= 64) {
+        // The drain sees the lane number through an empty asm, so that hipcc cannot hoist the sort's lane masks out of this branch, which no
+        // query of a 3DMatch pyramid enters.  Hoisted (this line removed, ISA of both forms read), they sit in SGPR pairs across the
+        // whole query loop: 106 SGPRs instead of 97, 7 waves per SIMD instead of 8, 43 more instructions per wave and 8 more per query.
+        int dl = lane;
+        asm volatile("" : "+v"(dl));
+        const unsigned long long k = wave_sort64(stage[dl], dl);
+        best = wave_merge_lower(best, k, dl);
+        const int rem = fill - 64;
+        const unsigned long long mv = dl < rem ? stage[64 + dl] : 0ull;
+        if (dl < rem) stage[dl] = mv;
+        fill = rem;
+      }
     }
-    fill += nh;
-    if (fill >= 64) {
-      const unsigned long long k = wave_sort64(stage[lane]);
-      best = wave_merge_lower(best, k);
-      const int rem = fill - 64;
-      const unsigned long long mv = lane < rem ? stage[64 + lane] : 0ull;
-      if (lane < rem) stage[lane] = mv;
-      fill = rem;
+    if (fill > 0) {
+      const unsigned long long k = wave_rank_sort(stage, fill);
+      best = (count == fill) ? k : wave_merge_lower(best, k, lane);    // nothing was drained: `best` is all sentinels, k is the list
     }
+    if (lane < limit) out[gq * limit + lane] = (best != ~0ull) ? (int64_t)(unsigned)(best & 0xffffffffull) : ns_total;
+    wave_max = max(wave_max, count);
+    if (tie_rows != nullptr) flag_tie_row(best, count, limit, gq, tie_rows, tie_count);
   }
-  if (fill > 0) {
-    const unsigned long long k = wave_sort64(lane < fill ? stage[lane] : ~0ull);
-    best = wave_merge_lower(best, k);
+  // The largest count reaches max_count[b] once per WORKGROUP.  The counters of all clouds lie in one cache line; the read that filters the
+  // atomics goes past the caches (the atomics of the other XCDs have to be seen: a cached copy stays behind and lets almost every atomic
+  // through), and such reads of one line serialise at ~1.5 ns each -- with one per query that was 60 % of this kernel's time.  The running
+  // maximum is monotonic, so a stale read only lets an atomic through that changes nothing.
+  if (lane == 0) wave_max_s[wave] = wave_max;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int wg_max = max(max(wave_max_s[0], wave_max_s[1]), max(wave_max_s[2], wave_max_s[3]));
+    if (wg_max > __atomic_load_n(max_count + b, __ATOMIC_RELAXED)) atomicMax(max_count + b, wg_max);
   }
-  if (lane < limit) out[gq * limit + lane] = (best != ~0ull) ? (int64_t)(unsigned)(best & 0xffffffffull) : ns_total;
-  // same-line atomics serialise in the L2 (~7 ns each: 80 000 queries = 0.5 ms); the running maximum is monotonic, so a plain
-  // (possibly stale) read filters almost all of them
-  if (lane == 0 && count > __atomic_load_n(max_count + b, __ATOMIC_RELAXED)) atomicMax(max_count + b, count);
-  if (tie_rows != nullptr) flag_tie_row(best, count, limit, gq, tie_rows, tie_count);
 }
 
 int fill_batch_table(BatchTable* bt, const int64_t* q_len, const int64_t* s_len, int batch, int64_t nq, int64_t ns,
@@ -444,12 +501,7 @@ extern "C" int se3_radius_grid_build(const float* s_points, int64_t ns, const in
   SE3_REQUIRE(grid_carve(ns, batch, (char*)workspace, &G) <= workspace_bytes, SE3_ERR_WORKSPACE,
               "radius_grid_build: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  // cell_start and cell_fill are neighbours in the workspace (grid_carve): one fill over both (and the alignment gap between them)
-  const size_t span = (size_t)((char*)(G.cell_fill + (size_t)batch * kCellCap) - (char*)G.cell_start);
-  if ((char*)G.cell_fill < (char*)G.cell_start || hipMemsetAsync(G.cell_start, 0, span, st) != hipSuccess) {
-    se3_set_error("radius_grid_build: memset failed");
-    return SE3_ERR_LAUNCH;
-  }
+  // (no fill of the workspace: grid_bounds_kernel clears the cell words each cloud's grid has)
   grid_bounds_kernel<<<batch, 1024, 0, st>>>(s_points, bt, radius, G);
   if (smax > 0) {
     dim3 gp((unsigned)se3_cdiv(smax, 256), (unsigned)batch);
@@ -484,8 +536,12 @@ extern "C" int se3_radius_neighbors_grid_ties(const float* q_points, int64_t nq,
     return SE3_ERR_LAUNCH;
   }
   if (nq == 0) return SE3_OK;
-  dim3 grid((unsigned)se3_cdiv(qmax, 4), (unsigned)batch);
-  radius_grid_search_kernel<<<grid, 256, 0, st>>>(q_points, bt, G, ns, radius * radius, limit, neighbors, max_count, tie_rows, tie_count);
+  // 1 .. kGridSearchMaxQPW queries per wave: about a thousand workgroups per launch up to 32 768 queries, more beyond (the cap: 3 200 and
+  // 5 000 for the 103 455 and 160 000 queries of a stacked 3DMatch pyramid; profiles/radius_select_parent_vs_pr.txt).  It is taken from
+  // the queries of the whole batch, nq; the launch is as wide as the largest cloud needs, qmax, and workgroups past a cloud's end leave at once.
+  const int64_t qpw = nq / 4096 < 1 ? 1 : (nq / 4096 > kGridSearchMaxQPW ? kGridSearchMaxQPW : nq / 4096);
+  dim3 grid((unsigned)se3_cdiv(qmax, 4 * qpw), (unsigned)batch);
+  radius_grid_search_kernel<<<grid, 256, 0, st>>>(q_points, bt, G, ns, radius * radius, limit, (int)qpw, neighbors, max_count, tie_rows, tie_count);
   SE3_CHECK_LAUNCH("radius_neighbors_grid");
   return SE3_OK;
 }
