@@ -45,7 +45,8 @@ struct StackCloud {
   const float* eq;      // (A, N, M, 4) equivariant embedding or null
   int q_start, k_start; // first packed row of the cloud's queries / keys
   int N, M, Mp;         // queries, keys, logits row stride (multiple of 32 >= M)
-  int unit_begin;       // bias kernel: flat index of the cloud's first (row, 32-key unit)
+  int unit_begin;       // bias kernel: flat index of the cloud's first (row, 32-key unit); x6_split_kernel: 1 = the all-padding 16-key block
+                        // behind the cloud's keys holds another cloud's keys and is left to that cloud (x6_mark_shared_tail_blocks)
   long long bias_off;   // float offset of the cloud's (A*H, N, Mp) logits block
 };
 struct Stack {
@@ -987,6 +988,9 @@ __global__ __launch_bounds__(256) void x6_split_kernel(X6SplitArgs p) {
       auto emit = [&](int aa, int b, const float4 (&x)[4], float s) {
         // (the padding keys of the last tile are multiplied by P = 0: they only have to be finite -- whatever the caller's buffer holds
         //  there, they are stored as zeros and never counted)
+        //  A block of padding keys ONLY may be the first block of the next cloud (key starts that are multiples of 16, not of 32): that
+        //  cloud writes all of it, and the zeros stored here would race with its values.
+        if (cl.unit_begin != 0 && 16 * b >= cl.M) return;
         float v[16];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -1050,6 +1054,18 @@ __global__ __launch_bounds__(256) void x6_split_kernel(X6SplitArgs p) {
     }
   }
   count_saturated(sat);
+}
+// The V^T pieces of a cloud cover its padded key range, ceil32(M) columns from its start, in 16-key blocks; the block from ceil16(M) on, if
+// there is one, holds padding only.  Marks the clouds whose padding-only block holds live keys of another cloud (unit_begin = 1, else 0):
+// that cloud writes the whole block (its own padding as zeros), this one must not store zeros over it.  The attention kernels give the
+// block's keys P = 0 for this cloud, whatever finite pieces it holds.
+static void x6_mark_shared_tail_blocks(Stack& S) {
+  for (int c = 0; c < S.n; c++) {
+    const int t0 = S.c[c].k_start + ((S.c[c].M + 15) / 16) * 16, t1 = S.c[c].k_start + ((S.c[c].M + 31) / 32) * 32;
+    S.c[c].unit_begin = 0;
+    for (int o = 0; o < S.n && t0 < t1; o++)
+      if (o != c && S.c[o].k_start < t1 && S.c[o].k_start + S.c[o].M > t0) S.c[c].unit_begin = 1;
+  }
 }
 // sizes of the scale tables behind the pieces (floats); `rows` of keys -> ceil(rows / 8) blocks
 static inline size_t x6_kinv_floats(int A, int C, int64_t k_rows) { return (size_t)A * (size_t)(C / 64 + 1) * (size_t)((k_rows + 7) / 8 + 4); }
@@ -1773,6 +1789,7 @@ static bool launch_attention_x6(AttnArgs& p, void* ws, size_t ws_bytes, hipStrea
   for (int c = 0; c < p.S.n; c++) mmax = p.S.c[c].M > mmax ? p.S.c[c].M : mmax;
   X6SplitArgs sp{};
   sp.S = p.S; sp.A = p.A; sp.C = p.C; sp.H = p.H;
+  x6_mark_shared_tail_blocks(sp.S);
   sp.k = p.k; sp.vt = p.v; sp.k_rs = p.k_rs; sp.v_rs = p.v_rs; sp.k_sa = p.k_sa; sp.v_sa = p.v_sa; sp.k_rows = R;
   sp.outk = wk; sp.outv = wv; sp.kinv = kinv; sp.vinv = vinv;
   sp.q_groups = 0; sp.k_groups = (((mmax + 7) / 8) * p.H + 3) / 4;
@@ -2251,6 +2268,7 @@ extern "C" int se3_cross_eq_stack_x6_fwd(const float* q, const float* k, const f
   }
   X6SplitArgs sp{};
   sp.S = p.S; sp.A = A; sp.C = C; sp.H = H;
+  x6_mark_shared_tail_blocks(sp.S);
   sp.q = q; sp.k = k; sp.vt = vt; sp.q_rs = C; sp.k_rs = C; sp.v_rs = v_row_stride;
   sp.q_sa = q_anchor_stride; sp.k_sa = k_anchor_stride; sp.v_sa = v_anchor_stride; sp.q_rows = q_rows; sp.k_rows = k_rows;
   sp.outq = wq; sp.outk = wk; sp.outv = wv; sp.qinv = qinv; sp.kinv = kinv; sp.vinv = vinv;

@@ -1,5 +1,6 @@
 """GPU parity of single HIP ops (through the C ABI) against the oracle on seeded inputs and against per-op
-inputs/outputs captured from the reference (tests/golden/micro_se3ete.npz, keys op/*)."""
+inputs/outputs captured from the reference (tests/golden/micro_se3ete.npz, keys op/*).  The attention tests below run generic shapes
+at a whole-tensor 1e-4; tests/test_gpu_attention_edges.py holds the same kernels to a float64 twin at their tile edges, per row."""
 import numpy as np
 import pytest
 import torch
