@@ -1004,7 +1004,8 @@ int se3_debug_knn_normals_host(const void* points, int64_t n, int elem, int k, c
                                double* out_covariances);
 
 /* ---- ICP refinement of stacked pairs (csrc/icp.hip, csrc/icp_core.h) ---------------------------------------------------------------------------
- * Open3D's registration_icp, point-to-point (no scale) or point-to-plane, for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64 and
+ * Open3D's registration_icp, point-to-point (no scale) or point-to-plane -- and, through the weighted entries below, its robust loss
+ * kernels and registration_generalized_icp -- for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64 and
  * resident on the device: a call enqueues every evaluation and update and waits for nothing; the contract is the header comment of
  * csrc/icp.hip.  Points and normals are (rows, 3) on the device, float32 (elem 0) or float64 (elem 1), promoted on load; pair p owns rows
  * [src_offsets_host[p], src_offsets_host[p + 1]) of the stacked source (HOST int64, num_pairs + 1 entries from 0).
@@ -1020,7 +1021,29 @@ int se3_debug_knn_normals_host(const void* points, int64_t n, int elem, int k, c
  *   se3_debug_icp_host      the same text for one pair on HOST memory, no GPU, in the same summation order: every pointer a host pointer,
  *                           T0 and out_transform (4, 4).  trace: NULL, or (max_iteration + 1, n) int64 whose row k receives evaluation k's
  *                           correspondence per source row; rows of evaluations not made are left untouched.
- *   se3_debug_icp_sincos_host   the series the point-to-plane update takes sin and cos from, on n HOST values of (-1, 1). */
+ *   se3_debug_icp_sincos_host   the series the point-to-plane update takes sin and cos from, on n HOST values of (-1, 1).
+ *
+ * Robust loss kernels and generalized ICP: the weighted entries.  se3_icp_stack and se3_debug_icp_host keep their signatures and every
+ * output bit; they take no loss and refuse SE3_ICP_GENERALIZED.
+ *   se3_icp_weighted_stack  se3_icp_stack with, in addition: src_normals (stacked source rows, 3) of src_normals_elem, read by
+ *                           SE3_ICP_GENERALIZED alone (NULL otherwise); loss, one of SE3_ICP_LOSS_*; loss_k, the loss's width k (finite,
+ *                           > 0; not read by NONE and L2); gicp_epsilon in (0, 1] (Open3D's default 1e-3; read by GENERALIZED alone).
+ *                           Weights w(r) of a scalar residual r: L2 1; HUBER 1 for |r| <= k, else k / |r|; CAUCHY 1 / (1 + (r / k)^2);
+ *                           GM k / (k + r^2)^2; TUKEY (1 - (r / k)^2)^2 for |r| <= k, else 0 (Open3D's RobustKernel; its L1Loss is not
+ *                           offered: 1 / |r| is unbounded at an exact match, and HUBER covers its use).  NONE runs the instantiation
+ *                           without weight code: for the two modes of se3_icp_stack, that entry's kernels and bits.
+ *                           Point-to-plane: r = (p - q) . n, (sum w J^T J) x = -sum w J^T r, Open3D's TransformationEstimationPointToPlane
+ *                           (kernel).  Point-to-point: r = sqrt(d^2) and a weighted Kabsch (weighted centroids and cross-covariance);
+ *                           Open3D's point-to-point takes no kernel, so this is the project's definition; a weight sum that is not > 0
+ *                           sets SE3_ICP_SINGULAR with the identity update.
+ *                           SE3_ICP_GENERALIZED: Open3D's registration_generalized_icp with covariances I - (1 - eps) n n^T from the unit
+ *                           normals of BOTH clouds (ref_normals and src_normals are required; their signs do not matter): with m = R
+ *                           ns, M = 2 I - (1 - eps)(nt nt^T + m m^T), A = [-[p]_x | I], d = p - q: (sum w A^T M^-1 A) x = -sum w A^T M^-1 d,
+ *                           solved, refused and applied as a point-to-plane step; at least 6 correspondences.  Its loss acts on the
+ *                           Mahalanobis residual sqrt(d^T M^-1 d); Open3D weights the three rows of M^(-1/2) d one by one (the same
+ *                           system under L2).  fitness and rmse stay Euclidean.  A non-finite source normal refuses the pair.
+ *   se3_icp_weighted_workspace_bytes   its workspace (that of se3_icp_stack).
+ *   se3_debug_icp_weighted_host   the same text for one pair on HOST memory, with the trace of se3_debug_icp_host. */
 enum {                             /* (an enum, not limits: se3et_amd/ops.py reads the names and values from this block) */
   SE3_ICP_POINT_TO_POINT = 0,      /* mode */
   SE3_ICP_POINT_TO_PLANE = 1,
@@ -1042,6 +1065,28 @@ int se3_debug_icp_host(const void* src_points, int64_t n, const void* ref_points
                        double relative_rmse, int max_iteration, double* out_transform, double* out_fitness, double* out_rmse,
                        int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace);
 int se3_debug_icp_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos);
+enum se3_icp_option {              /* (a NAMED enum: the binding reads it as a table of its own, beside the limits and the enum above) */
+  SE3_ICP_GENERALIZED = 2,         /* mode, beside SE3_ICP_POINT_TO_POINT and SE3_ICP_POINT_TO_PLANE: the weighted entries alone */
+  SE3_ICP_LOSS_NONE = -1,          /* loss */
+  SE3_ICP_LOSS_L2 = 0,
+  SE3_ICP_LOSS_HUBER = 1,
+  SE3_ICP_LOSS_CAUCHY = 2,
+  SE3_ICP_LOSS_GM = 3,
+  SE3_ICP_LOSS_TUKEY = 4
+};
+size_t se3_icp_weighted_workspace_bytes(int64_t nsrc_total, int num_pairs);
+int se3_icp_weighted_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
+                           const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem, const void* src_normals,
+                           int src_normals_elem, const double* T0, double max_correspondence_distance, int mode, int loss, double loss_k,
+                           double gicp_epsilon, double relative_fitness, double relative_rmse, int max_iteration, double* out_transforms,
+                           double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged, int* out_status,
+                           int64_t* out_correspondences, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_icp_weighted_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
+                                int normals_elem, const void* src_normals, int src_normals_elem, const double* T0,
+                                double max_correspondence_distance, int mode, int loss, double loss_k, double gicp_epsilon,
+                                double relative_fitness, double relative_rmse, int max_iteration, double* out_transform, double* out_fitness,
+                                double* out_rmse, int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences,
+                                int64_t* trace);
 
 /* ---- keypoint selection: radius non-maximum suppression in score order (csrc/keypoint_nms.hip) -------------------------------------------------
  * The loop of the reference's sample_keypoints_with_nms / random_sample_keypoints_with_nms (utils/pointcloud.py:191-248) in an exact parallel

@@ -29,14 +29,24 @@ def _ctype(spelling, proto, ret=False):
     raise RuntimeError('%s: no ctypes type for %r (the binding knows pointers, %s)' % (proto, ' '.join(spelling.split()), ', '.join(_SCALARS)))
 
 
+_ENUMERATOR = r'\b(SE3_\w+)\s*=\s*(-?\d+)\s*(?:,|$)'
+
+
+def read_named_enums(text):
+    """enum name -> {enumerator: value} of every `enum se3_name { SE3_NAME = integer, .. };` of a C header: the option tables that an
+    entry adds beside the limits (ops.ICP_LOSSES).  They are kept apart from read_header's flat constants."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    return {name: {k: int(v) for k, v in re.findall(_ENUMERATOR, body)} for name, body in re.findall(r'\benum\s+(se3_\w+)\s*\{([^}]*)\}', text)}
+
+
 def read_header(text):
     """(signatures, constants) of a C header: name -> (restype, argtypes) of every `ret se3_name(args);`, and its integer `#define SE3_*`s
-    together with the enumerators `SE3_NAME = integer,` of its enums.
+    together with the enumerators `SE3_NAME = integer,` of its anonymous enums.
     A prototype outside the closed type map of _ctype raises: a symbol is never left to ctypes' default int signature."""
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
     constants = {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(SE3_\w+)[ \t]+(-?\d+)[ \t]*$', text, flags=re.M)}
-    for body in re.findall(r'\benum\b[^{;]*\{([^}]*)\}', text):
-        constants.update((k, int(v)) for k, v in re.findall(r'\b(SE3_\w+)\s*=\s*(-?\d+)\s*(?:,|$)', body))
+    for body in re.findall(r'\benum\s*\{([^}]*)\}', text):             # (the anonymous enums; a named one is a table of read_named_enums)
+        constants.update((k, int(v)) for k, v in re.findall(_ENUMERATOR, body))
     text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
     signatures = {}
     for ret, name, params in re.findall(r'([\w\s*]+?)\b(se3_\w+)\s*\(((?:[^()]|\([^()]*\))*)\)\s*;', text):
@@ -52,11 +62,13 @@ def _read():
     if not os.path.exists(HEADER):
         raise RuntimeError('%s is missing: it is the declaration of the C ABI that this binding reads' % HEADER)
     with open(HEADER) as f:
-        return read_header(f.read())
+        text = f.read()
+    return read_header(text) + (read_named_enums(text),)
 
 
-# name -> (restype, argtypes) of every symbol, and the integer limits and enumerators, that include/se3et_hip.h declares: read once per process
-SIGNATURES, CONSTANTS = _read()
+# name -> (restype, argtypes) of every symbol, the integer limits and enumerators, and the named option enums, that include/se3et_hip.h
+# declares: read once per process
+SIGNATURES, CONSTANTS, ENUMS = _read()
 
 _lib = None
 

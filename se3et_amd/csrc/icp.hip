@@ -1,6 +1,6 @@
 // ICP refinement of stacked pairs, resident on the device: Open3D's registration_icp with TransformationEstimationPointToPoint (no
-// scale) or TransformationEstimationPointToPlane, for up to SE3_PAIR_MAX_PAIRS pairs per call and without a host round trip per
-// iteration.  csrc/icp_core.h holds the iteration as __host__ __device__ text, csrc/pair_grid.h the search, csrc/kabsch.h the 3x3 solve;
+// scale) or TransformationEstimationPointToPlane, and its registration_generalized_icp in the normals form, each with or without one of
+// Open3D's robust loss kernels, for up to SE3_PAIR_MAX_PAIRS pairs per call and without a host round trip per iteration.  csrc/icp_core.h holds the iteration as __host__ __device__ text, csrc/pair_grid.h the search, csrc/kabsch.h the 3x3 solve;
 // se3et_amd/icp.py carries the same contract.
 // (SE3_EXACT_FP: the file is built with contraction off, and every contract function fences itself as well.)
 //
@@ -8,7 +8,10 @@
 //   icp_nearest_kernel   (a) one wave per stacked source row: the row moved by its pair's current T, the pair_grid.h nearest-neighbour walk,
 //                        (index, d^2) to the workspace.
 //   icp_step_kernel      (b) one workgroup per pair: fitness, rmse, the convergence test, and for a pair that goes on the fixed-order sums,
-//                        the solve and T <- U T.
+//                        the solve and T <- U T.  <kWeighted, kGeneral>: four instantiations; <false, false> is se3_icp_stack's and holds no
+//                        weight code, so a call without a loss gives the bits it gave before the losses existed.  kGeneral keeps 27 sum
+//                        columns in LDS (27 x 256 doubles = 54 KiB of the 64 KiB a workgroup may declare; one workgroup per pair, so the
+//                        occupancy it costs is of no account) and forms them in ONE pass over the rows: the row's M^-1 is formed once.
 //   A call enqueues init and then (a), (b) max_iteration + 1 times; nothing waits on the host.  Every pair has a `done` word on the
 //   device: the kernels of a converged, stopped or refused pair read it (uniform over the wave / the workgroup) and return.
 //
@@ -37,7 +40,27 @@
 //   Sums.  No float atomics.  Every sum over a pair's rows is formed by lane l of 256 adding rows l, l + 256, .. serially and a fixed
 //     tree over the lanes (icp_sum), so it depends on the pair's row count alone: results are bit-identical from run to run, for a pair
 //     alone and anywhere in a batch, and between the device and se3_debug_icp_host.
-//   No robust loss kernels, no captured graphs.
+//   Loss kernels (se3_icp_weighted_stack; se3_icp_stack has none).  Open3D's RobustKernel weights of a scalar residual r, k > 0:
+//     l2: 1;  huber: 1 for |r| <= k, else k / |r|;  cauchy: 1 / (1 + (r / k)^2);  gm: k / (k + r^2)^2;  tukey: (1 - (r / k)^2)^2 for
+//     |r| <= k, else 0.  Every weight is continuous at its branch.  Open3D's L1Loss is not offered: its weight 1 / |r| is unbounded at an
+//     exact match, and huber covers its use.  Iteratively reweighted least squares, the weights from the current evaluation; the
+//     evaluation itself (correspondences, fitness, inlier_rmse), the loop, the too-few counts (which count correspondences, not weights)
+//     and the status bits are untouched.
+//     Point-to-plane: w_i = w(r_i), (sum w_i J_i^T J_i) x = -sum w_i J_i^T r_i: Open3D's TransformationEstimationPointToPlane(kernel).
+//       Weights that leave the system rank-deficient are caught by the pivot test.
+//     Point-to-point: w_i = w(sqrt(d_i^2)) and the weighted Kabsch pc = sum w p / W, qc = sum w q / W, H = sum w (p - pc)(q - qc)^T,
+//       W = sum w.  A W that is not > 0 is SE3_ICP_SINGULAR with the identity update (tukey with every correspondence beyond k).
+//       Open3D's legacy point-to-point takes no kernel: this is the project's definition.
+//   Generalized ICP (SE3_ICP_GENERALIZED).  Open3D's registration_generalized_icp with the covariances of its normals form: a point with
+//     unit normal n has C = I - (1 - eps) n n^T (= R diag(eps, 1, 1) R^T with n the first column of R), eps = gicp_epsilon in (0, 1],
+//     Open3D's default 1e-3.  It needs the unit normals of BOTH clouds and nothing else, and does not depend on a normal's sign.  For a
+//     correspondence under T = [R | t]: p the moved source row, q its reference row, nt the normal of q, m = R ns the source normal turned
+//     by T, d = p - q, M = 2 I - (1 - eps)(nt nt^T + m m^T) (eigenvalues >= 2 eps) inverted by its cofactors, A = [-[p]_x | I];
+//     (sum w A^T M^-1 A) x = -sum w A^T M^-1 d, then the solve, the 1 rad refusal and the update matrix of point-to-plane.  The too-few
+//     count is 6; fitness and inlier_rmse stay Euclidean, as Open3D's result fields are.  A non-finite source normal refuses the pair.
+//     The loss acts on the Mahalanobis residual: w = w(sqrt(d^T M^-1 d)).  Open3D weights the three rows of M^(-1/2) d one by one, which
+//     needs a matrix square root; with l2 the two systems are the same in exact arithmetic.
+//   No coloured ICP, no captured graphs.
 #include <math.h>
 
 #include <vector>
@@ -73,6 +96,8 @@ struct IcpCall {
   const double* ref;              // the grid's `moved`
   const void* normals;
   int normals_elem;
+  const void* src_normals;        // generalized ICP alone
+  int src_normals_elem;
   IcpLayout ws;
   double* T;
   double* fitness;
@@ -94,6 +119,10 @@ __host__ __device__ IcpPair icp_pair_of(const IcpCall& c, const PairGridMeta* me
   v.normals = !c.normals ? nullptr
                          : (c.normals_elem ? (const void*)((const double*)c.normals + 3 * r0) : (const void*)((const float*)c.normals + 3 * r0));
   v.normals_elem = c.normals_elem;
+  v.src_normals = !c.src_normals ? nullptr
+                                 : (c.src_normals_elem ? (const void*)((const double*)c.src_normals + 3 * s0)
+                                                       : (const void*)((const float*)c.src_normals + 3 * s0));
+  v.src_normals_elem = c.src_normals_elem;
   v.nn_idx = c.ws.nn_idx + s0, v.nn_d2 = c.ws.nn_d2 + s0;
   v.T = c.T + 16 * p, v.fitness = c.fitness + p, v.rmse = c.rmse + p;
   v.iterations = c.iterations + p, v.converged = c.converged + p, v.status = c.status + p, v.done = c.ws.done + p;
@@ -125,17 +154,47 @@ __global__ __launch_bounds__(kIcpNnWaves* SE3_WAVE) void icp_nearest_kernel(Pair
   }
 }
 
+template <bool kWeighted, bool kGeneral>
 __global__ __launch_bounds__(kIcpLanes) void icp_step_kernel(IcpCall c, const PairGridMeta* __restrict__ meta, IcpCriteria crit, int k) {
-  __shared__ double sh[kIcpMaxSums * kIcpLanes];
+  __shared__ double sh[(kGeneral ? kIcpGeneralSums : kIcpMaxSums) * kIcpLanes];
   const IcpPair v = icp_pair_of(c, meta, blockIdx.x);
-  icp_pair_step(v, crit, k, threadIdx.x, threadIdx.x + 1, sh, [] { __syncthreads(); });
+  icp_pair_step<kWeighted, kGeneral>(v, crit, k, threadIdx.x, threadIdx.x + 1, sh, [] { __syncthreads(); });
+}
+
+using IcpStepKernel = void (*)(IcpCall, const PairGridMeta*, IcpCriteria, int);
+IcpStepKernel icp_step_kernel_of(const IcpCriteria& crit) {
+  const bool weighted = crit.loss != SE3_ICP_LOSS_NONE;
+  if (crit.mode == SE3_ICP_GENERALIZED) return weighted ? icp_step_kernel<true, true> : icp_step_kernel<false, true>;
+  return weighted ? icp_step_kernel<true, false> : icp_step_kernel<false, false>;
+}
+
+// one step of the host entries
+void icp_host_step(const IcpPair& v, const IcpCriteria& crit, int k, double* sh) {
+  const bool weighted = crit.loss != SE3_ICP_LOSS_NONE;
+  auto none = [] {};
+  if (crit.mode == SE3_ICP_GENERALIZED) {
+    if (weighted) icp_pair_step<true, true>(v, crit, k, 0, kIcpLanes, sh, none);
+    else icp_pair_step<false, true>(v, crit, k, 0, kIcpLanes, sh, none);
+  } else {
+    if (weighted) icp_pair_step<true, false>(v, crit, k, 0, kIcpLanes, sh, none);
+    else icp_pair_step<false, false>(v, crit, k, 0, kIcpLanes, sh, none);
+  }
 }
 
 bool icp_criteria(IcpCriteria* crit, double r, int mode, double relative_fitness, double relative_rmse, int max_iteration) {
-  if (!pg_radius_ok(r) || (mode != SE3_ICP_POINT_TO_POINT && mode != SE3_ICP_POINT_TO_PLANE)) return false;
+  if (!pg_radius_ok(r) || (mode != SE3_ICP_POINT_TO_POINT && mode != SE3_ICP_POINT_TO_PLANE && mode != SE3_ICP_GENERALIZED)) return false;
   if (!(relative_fitness >= 0.0) || !(relative_rmse >= 0.0) || max_iteration < 0 || max_iteration > SE3_ICP_MAX_ITERATION) return false;
   crit->r2 = r * r, crit->relative_fitness = relative_fitness, crit->relative_rmse = relative_rmse;
   crit->max_iteration = max_iteration, crit->mode = mode;
+  crit->loss = SE3_ICP_LOSS_NONE, crit->loss_k = 1.0, crit->eps = 1.0;
+  return true;
+}
+
+// the loss, its width and generalized ICP's epsilon of the weighted entries
+bool icp_loss_criteria(IcpCriteria* crit, int loss, double loss_k, double eps) {
+  if (loss != SE3_ICP_LOSS_NONE && (loss < SE3_ICP_LOSS_L2 || loss > SE3_ICP_LOSS_TUKEY)) return false;
+  if (!(loss_k > 0.0) || !(loss_k < INFINITY) || !(eps > 0.0) || !(eps <= 1.0)) return false;
+  crit->loss = loss, crit->loss_k = loss_k, crit->eps = eps;
   return true;
 }
 
@@ -146,88 +205,165 @@ extern "C" size_t se3_icp_workspace_bytes(int64_t nsrc_total, int num_pairs) {
   return icp_carve(nsrc_total, num_pairs, nullptr, nullptr);
 }
 
+namespace {
+
+// the body of se3_icp_stack and se3_icp_weighted_stack (`what` words the errors); crit is checked
+int icp_stack_run(const char* what, const IcpCriteria& crit, const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total,
+                  const void* src_points, int elem, const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem,
+                  const void* src_normals, int src_normals_elem, const double* T0, double* out_transforms, double* out_fitness, double* out_rmse,
+                  int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  SE3_REQUIRE(grid_workspace && src_points && src_offsets_host && T0 && workspace, SE3_ERR_INVALID_ARG, "%s: null pointer", what);
+  SE3_REQUIRE(out_transforms && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
+              "%s: null result pointer", what);
+  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && nref_total >= 0 && (elem == 0 || elem == 1) && (normals_elem == 0 || normals_elem == 1) &&
+                  (src_normals_elem == 0 || src_normals_elem == 1),
+              SE3_ERR_INVALID_ARG, "%s: %d pairs (at most %d), nref_total %lld, elem %d, normals_elem %d, src_normals_elem %d", what, num_pairs,
+              kPairMaxPairs, (long long)nref_total, elem, normals_elem, src_normals_elem);
+  SE3_REQUIRE(crit.mode == SE3_ICP_POINT_TO_POINT || ref_normals, SE3_ERR_INVALID_ARG, "%s: %s needs the reference normals", what,
+              crit.mode == SE3_ICP_GENERALIZED ? "generalized" : "point-to-plane");
+  SE3_REQUIRE(crit.mode != SE3_ICP_GENERALIZED || src_normals, SE3_ERR_INVALID_ARG, "%s: generalized needs the source normals", what);
+  PairGridCall gc;                // (the count above and the row bound below are worded by this entry: the call makes the other checks)
+  if (const int rc = pg_grid_call(what, "pairs", true, grid_workspace, grid_workspace_bytes, nref_total, elem, src_offsets_host, num_pairs,
+                                  INT64_MAX, &gc))
+    return rc;
+  const int64_t n_total = gc.n_total;
+  SE3_REQUIRE(n_total < (1ll << 31), SE3_ERR_UNSUPPORTED, "%s: %lld source rows in one call", what, (long long)n_total);
+  const PairGridLayout& G = gc.G;
+  IcpCall c;
+  c.rows = gc.rows;
+  SE3_REQUIRE(icp_carve(n_total, num_pairs, (char*)workspace, &c.ws) <= workspace_bytes, SE3_ERR_WORKSPACE,
+              "%s: workspace of %zu bytes is too small", what, workspace_bytes);
+  if (num_pairs == 0) return SE3_OK;
+  c.src = src_points, c.elem = elem, c.ref = G.moved, c.normals = ref_normals, c.normals_elem = normals_elem;
+  c.src_normals = crit.mode == SE3_ICP_GENERALIZED ? src_normals : nullptr, c.src_normals_elem = src_normals_elem;
+  c.T = out_transforms, c.fitness = out_fitness, c.rmse = out_rmse, c.iterations = out_iterations, c.converged = out_converged;
+  c.status = out_status, c.corr = out_correspondences;
+  hipStream_t st = (hipStream_t)stream;
+  const IcpStepKernel step = icp_step_kernel_of(crit);
+  icp_init_kernel<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, G.meta, T0, crit.mode);
+  for (int k = 0; k <= crit.max_iteration; k++) {
+    if (n_total > 0) icp_nearest_kernel<<<(unsigned)se3_cdiv(n_total, kIcpNnWaves), kIcpNnWaves * SE3_WAVE, 0, st>>>(G.view(), c, n_total);
+    step<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, G.meta, crit, k);
+  }
+  SE3_CHECK_LAUNCH(what);
+  return SE3_OK;
+}
+
+}  // namespace
+
 extern "C" int se3_icp_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
                              const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem, const double* T0,
                              double max_correspondence_distance, int mode, double relative_fitness, double relative_rmse, int max_iteration,
                              double* out_transforms, double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged,
                              int* out_status, int64_t* out_correspondences, void* workspace, size_t workspace_bytes, void* stream) {
-  SE3_REQUIRE(grid_workspace && src_points && src_offsets_host && T0 && workspace, SE3_ERR_INVALID_ARG, "icp_stack: null pointer");
-  SE3_REQUIRE(out_transforms && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
-              "icp_stack: null result pointer");
-  SE3_REQUIRE(num_pairs >= 0 && num_pairs <= kPairMaxPairs && nref_total >= 0 && (elem == 0 || elem == 1) && (normals_elem == 0 || normals_elem == 1),
-              SE3_ERR_INVALID_ARG, "icp_stack: %d pairs (at most %d), nref_total %lld, elem %d, normals_elem %d", num_pairs, kPairMaxPairs,
-              (long long)nref_total, elem, normals_elem);
   IcpCriteria crit;
-  SE3_REQUIRE(icp_criteria(&crit, max_correspondence_distance, mode, relative_fitness, relative_rmse, max_iteration), SE3_ERR_INVALID_ARG,
-              "icp_stack: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode, relative_fitness,
-              relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
-  SE3_REQUIRE(mode != SE3_ICP_POINT_TO_PLANE || ref_normals, SE3_ERR_INVALID_ARG, "icp_stack: point-to-plane needs the reference normals");
-  PairGridCall gc;                // (the count above and the row bound below are worded by this entry: the call makes the other checks)
-  if (const int rc = pg_grid_call("icp_stack", "pairs", true, grid_workspace, grid_workspace_bytes, nref_total, elem, src_offsets_host, num_pairs,
-                                  INT64_MAX, &gc))
-    return rc;
-  const int64_t n_total = gc.n_total;
-  SE3_REQUIRE(n_total < (1ll << 31), SE3_ERR_UNSUPPORTED, "icp_stack: %lld source rows in one call", (long long)n_total);
-  const PairGridLayout& G = gc.G;
-  IcpCall c;
-  c.rows = gc.rows;
-  SE3_REQUIRE(icp_carve(n_total, num_pairs, (char*)workspace, &c.ws) <= workspace_bytes, SE3_ERR_WORKSPACE,
-              "icp_stack: workspace of %zu bytes is too small", workspace_bytes);
-  if (num_pairs == 0) return SE3_OK;
-  c.src = src_points, c.elem = elem, c.ref = G.moved, c.normals = ref_normals, c.normals_elem = normals_elem;
-  c.T = out_transforms, c.fitness = out_fitness, c.rmse = out_rmse, c.iterations = out_iterations, c.converged = out_converged;
-  c.status = out_status, c.corr = out_correspondences;
-  hipStream_t st = (hipStream_t)stream;
-  icp_init_kernel<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, G.meta, T0, mode);
-  for (int k = 0; k <= max_iteration; k++) {
-    if (n_total > 0) icp_nearest_kernel<<<(unsigned)se3_cdiv(n_total, kIcpNnWaves), kIcpNnWaves * SE3_WAVE, 0, st>>>(G.view(), c, n_total);
-    icp_step_kernel<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, G.meta, crit, k);
-  }
-  SE3_CHECK_LAUNCH("icp_stack");
-  return SE3_OK;
+  SE3_REQUIRE(mode != SE3_ICP_GENERALIZED && icp_criteria(&crit, max_correspondence_distance, mode, relative_fitness, relative_rmse, max_iteration),
+              SE3_ERR_INVALID_ARG, "icp_stack: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode,
+              relative_fitness, relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
+  return icp_stack_run("icp_stack", crit, grid_workspace, grid_workspace_bytes, nref_total, src_points, elem, src_offsets_host, num_pairs,
+                       ref_normals, normals_elem, nullptr, 0, T0, out_transforms, out_fitness, out_rmse, out_iterations, out_converged,
+                       out_status, out_correspondences, workspace, workspace_bytes, stream);
 }
 
-// ---- the same text on host memory, one pair, no GPU (tests/test_icp_cpu.py) -------------------------------------------------------------------
-// trace: NULL, or (max_iteration + 1, n) int64: row k receives evaluation k's correspondence of every source row (-1 for none); the rows
-// of evaluations that were not made are left as they are.
-extern "C" int se3_debug_icp_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
-                                  int normals_elem, const double* T0, double max_correspondence_distance, int mode, double relative_fitness,
-                                  double relative_rmse, int max_iteration, double* out_transform, double* out_fitness, double* out_rmse,
-                                  int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace) {
-  SE3_REQUIRE(src_points && ref_points && T0, SE3_ERR_INVALID_ARG, "debug_icp_host: null pointer");
-  SE3_REQUIRE(out_transform && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
-              "debug_icp_host: null result pointer");
-  SE3_REQUIRE(n >= 0 && n < (1ll << 31) && nref >= 0 && nref < (1ll << 31) && (elem == 0 || elem == 1) && (normals_elem == 0 || normals_elem == 1),
-              SE3_ERR_INVALID_ARG, "debug_icp_host: n %lld, nref %lld, elem %d, normals_elem %d", (long long)n, (long long)nref, elem, normals_elem);
+extern "C" size_t se3_icp_weighted_workspace_bytes(int64_t nsrc_total, int num_pairs) { return se3_icp_workspace_bytes(nsrc_total, num_pairs); }
+
+extern "C" int se3_icp_weighted_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points,
+                                      int elem, const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem,
+                                      const void* src_normals, int src_normals_elem, const double* T0, double max_correspondence_distance,
+                                      int mode, int loss, double loss_k, double gicp_epsilon, double relative_fitness, double relative_rmse,
+                                      int max_iteration, double* out_transforms, double* out_fitness, double* out_rmse, int* out_iterations,
+                                      int* out_converged, int* out_status, int64_t* out_correspondences, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
   IcpCriteria crit;
   SE3_REQUIRE(icp_criteria(&crit, max_correspondence_distance, mode, relative_fitness, relative_rmse, max_iteration), SE3_ERR_INVALID_ARG,
-              "debug_icp_host: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode,
+              "icp_weighted_stack: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode,
               relative_fitness, relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
-  SE3_REQUIRE(mode != SE3_ICP_POINT_TO_PLANE || ref_normals, SE3_ERR_INVALID_ARG, "debug_icp_host: point-to-plane needs the reference normals");
+  SE3_REQUIRE(icp_loss_criteria(&crit, loss, loss_k, gicp_epsilon), SE3_ERR_INVALID_ARG,
+              "icp_weighted_stack: loss %d, loss_k %g (positive and finite), gicp_epsilon %g (in (0, 1])", loss, loss_k, gicp_epsilon);
+  return icp_stack_run("icp_weighted_stack", crit, grid_workspace, grid_workspace_bytes, nref_total, src_points, elem, src_offsets_host,
+                       num_pairs, ref_normals, normals_elem, src_normals, src_normals_elem, T0, out_transforms, out_fitness, out_rmse,
+                       out_iterations, out_converged, out_status, out_correspondences, workspace, workspace_bytes, stream);
+}
+
+// ---- the same text on host memory, one pair, no GPU (tests/test_icp_cpu.py, tests/test_icp_robust_cpu.py) --------------------------------------
+// icp_host_run is the body of se3_debug_icp_host and se3_debug_icp_weighted_host (`what` words the errors); crit is checked.
+// trace: NULL, or (max_iteration + 1, n) int64: row k receives evaluation k's correspondence of every source row (-1 for none); the rows
+// of evaluations that were not made are left as they are.
+namespace {
+
+int icp_host_run(const char* what, const IcpCriteria& crit, const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem,
+                 const void* ref_normals, int normals_elem, const void* src_normals, int src_normals_elem, const double* T0,
+                 double max_correspondence_distance, double* out_transform, double* out_fitness, double* out_rmse, int* out_iterations,
+                 int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace) {
+  SE3_REQUIRE(src_points && ref_points && T0, SE3_ERR_INVALID_ARG, "%s: null pointer", what);
+  SE3_REQUIRE(out_transform && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
+              "%s: null result pointer", what);
+  SE3_REQUIRE(n >= 0 && n < (1ll << 31) && nref >= 0 && nref < (1ll << 31) && (elem == 0 || elem == 1) && (normals_elem == 0 || normals_elem == 1) &&
+                  (src_normals_elem == 0 || src_normals_elem == 1),
+              SE3_ERR_INVALID_ARG, "%s: n %lld, nref %lld, elem %d, normals_elem %d, src_normals_elem %d", what, (long long)n, (long long)nref,
+              elem, normals_elem, src_normals_elem);
+  SE3_REQUIRE(crit.mode == SE3_ICP_POINT_TO_POINT || ref_normals, SE3_ERR_INVALID_ARG, "%s: %s needs the reference normals", what,
+              crit.mode == SE3_ICP_GENERALIZED ? "generalized" : "point-to-plane");
+  SE3_REQUIRE(crit.mode != SE3_ICP_GENERALIZED || src_normals, SE3_ERR_INVALID_ARG, "%s: generalized needs the source normals", what);
   PairHostGrid H(ref_points, nref, elem, nullptr, max_correspondence_distance);
   const PairGridLayout& G = H.G;
   std::vector<int> nn_idx((size_t)n + 1);
-  std::vector<double> nn_d2((size_t)n + 1), sh((size_t)kIcpMaxSums * kIcpLanes);
+  std::vector<double> nn_d2((size_t)n + 1), sh((size_t)kIcpGeneralSums * kIcpLanes);
   int done = 0;
   IcpCall c;
   c.rows = pg_single_rows(n);
   c.src = src_points, c.elem = elem, c.ref = G.moved, c.normals = ref_normals, c.normals_elem = normals_elem;
+  c.src_normals = crit.mode == SE3_ICP_GENERALIZED ? src_normals : nullptr, c.src_normals_elem = src_normals_elem;
   c.ws.nn_idx = nn_idx.data(), c.ws.nn_d2 = nn_d2.data(), c.ws.done = &done;
   c.T = out_transform, c.fitness = out_fitness, c.rmse = out_rmse, c.iterations = out_iterations, c.converged = out_converged;
   c.status = out_status, c.corr = out_correspondences;
   const IcpPair v = icp_pair_of(c, G.meta, 0);
   const PairGridView g = G.view();
-  icp_pair_init(v, T0, mode, 0, kIcpLanes, sh.data(), [] {});
-  for (int k = 0; k <= max_iteration && !done; k++) {
+  icp_pair_init(v, T0, crit.mode, 0, kIcpLanes, sh.data(), [] {});
+  for (int k = 0; k <= crit.max_iteration && !done; k++) {
     for (int64_t i = 0; i < n; i++) {
       double qv[3];
       icp_moved(v, v.T, i, qv);
       pg_nearest(g, 0, qv, 0, 1, [](double*, int*) {}, &nn_d2[(size_t)i], &nn_idx[(size_t)i]);
       if (trace) trace[(int64_t)k * n + i] = nn_d2[(size_t)i] < crit.r2 ? nn_idx[(size_t)i] : -1;
     }
-    icp_pair_step(v, crit, k, 0, kIcpLanes, sh.data(), [] {});
+    icp_host_step(v, crit, k, sh.data());
   }
   return SE3_OK;
+}
+
+}  // namespace
+
+extern "C" int se3_debug_icp_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
+                                  int normals_elem, const double* T0, double max_correspondence_distance, int mode, double relative_fitness,
+                                  double relative_rmse, int max_iteration, double* out_transform, double* out_fitness, double* out_rmse,
+                                  int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace) {
+  IcpCriteria crit;
+  SE3_REQUIRE(mode != SE3_ICP_GENERALIZED && icp_criteria(&crit, max_correspondence_distance, mode, relative_fitness, relative_rmse, max_iteration),
+              SE3_ERR_INVALID_ARG, "debug_icp_host: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance,
+              mode, relative_fitness, relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
+  return icp_host_run("debug_icp_host", crit, src_points, n, ref_points, nref, elem, ref_normals, normals_elem, nullptr, 0, T0,
+                      max_correspondence_distance, out_transform, out_fitness, out_rmse, out_iterations, out_converged, out_status,
+                      out_correspondences, trace);
+}
+
+// the weighted entry on host memory: se3_icp_weighted_stack's text for one pair, with se3_debug_icp_host's trace
+extern "C" int se3_debug_icp_weighted_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem,
+                                           const void* ref_normals, int normals_elem, const void* src_normals, int src_normals_elem,
+                                           const double* T0, double max_correspondence_distance, int mode, int loss, double loss_k,
+                                           double gicp_epsilon, double relative_fitness, double relative_rmse, int max_iteration,
+                                           double* out_transform, double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged,
+                                           int* out_status, int64_t* out_correspondences, int64_t* trace) {
+  IcpCriteria crit;
+  SE3_REQUIRE(icp_criteria(&crit, max_correspondence_distance, mode, relative_fitness, relative_rmse, max_iteration), SE3_ERR_INVALID_ARG,
+              "debug_icp_weighted_host: distance %g, mode %d, criteria %g %g %d (at most %d iterations)", max_correspondence_distance, mode,
+              relative_fitness, relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
+  SE3_REQUIRE(icp_loss_criteria(&crit, loss, loss_k, gicp_epsilon), SE3_ERR_INVALID_ARG,
+              "debug_icp_weighted_host: loss %d, loss_k %g (positive and finite), gicp_epsilon %g (in (0, 1])", loss, loss_k, gicp_epsilon);
+  return icp_host_run("debug_icp_weighted_host", crit, src_points, n, ref_points, nref, elem, ref_normals, normals_elem, src_normals,
+                      src_normals_elem, T0, max_correspondence_distance, out_transform, out_fitness, out_rmse, out_iterations, out_converged,
+                      out_status, out_correspondences, trace);
 }
 
 extern "C" int se3_debug_icp_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos) {

@@ -2,6 +2,9 @@
 // convergence test and update (icp_pair_step), with the summation order they share.  The kernels run it with one workgroup of kIcpLanes
 // threads per pair (each thread one lane, `barrier` = __syncthreads); se3_debug_icp_host runs the same text serially over all lanes with
 // a no-op barrier.  The contract is the header comment of icp.hip.
+//
+// icp_pair_step<kWeighted, kGeneral> is four instantiations.  kWeighted = false holds no weight code at all: <false, false> is the text
+// of se3_icp_stack, and its sums are not multiplied by 1.  kGeneral = true is generalized ICP alone, whose 27 sums are formed in one pass.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -13,6 +16,7 @@
 // lanes are added by the tree lane[l] += lane[l + o], o = kIcpLanes / 2 .. 1.  It depends on the pair's row count alone.
 constexpr int kIcpLanes = 256;
 constexpr int kIcpMaxSums = 21;                 // the widest sum: the upper triangle of the point-to-plane J^T J
+constexpr int kIcpGeneralSums = 27;             // generalized ICP: the upper triangle of sum A^T M^-1 A and sum A^T M^-1 d, one pass
 constexpr double kIcpPivotTol = 1e-13;          // a Cholesky pivot must exceed this share of its diagonal entry: below it is rounding
 constexpr double kIcpMaxAngle = 1.0;            // rad: a linearised step with an angle this large is refused
 
@@ -22,7 +26,9 @@ struct IcpMath {                                // the Kabsch solve's root, roun
 
 struct IcpCriteria {
   double r2, relative_fitness, relative_rmse;
-  int max_iteration, mode;                      // SE3_ICP_POINT_TO_POINT / SE3_ICP_POINT_TO_PLANE
+  int max_iteration, mode;                      // SE3_ICP_POINT_TO_POINT / SE3_ICP_POINT_TO_PLANE / SE3_ICP_GENERALIZED
+  int loss;                                     // SE3_ICP_LOSS_*; SE3_ICP_LOSS_NONE selects the instantiations without weight code
+  double loss_k, eps;                           // the loss's width k > 0; generalized ICP's epsilon in (0, 1]
 };
 
 // one pair's rows and results; every pointer already points at the pair's first entry
@@ -34,6 +40,8 @@ struct IcpPair {
   int64_t nref;
   const void* normals;      // (nref, 3), normals_elem; may be null for point-to-point
   int normals_elem;
+  const void* src_normals;  // (n, 3), src_normals_elem: generalized ICP alone, null otherwise
+  int src_normals_elem;
   int* nn_idx;              // (n): nearest reference row of the last evaluation
   double* nn_d2;            // (n)
   double* T;                // (4, 4): the current transform, the result at the end
@@ -129,6 +137,103 @@ PG_HD void icp_plane_row(const IcpPair& v, const double* T, int64_t i, double* J
   J[0] = yz - zy, J[1] = zx - xz, J[2] = xy - yx, J[3] = nx, J[4] = ny, J[5] = nz;
 }
 
+// Open3D's RobustKernel weights w(r) of a scalar residual, k > 0; every one is continuous at its branch.  Divisions and products are
+// IEEE on both sides, so the host and the device give the same bits.
+PG_HD double icp_weight(int loss, double k, double r) {
+#pragma clang fp contract(off)
+  const double a = fabs(r);
+  if (loss == SE3_ICP_LOSS_HUBER) return a <= k ? 1.0 : k / a;
+  const double t = r / k;
+  const double tt = t * t;
+  if (loss == SE3_ICP_LOSS_CAUCHY) return 1.0 / (1.0 + tt);
+  if (loss == SE3_ICP_LOSS_GM) {
+    const double rr = r * r;
+    const double s = k + rr;
+    return k / (s * s);
+  }
+  if (loss == SE3_ICP_LOSS_TUKEY) {
+    if (!(a <= k)) return 0.0;
+    const double u = 1.0 - tt;
+    return u * u;
+  }
+  return 1.0;                                   // SE3_ICP_LOSS_L2
+}
+
+// p x v, every product rounded on its own
+PG_HD void icp_cross(const double* p, const double* v, double* out) {
+#pragma clang fp contract(off)
+  const double yz = p[1] * v[2], zy = p[2] * v[1], zx = p[2] * v[0], xz = p[0] * v[2], xy = p[0] * v[1], yx = p[1] * v[0];
+  out[0] = yz - zy, out[1] = zx - xz, out[2] = xy - yx;
+}
+
+// Correspondence i of generalized ICP: h[21] = the upper triangle of A^T B A, row by row, g[6] = A^T B d and *rho2 = d^T B d, with
+// d = p - q, A = [-[p]_x | I] and B = M^-1, M = 2 I - (1 - eps)(nt nt^T + m m^T), m = R ns, inverted by its cofactors.  A^T = [[p]_x ; I],
+// so the blocks are p x (columns of B G), p x (columns of B) and B itself, G = -[p]_x.  Every term is even in nt and in ns.
+PG_HD void icp_general_row(const IcpPair& v, const double* T, double eps, int64_t i, double* h, double* g, double* rho2) {
+#pragma clang fp contract(off)
+  double p[3];
+  icp_moved(v, T, i, p);
+  const int64_t j = v.nn_idx[i];
+  const double* q = v.ref + 3 * j;
+  double nt[3], ns[3], m[3];
+  for (int a = 0; a < 3; a++) nt[a] = pg_load(v.normals, v.normals_elem, 3 * j + a), ns[a] = pg_load(v.src_normals, v.src_normals_elem, 3 * i + a);
+  for (int a = 0; a < 3; a++) {
+    const double x = T[4 * a] * ns[0], y = T[4 * a + 1] * ns[1], z = T[4 * a + 2] * ns[2];
+    m[a] = (x + y) + z;
+  }
+  const double c = 1.0 - eps;
+  double M[3][3];
+  for (int a = 0; a < 3; a++)
+    for (int b = a; b < 3; b++) {
+      const double tt = nt[a] * nt[b], mm = m[a] * m[b];
+      const double s = c * (tt + mm);
+      M[a][b] = M[b][a] = (a == b ? 2.0 : 0.0) - s;
+    }
+  double C[3][3];                                                       // the cofactors of the symmetric M
+  {
+    const double df = M[1][1] * M[2][2], ee = M[1][2] * M[1][2], ce = M[0][2] * M[1][2], bf = M[0][1] * M[2][2], be = M[0][1] * M[1][2],
+                 cd = M[0][2] * M[1][1], af = M[0][0] * M[2][2], cc = M[0][2] * M[0][2], bc = M[0][1] * M[0][2], ae = M[0][0] * M[1][2],
+                 ad = M[0][0] * M[1][1], bb = M[0][1] * M[0][1];
+    C[0][0] = df - ee, C[0][1] = C[1][0] = ce - bf, C[0][2] = C[2][0] = be - cd;
+    C[1][1] = af - cc, C[1][2] = C[2][1] = bc - ae, C[2][2] = ad - bb;
+  }
+  const double d0 = M[0][0] * C[0][0], d1 = M[0][1] * C[0][1], d2 = M[0][2] * C[0][2];
+  const double det = (d0 + d1) + d2;
+  double B[3][3];
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) B[a][b] = C[a][b] / det;
+  const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  double e[3];                                                          // B d
+  for (int a = 0; a < 3; a++) {
+    const double x = B[a][0] * d[0], y = B[a][1] * d[1], z = B[a][2] * d[2];
+    e[a] = (x + y) + z;
+  }
+  {
+    const double x = d[0] * e[0], y = d[1] * e[1], z = d[2] * e[2];
+    *rho2 = (x + y) + z;
+  }
+  double F[6][6];                                                       // A^T B A, the upper triangle
+  for (int b = 0; b < 3; b++) {
+    double col[3], out[3];
+    // column b of B G: G = [[0, pz, -py], [-pz, 0, px], [py, -px, 0]]
+    for (int a = 0; a < 3; a++) {
+      const int b1 = (b + 1) % 3, b2 = (b + 2) % 3;                     // column b of G holds p[b1] in row b2 and -p[b2] in row b1
+      const double x = B[a][b2] * p[b1], y = B[a][b1] * p[b2];
+      col[a] = x - y;
+    }
+    icp_cross(p, col, out);
+    for (int a = 0; a <= b; a++) F[a][b] = out[a];
+    for (int a = 0; a < 3; a++) col[a] = B[a][b];
+    icp_cross(p, col, out);
+    for (int a = 0; a < 3; a++) F[a][3 + b] = out[a];
+    for (int a = 0; a <= b; a++) F[3 + a][3 + b] = B[a][b];
+  }
+  for (int a = 0, k = 0; a < 6; a++)
+    for (int b = a; b < 6; b++, k++) h[k] = F[a][b];
+  icp_cross(p, e, g);
+  g[3] = e[0], g[4] = e[1], g[5] = e[2];
+}
+
 // T <- U T for two rigid 4x4 (the last rows are 0 0 0 1): (a b + c d) + e f per entry, the translation added last
 PG_HD void icp_compose(const double* U, const double* T, double* out) {
 #pragma clang fp contract(off)
@@ -199,16 +304,22 @@ PG_HD void icp_vector6_to_matrix(const double* x, double* U) {
   U[12] = 0.0, U[13] = 0.0, U[14] = 0.0, U[15] = 1.0;
 }
 
-// Before the first evaluation: T <- T0, the results cleared; a non-finite T0, point or (point-to-plane) normal refuses the pair:
-// SE3_ICP_NONFINITE, a NaN transform, done.
+// Before the first evaluation: T <- T0, the results cleared; a non-finite T0, point or normal that the mode reads (point-to-plane: the
+// reference's; generalized: both clouds') refuses the pair: SE3_ICP_NONFINITE, a NaN transform, done.
 template <class Barrier>
 PG_HD void icp_pair_init(const IcpPair& v, const double* T0, int mode, int lane_begin, int lane_end, double* sh, Barrier&& barrier) {
   double bad[1], part[1];
-  icp_sum<1>(v.n, lane_begin, lane_end, [&](int64_t i, double* acc) { acc[0] += icp_finite3(v.src, v.elem, i) ? 0.0 : 1.0; }, sh, barrier, bad);
+  icp_sum<1>(v.n, lane_begin, lane_end,
+             [&](int64_t i, double* acc) {
+               bool ok = icp_finite3(v.src, v.elem, i);
+               if (mode == SE3_ICP_GENERALIZED) ok = ok && icp_finite3(v.src_normals, v.src_normals_elem, i);
+               acc[0] += ok ? 0.0 : 1.0;
+             },
+             sh, barrier, bad);
   icp_sum<1>(v.nref, lane_begin, lane_end,
              [&](int64_t i, double* acc) {
                bool ok = icp_finite3(v.ref, 1, i);
-               if (mode == SE3_ICP_POINT_TO_PLANE) ok = ok && icp_finite3(v.normals, v.normals_elem, i);
+               if (mode != SE3_ICP_POINT_TO_POINT) ok = ok && icp_finite3(v.normals, v.normals_elem, i);
                acc[0] += ok ? 0.0 : 1.0;
              },
              sh, barrier, part);
@@ -227,7 +338,10 @@ PG_HD void icp_pair_init(const IcpPair& v, const double* T0, int mode, int lane_
 
 // Evaluation k of a pair from the (index, d^2) its rows hold, the convergence test against evaluation k - 1, and, when the pair goes on,
 // the update U and T <- U T.  Uniform over the lanes: every lane forms the same sums and solves the same system; lane 0 writes.
-template <class Barrier>
+// kWeighted: every term of the update's sums carries w(residual) of crit.loss (iteratively reweighted least squares, the weights from
+// this evaluation); the counts, fitness and rmse never do.  kGeneral: crit.mode is SE3_ICP_GENERALIZED, and sh holds kIcpGeneralSums
+// columns; otherwise it is one of the other two and sh holds kIcpMaxSums.
+template <bool kWeighted, bool kGeneral, class Barrier>
 PG_HD void icp_pair_step(const IcpPair& v, const IcpCriteria& crit, int k, int lane_begin, int lane_end, double* sh, Barrier&& barrier) {
 #pragma clang fp contract(off)
   if (*v.done) return;
@@ -256,9 +370,89 @@ PG_HD void icp_pair_step(const IcpPair& v, const IcpCriteria& crit, int k, int l
     icp_identity(U);
     if (v.n == 0 || v.nref == 0) {
       status |= SE3_ICP_EMPTY;
+    } else if constexpr (kGeneral) {
+      if (count < 6.0) {
+        status |= SE3_ICP_TOO_FEW;
+      } else {
+        double s[kIcpGeneralSums];
+        icp_sum<kIcpGeneralSums>(v.n, lane_begin, lane_end,
+                                 [&](int64_t i, double* acc) {
+                                   if (!(v.nn_d2[i] < r2)) return;
+                                   double h[21], g[6], rho2;
+                                   icp_general_row(v, T, crit.eps, i, h, g, &rho2);
+                                   if constexpr (kWeighted) {
+                                     const double w = icp_weight(crit.loss, crit.loss_k, pg_sqrt(rho2));
+                                     for (int e = 0; e < 21; e++) {
+                                       const double m = w * h[e];
+                                       acc[e] += m;
+                                     }
+                                     for (int a = 0; a < 6; a++) {
+                                       const double m = w * g[a];
+                                       acc[21 + a] += m;
+                                     }
+                                   } else {
+                                     for (int e = 0; e < 21; e++) acc[e] += h[e];
+                                     for (int a = 0; a < 6; a++) acc[21 + a] += g[a];
+                                   }
+                                 },
+                                 sh, barrier, s);
+        double rhs[6], x[6];
+        for (int a = 0; a < 6; a++) rhs[a] = -s[21 + a];
+        if (!icp_cholesky6(s, rhs, x)) {
+          status |= SE3_ICP_SINGULAR;
+        } else if (!(fabs(x[0]) < kIcpMaxAngle) || !(fabs(x[1]) < kIcpMaxAngle) || !(fabs(x[2]) < kIcpMaxAngle)) {
+          status |= SE3_ICP_STEP_REFUSED;
+          finished = true;
+        } else {
+          icp_vector6_to_matrix(x, U);
+        }
+      }
     } else if (crit.mode == SE3_ICP_POINT_TO_POINT) {
       if (count < 3.0) {
         status |= SE3_ICP_TOO_FEW;
+      } else if constexpr (kWeighted) {
+        // weighted Kabsch: w = w(sqrt(d^2)); W = sum w, the centroids sum w p / W and sum w q / W, H = sum w (p - pc)(q - qc)^T
+        double s[7], pc[3], qc[3], h[9];
+        icp_sum<7>(v.n, lane_begin, lane_end,
+                   [&](int64_t i, double* acc) {
+                     if (!(v.nn_d2[i] < r2)) return;
+                     const double w = icp_weight(crit.loss, crit.loss_k, pg_sqrt(v.nn_d2[i]));
+                     double p[3];
+                     icp_moved(v, T, i, p);
+                     const double* q = v.ref + 3 * (int64_t)v.nn_idx[i];
+                     acc[6] += w;
+                     for (int d = 0; d < 3; d++) {
+                       const double wp = w * p[d], wq = w * q[d];
+                       acc[d] += wp, acc[3 + d] += wq;
+                     }
+                   },
+                   sh, barrier, s);
+        if (!(s[6] > 0.0) || !(s[6] < INFINITY)) {
+          status |= SE3_ICP_SINGULAR;                                    // no weight left: the identity update
+        } else {
+          for (int d = 0; d < 3; d++) pc[d] = s[d] / s[6], qc[d] = s[3 + d] / s[6];
+          icp_sum<9>(v.n, lane_begin, lane_end,
+                     [&](int64_t i, double* acc) {
+                       if (!(v.nn_d2[i] < r2)) return;
+                       const double w = icp_weight(crit.loss, crit.loss_k, pg_sqrt(v.nn_d2[i]));
+                       double p[3];
+                       icp_moved(v, T, i, p);
+                       const double* q = v.ref + 3 * (int64_t)v.nn_idx[i];
+                       for (int a = 0; a < 3; a++) {
+                         const double pa = w * (p[a] - pc[a]);
+                         for (int b = 0; b < 3; b++) {
+                           const double qb = q[b] - qc[b];
+                           const double m = pa * qb;
+                           acc[3 * a + b] += m;
+                         }
+                       }
+                     },
+                     sh, barrier, h);
+          double H[3][3];
+          for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) H[a][b] = h[3 * a + b];
+          kabsch<IcpMath, double>(H, pc, qc, U);
+        }
       } else {
         double s[6], pc[3], qc[3], h[9];
         icp_sum<6>(v.n, lane_begin, lane_end,
@@ -302,6 +496,17 @@ PG_HD void icp_pair_step(const IcpPair& v, const IcpCriteria& crit, int k, int l
                       if (!(v.nn_d2[i] < r2)) return;
                       double J[6], res;
                       icp_plane_row(v, T, i, J, &res);
+                      if constexpr (kWeighted) {
+                        const double w = icp_weight(crit.loss, crit.loss_k, res);
+                        for (int a = 0, e = 0; a < 6; a++) {
+                          const double wJ = w * J[a];
+                          for (int b = a; b < 6; b++, e++) {
+                            const double m = wJ * J[b];
+                            acc[e] += m;
+                          }
+                        }
+                        return;
+                      }
                       for (int a = 0, e = 0; a < 6; a++)
                         for (int b = a; b < 6; b++, e++) {
                           const double m = J[a] * J[b];
@@ -314,6 +519,14 @@ PG_HD void icp_pair_step(const IcpPair& v, const IcpCriteria& crit, int k, int l
                      if (!(v.nn_d2[i] < r2)) return;
                      double J[6], res;
                      icp_plane_row(v, T, i, J, &res);
+                     if constexpr (kWeighted) {
+                       const double wr = icp_weight(crit.loss, crit.loss_k, res) * res;
+                       for (int a = 0; a < 6; a++) {
+                         const double m = J[a] * wr;
+                         acc[a] += m;
+                       }
+                       return;
+                     }
                      for (int a = 0; a < 6; a++) {
                        const double m = J[a] * res;
                        acc[a] += m;

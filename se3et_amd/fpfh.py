@@ -195,16 +195,19 @@ def compute_fpfh_feature(points, normals, radius=None, max_nn=None, device=None)
 @torch.no_grad()
 def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpfh_radius=None, fpfh_max_nn=None, distance_threshold=None,
                               ransac_n=3, num_iterations=50000, mutual_filter=True, edge_length_similarity=0.9, check_distance=True,
-                              icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None):
+                              icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None, icp_loss=None,
+                              icp_loss_k=None):
     """The classical global registration of P pairs, a composition of the batched tools (no kernel of its own): voxel_downsample_clouds at
     voxel_size, estimate_normals_clouds (normal_knn), compute_fpfh_clouds (float32), ransac_from_feats_pairs, and with icp_distance
     icp_pairs from the RANSAC result on the downsampled clouds.  src_list / ref_list: (n, 3) float32 or float64 GPU tensors.
     Defaults, as multiples of voxel_size: fpfh_radius None = 5 voxel_size when fpfh_max_nn is None too (a radius search; give fpfh_max_nn
     alone for the k nearest, both for the hybrid); distance_threshold None = 1.5 voxel_size.  icp_distance None: no refinement.
+    icp_estimation 'generalized' refines with generalized_icp_pairs on the normals computed here for both clouds; icp_loss / icp_loss_k:
+    the robust loss kernel of either refinement (icp.icp_pairs), None for none.
     Returns a dict: transforms (P, 4, 4) float64 on the device (ref ~ T src), ransac_transforms, src_points / ref_points / src_normals /
-    ref_normals / src_feats / ref_feats (the intermediate lists), ransac (the dict of ransac_from_feats_pairs) and icp (that of icp_pairs,
-    or None)."""
-    from .icp import icp_pairs
+    ref_normals / src_feats / ref_feats (the intermediate lists), ransac (the dict of ransac_from_feats_pairs) and icp (that of icp_pairs
+    or generalized_icp_pairs, or None)."""
+    from .icp import generalized_icp_pairs, icp_pairs
     from .ransac import ransac_from_feats_pairs
     from .scan_prep import estimate_normals_clouds, voxel_downsample_clouds
     what = 'global_registration_pairs'
@@ -227,8 +230,11 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
                                      distance_threshold, ransac_n, num_iterations, mutual_filter, seed, edge_length_similarity, check_distance)
     coarse = ransac['transforms'].to(torch.float64)
     icp = None
-    if icp_distance is not None:
+    if icp_distance is not None and icp_estimation == 'generalized':
+        icp = generalized_icp_pairs(src, ref, coarse, icp_distance, normals[:P], normals[P:], loss=icp_loss, loss_k=icp_loss_k,
+                                    max_iteration=icp_max_iteration, device=dev)
+    elif icp_distance is not None:
         icp = icp_pairs(src, ref, coarse, icp_distance, icp_estimation, normals[P:] if icp_estimation == 'point_to_plane' else None,
-                        max_iteration=icp_max_iteration, device=dev)
+                        max_iteration=icp_max_iteration, device=dev, loss=icp_loss, loss_k=icp_loss_k)
     return {'transforms': icp['transforms'] if icp is not None else coarse, 'ransac_transforms': coarse, 'src_points': src, 'ref_points': ref,
             'src_normals': normals[:P], 'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'icp': icp}

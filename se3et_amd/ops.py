@@ -8,7 +8,7 @@ import threading
 import torch
 
 from .caches import CACHE_EPOCH, Derived, Workspace, _Shared, also_clear, clear_caches, clear_weight_caches, validate_weight_caches  # noqa: F401
-from ._lib import CONSTANTS, check, lib
+from ._lib import CONSTANTS, ENUMS, check, lib
 from .stacking import PAIR_MAX_PAIRS, device_offsets, exclusive_offsets, to_device
 
 
@@ -2533,6 +2533,79 @@ def icp_stack(grid, src_points, src_lengths, init_transforms, max_correspondence
     if corr is not None:
         out['correspondences'] = corr
     return out
+
+
+# the weighted entry: robust loss kernels and generalized ICP.  ICP_MODES stays the two modes of icp_stack; the third is this entry's own.
+ICP_GENERALIZED = ENUMS['se3_icp_option']['SE3_ICP_GENERALIZED']
+ICP_WEIGHTED_MODES = dict(ICP_MODES, generalized=ICP_GENERALIZED)
+ICP_LOSSES = {name[len('SE3_ICP_LOSS_'):].lower(): value for name, value in ENUMS['se3_icp_option'].items()
+              if name.startswith('SE3_ICP_LOSS_') and value >= 0}
+_ICP_LOSS_NONE = ENUMS['se3_icp_option']['SE3_ICP_LOSS_NONE']
+
+
+def icp_weighted_stack(grid, src_points, src_lengths, init_transforms, max_correspondence_distance, mode, ref_normals=None, src_normals=None,
+                       loss=None, loss_k=None, gicp_epsilon=1e-3, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
+                       return_correspondences=False):
+    """HIP: icp_stack with a robust loss kernel and / or generalized ICP.  mode: a key of ICP_WEIGHTED_MODES; 'generalized' needs
+    ref_normals and src_normals ((total source rows, 3) float32 / float64), unit normals of both clouds, and reads gicp_epsilon in (0, 1].
+    loss: None (the instantiation without weight code: for the modes of icp_stack, its kernels and bits) or a key of ICP_LOSSES with its
+    width loss_k, finite and positive ('l2' takes none).  Everything else, and the returned dict, as icp_stack."""
+    s, elem = _pair_points(src_points, 'src_points')
+    P = len(src_lengths)
+    if s.device != grid.device or P != grid.num_pairs:
+        raise RuntimeError('icp_weighted_stack: %d pairs on %s expected' % (grid.num_pairs, grid.device))
+    if mode not in ICP_WEIGHTED_MODES:
+        raise ValueError('icp_weighted_stack: estimation %r is not one of %s' % (mode, ', '.join(sorted(ICP_WEIGHTED_MODES))))
+    loss_id, k = icp_loss_of(loss, loss_k, 'icp_weighted_stack')
+    offsets = _pair_offsets(src_lengths, s.shape[0], 'icp_weighted_stack')
+    T0 = _req(init_transforms, torch.float64, 'init_transforms', 3)
+    if tuple(T0.shape) != (P, 4, 4) or T0.device != s.device:
+        raise RuntimeError('icp_weighted_stack: init_transforms must be (%d, 4, 4) on %s' % (P, s.device))
+    nr, nelem, sn, selem = None, 1, None, 1
+    if ref_normals is not None:
+        nr, nelem = _pair_points(ref_normals, 'ref_normals')
+        if nr.shape[0] != grid.ns_total or nr.device != s.device:
+            raise RuntimeError('icp_weighted_stack: ref_normals must be (%d, 3) on %s' % (grid.ns_total, s.device))
+    elif mode != 'point_to_point':
+        raise RuntimeError('icp_weighted_stack: %s needs the reference normals' % mode)
+    if mode == 'generalized':
+        if src_normals is None:
+            raise RuntimeError('icp_weighted_stack: generalized needs the source normals')
+        sn, selem = _pair_points(src_normals, 'src_normals')
+        if sn.shape[0] != s.shape[0] or sn.device != s.device:
+            raise RuntimeError('icp_weighted_stack: src_normals must be (%d, 3) on %s' % (s.shape[0], s.device))
+    dev = s.device
+    out = icp_outputs(P, dev)
+    corr = torch.empty((s.shape[0],), dtype=torch.int64, device=dev) if return_correspondences else None
+    nbytes = lib().se3_icp_weighted_workspace_bytes(s.shape[0], P)
+    stream = _stream()
+    ws = _ws_icp.get(dev, stream.value, nbytes)
+    check(lib().se3_icp_weighted_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(s), elem, offsets, P, None if nr is None else _dp(nr),
+                                       nelem, None if sn is None else _dp(sn), selem, _dp(T0), float(max_correspondence_distance),
+                                       ICP_WEIGHTED_MODES[mode], loss_id, k, float(gicp_epsilon), float(relative_fitness), float(relative_rmse),
+                                       int(max_iteration), _dp(out['transforms']), _dp(out['fitness']), _dp(out['inlier_rmse']),
+                                       _dp(out['iterations']), _dp(out['converged']), _dp(out['status']), None if corr is None else _dp(corr),
+                                       ws.data_ptr(), nbytes, stream),
+          'se3_icp_weighted_stack')
+    if corr is not None:
+        out['correspondences'] = corr
+    return out
+
+
+def icp_loss_of(loss, loss_k, what):
+    """(the library's loss id, its width) of a loss name or None and loss_k; a ValueError for an unknown name or a width that is not
+    finite and positive.  None and 'l2' read no width: 1.0 stands in."""
+    if loss is not None and loss not in ICP_LOSSES:
+        raise ValueError('%s: loss %r is not one of %s' % (what, loss, ', '.join(sorted(ICP_LOSSES))))
+    if loss_k is None and loss in (None, 'l2'):
+        return (_ICP_LOSS_NONE if loss is None else ICP_LOSSES[loss]), 1.0
+    try:
+        k = float(loss_k)
+    except (TypeError, ValueError):
+        k = float('nan')
+    if not (math.isfinite(k) and k > 0):
+        raise ValueError('%s: loss_k %r is not a finite, positive number' % (what, loss_k))
+    return (_ICP_LOSS_NONE if loss is None else ICP_LOSSES[loss]), k
 
 
 # ---- keypoint selection: radius NMS in score order (csrc/keypoint_nms.hip) -----------------------------------------------------------------------
