@@ -692,7 +692,7 @@ int se3_registration_metrics_stack(const int64_t* pair_table, int num_pairs, flo
  * pairs: src_points / ref_points (total, 3) float32, pair p owns rows [offsets[p], offsets[p+1]) (int64, DEVICE, num_pairs + 1 entries,
  * n_p rows).  Each pair scores H = num_iterations hypotheses of ransac_n (3..16) correspondences drawn uniformly with replacement:
  *   idx_j(h) = ((splitmix64(splitmix64(seed) + h * ransac_n + j) >> 32) * n_p) >> 32        (uint64 wrap-around; splitmix64 with the
- *   standard constants 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB -- csrc/ransac.hip), independent of the pair's position,
+ *   standard constants 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB -- csrc/splitmix.h), independent of the pair's position,
  * or taken from hypothesis_indices (DEVICE (num_pairs, H, ransac_n) int32, pair-local; an index outside [0, n_p) voids the hypothesis).
  * A hypothesis is the unweighted float64 Kabsch fit of its sample (src -> ref) rounded to float32; correspondence i is its inlier iff
  * |T s_i - r_i|^2 < distance_threshold^2 in float32.  The winner has the most inliers, then the smallest inlier error sum, then the lowest
@@ -1137,6 +1137,57 @@ int se3_fpfh_stack(const void* points, int elem, const double* spfh, const int64
 int se3_debug_fpfh_host(const void* points, const void* normals, int64_t n, int elem, int normals_elem, const int64_t* row_offsets,
                         const int64_t* pairs, int64_t total, double* out_spfh, double* out_fpfh, int* status);
 int se3_debug_fpfh_sectors_host(double* out);
+
+/* ---- Fast Global Registration of stacked pairs (csrc/fgr.hip, csrc/fgr_core.h) ------------------------------------------------------------------
+ * Open3D's registration_fgr_based_on_correspondence (Zhou, Park, Koltun, ECCV 2016: the tuple test, then graduated non-convexity over the
+ * kept correspondences, 6x6 Gauss-Newton steps) for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64, three launches and no
+ * host round trip; the contract is the header comment of csrc/fgr.hip.  Points are (rows, 3) on the device, float32 (elem 0) or float64
+ * (elem 1), promoted on load; pair p owns the source rows [src_offsets_host[p], src_offsets_host[p + 1]), the reference rows and the
+ * correspondences likewise (HOST int64, num_pairs + 1 entries from 0).  correspondences: DEVICE (K_total, 2) int64 rows of pair-local
+ * (source row, reference row), at most SE3_FGR_MAX_CORRESPONDENCES per pair (100 K trials stay below 2^31).
+ *   se3_fgr_stack           maximum_correspondence_distance finite and > 0 (compared with mu: in normalised units unless
+ *                           use_absolute_scale); division_factor finite and >= 1; iteration_number in [0, SE3_FGR_MAX_ITERATION];
+ *                           tuple_scale in (0, 1]; maximum_tuple_count in [0, SE3_FGR_MAX_TUPLE_COUNT].  out_transforms (P, 4, 4)
+ *                           float64, ref ~ T src; out_status: a sum of SE3_FGR_* bits -- NONFINITE (a non-finite coordinate: NaN
+ *                           transform), BAD_INDEX (a correspondence outside its cloud: NaN transform), EMPTY (an empty cloud or K = 0:
+ *                           identity), TOO_FEW (|C'| < 10: identity), SINGULAR (a scale that is not > 0: identity; or a 6x6 system that is
+ *                           not positive definite: that step is the identity), STEP_REFUSED (a step angle that is not finite or of 4 rad and
+ *                           more: the pair ends with what it has); out_num_correspondences |C'|; out_num_tuples the accepted trials that
+ *                           were kept (0 without the tuple test).  Optional (NULL): out_mu (P) the last mu; out_tuples
+ *                           (P, 3 maximum_tuple_count, 2) int64, pair p's C' in its first out_num_correspondences[p] rows (written by the
+ *                           tuple test alone); out_trials (P, maximum_tuple_count) int64, the kept trials' indices.  Every output is on the
+ *                           DEVICE; nothing waits on the host.  workspace: se3_fgr_workspace_bytes.
+ *   se3_debug_fgr_host      the same text for one pair on HOST memory, no GPU, run serially over the lanes: every pointer a host pointer.
+ *   se3_debug_fgr_sincos_host   the sine and cosine of the update, on n HOST values of (-4, 4): the series of the ICP update at a / 4
+ *                           and two double-angle steps. */
+enum se3_fgr_status {              /* (a NAMED enum: the binding reads it as a table of its own; the shared names carry ICP's values) */
+  SE3_FGR_NONFINITE = 1,
+  SE3_FGR_TOO_FEW = 2,
+  SE3_FGR_SINGULAR = 4,
+  SE3_FGR_EMPTY = 8,
+  SE3_FGR_STEP_REFUSED = 16,
+  SE3_FGR_BAD_INDEX = 32
+};
+enum se3_fgr_limit {               /* (NAMED too: the flat table of #defines and anonymous enumerators stays as it is) */
+  SE3_FGR_MAX_ITERATION = 1000,
+  SE3_FGR_MAX_CORRESPONDENCES = 21474836,   /* per pair: 100 K trials stay below 2^31 */
+  SE3_FGR_MAX_TUPLE_COUNT = 1000000,
+  SE3_FGR_TUPLE_CHUNK = 256,       /* trials per step of the tuple test */
+  SE3_FGR_MAX_ANGLE = 4            /* rad */
+};
+size_t se3_fgr_workspace_bytes(int num_pairs, int maximum_tuple_count, int tuple_test);
+int se3_fgr_stack(const void* src_points, int src_elem, const int64_t* src_offsets_host, const void* ref_points, int ref_elem,
+                  const int64_t* ref_offsets_host, const int64_t* correspondences, const int64_t* corr_offsets_host, int num_pairs,
+                  double maximum_correspondence_distance, double division_factor, int use_absolute_scale, int decrease_mu,
+                  int iteration_number, double tuple_scale, int maximum_tuple_count, int tuple_test, uint64_t seed, double* out_transforms,
+                  int* out_status, int* out_num_correspondences, int* out_num_tuples, double* out_mu, int64_t* out_tuples,
+                  int64_t* out_trials, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_fgr_host(const void* src_points, int64_t ns, int src_elem, const void* ref_points, int64_t nr, int ref_elem,
+                       const int64_t* correspondences, int64_t num_correspondences, double maximum_correspondence_distance,
+                       double division_factor, int use_absolute_scale, int decrease_mu, int iteration_number, double tuple_scale,
+                       int maximum_tuple_count, int tuple_test, uint64_t seed, double* out_transform, int* out_status,
+                       int* out_num_correspondences, int* out_num_tuples, double* out_mu, int64_t* out_tuples, int64_t* out_trials);
+int se3_debug_fgr_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos);
 
 #ifdef __cplusplus
 }

@@ -291,10 +291,9 @@ PG_HD bool icp_cholesky6(const double* a, const double* rhs, double* x) {
   return true;
 }
 
-// [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5]: Open3D's TransformVector6dToMatrix4d, with the shared sin and cos
-PG_HD void icp_vector6_to_matrix(const double* x, double* U) {
+// [Rz Ry Rx | x3 x4 x5] from the sines and cosines of the three angles: Open3D's TransformVector6dToMatrix4d
+PG_HD void icp_sincos_to_matrix(double sx, double cx, double sy, double cy, double sz, double cz, const double* x, double* U) {
 #pragma clang fp contract(off)
-  const double sx = icp_sin(x[0]), cx = icp_cos(x[0]), sy = icp_sin(x[1]), cy = icp_cos(x[1]), sz = icp_sin(x[2]), cz = icp_cos(x[2]);
   const double sxsy = sx * sy, cxsy = cx * sy;
   const double a01 = sxsy * cz, b01 = cx * sz, a02 = cxsy * cz, b02 = sx * sz;
   const double a11 = sxsy * sz, b11 = cx * cz, a12 = cxsy * sz, b12 = sx * cz;
@@ -302,6 +301,11 @@ PG_HD void icp_vector6_to_matrix(const double* x, double* U) {
   U[4] = cy * sz, U[5] = a11 + b11, U[6] = a12 - b12, U[7] = x[4];
   U[8] = -sy, U[9] = sx * cy, U[10] = cx * cy, U[11] = x[5];
   U[12] = 0.0, U[13] = 0.0, U[14] = 0.0, U[15] = 1.0;
+}
+
+// [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5] for angles of (-1, 1), with the shared sin and cos
+PG_HD void icp_vector6_to_matrix(const double* x, double* U) {
+  icp_sincos_to_matrix(icp_sin(x[0]), icp_cos(x[0]), icp_sin(x[1]), icp_cos(x[1]), icp_sin(x[2]), icp_cos(x[2]), x, U);
 }
 
 // Before the first evaluation: T <- T0, the results cleared; a non-finite T0, point or normal that the mode reads (point-to-plane: the

@@ -34,6 +34,7 @@
 //   ransac_select_kernel  one wave per pair: the best of its workgroups' candidates under the total order of 5, then the outputs.
 #include "common.h"
 #include "kabsch.h"
+#include "splitmix.h"          // splitmix64 and the draw of item 2, shared with csrc/fgr_core.h
 
 namespace {
 
@@ -52,13 +53,6 @@ struct Candidate {                         // a workgroup's best hypothesis (cou
   int h;
   int pad;
 };
-
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // a beats b: more inliers, then the smaller error sum, then the lower hypothesis index
 __device__ __forceinline__ bool beats(int ca, float ea, int ha, int cb, float eb, int hb) {
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(kFitThreads) void ransac_fit_kernel(const float* __
   // sample j of this hypothesis (recomputed in the second pass rather than held in a register array indexed at run time)
   auto index = [&](int j) -> int64_t {
     if (explicit_idx) return explicit_idx[((int64_t)p * H + h) * rn + j];
-    return (int64_t)(((splitmix64(key + (uint64_t)h * (uint64_t)rn + (uint64_t)j) >> 32) * (uint64_t)n) >> 32);
+    return splitmix_draw(key, (uint64_t)h, (uint64_t)rn, (uint64_t)j, (uint64_t)n);
   };
   double sc[3] = {0, 0, 0}, rc[3] = {0, 0, 0};
   for (int j = 0; j < rn && ok; j++) {

@@ -196,7 +196,7 @@ def compute_fpfh_feature(points, normals, radius=None, max_nn=None, device=None)
 def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpfh_radius=None, fpfh_max_nn=None, distance_threshold=None,
                               ransac_n=3, num_iterations=50000, mutual_filter=True, edge_length_similarity=0.9, check_distance=True,
                               icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None, icp_loss=None,
-                              icp_loss_k=None):
+                              icp_loss_k=None, coarse='ransac', fgr_distance=None, fgr_options=None):
     """The classical global registration of P pairs, a composition of the batched tools (no kernel of its own): voxel_downsample_clouds at
     voxel_size, estimate_normals_clouds (normal_knn), compute_fpfh_clouds (float32), ransac_from_feats_pairs, and with icp_distance
     icp_pairs from the RANSAC result on the downsampled clouds.  src_list / ref_list: (n, 3) float32 or float64 GPU tensors.
@@ -204,9 +204,14 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     alone for the k nearest, both for the hybrid); distance_threshold None = 1.5 voxel_size.  icp_distance None: no refinement.
     icp_estimation 'generalized' refines with generalized_icp_pairs on the normals computed here for both clouds; icp_loss / icp_loss_k:
     the robust loss kernel of either refinement (icp.icp_pairs), None for none.
-    Returns a dict: transforms (P, 4, 4) float64 on the device (ref ~ T src), ransac_transforms, src_points / ref_points / src_normals /
-    ref_normals / src_feats / ref_feats (the intermediate lists), ransac (the dict of ransac_from_feats_pairs) and icp (that of icp_pairs
-    or generalized_icp_pairs, or None)."""
+    coarse: 'ransac' (ransac_from_feats_pairs, as above) or 'fgr': fgr.fgr_from_feats_pairs on the same features, mutual matches always,
+    with maximum_correspondence_distance = fgr_distance (None: distance_threshold; in normalised units unless fgr_options says
+    use_absolute_scale) and fgr_options, a dict of further options of fgr.fgr_pairs; ransac_n, num_iterations, mutual_filter and the
+    checkers are then not read.
+    Returns a dict: transforms (P, 4, 4) float64 on the device (ref ~ T src), coarse_transforms (the coarse method's), ransac_transforms
+    (the same tensor under coarse='ransac', else None), src_points / ref_points / src_normals / ref_normals / src_feats / ref_feats (the
+    intermediate lists), ransac (the dict of ransac_from_feats_pairs, or None), fgr (the dict of fgr_from_feats_pairs, or None) and icp
+    (that of icp_pairs or generalized_icp_pairs, or None)."""
     from .icp import generalized_icp_pairs, icp_pairs
     from .ransac import ransac_from_feats_pairs
     from .scan_prep import estimate_normals_clouds, voxel_downsample_clouds
@@ -214,6 +219,8 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     P = len(src_list)
     if len(ref_list) != P:
         raise ValueError('%s: one source and one reference cloud per pair' % what)
+    if coarse not in ('ransac', 'fgr'):
+        raise ValueError("%s: coarse %r is not one of 'ransac', 'fgr'" % (what, coarse))
     v = float(voxel_size)
     if not (np.isfinite(v) and v > 0):
         raise ValueError('%s: voxel size %r is not a positive finite number' % (what, voxel_size))
@@ -226,15 +233,25 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     normals = estimate_normals_clouds(clouds, normal_knn, device=dev)
     feats = compute_fpfh_clouds(clouds, normals, fpfh_radius, fpfh_max_nn, torch.float32, device=dev)
     src, ref = clouds[:P], clouds[P:]
-    ransac = ransac_from_feats_pairs([c.to(torch.float32) for c in src], [c.to(torch.float32) for c in ref], feats[:P], feats[P:],
-                                     distance_threshold, ransac_n, num_iterations, mutual_filter, seed, edge_length_similarity, check_distance)
-    coarse = ransac['transforms'].to(torch.float64)
+    ransac, fgr = None, None
+    if coarse == 'fgr':
+        from .fgr import fgr_from_feats_pairs
+        options = dict(fgr_options or {}, maximum_correspondence_distance=distance_threshold if fgr_distance is None else fgr_distance)
+        options.setdefault('seed', seed)
+        fgr = fgr_from_feats_pairs(src, ref, feats[:P], feats[P:], device=dev, **options)
+        coarse_transforms = fgr['transforms']
+    else:
+        ransac = ransac_from_feats_pairs([c.to(torch.float32) for c in src], [c.to(torch.float32) for c in ref], feats[:P], feats[P:],
+                                         distance_threshold, ransac_n, num_iterations, mutual_filter, seed, edge_length_similarity,
+                                         check_distance)
+        coarse_transforms = ransac['transforms'].to(torch.float64)
     icp = None
     if icp_distance is not None and icp_estimation == 'generalized':
-        icp = generalized_icp_pairs(src, ref, coarse, icp_distance, normals[:P], normals[P:], loss=icp_loss, loss_k=icp_loss_k,
+        icp = generalized_icp_pairs(src, ref, coarse_transforms, icp_distance, normals[:P], normals[P:], loss=icp_loss, loss_k=icp_loss_k,
                                     max_iteration=icp_max_iteration, device=dev)
     elif icp_distance is not None:
-        icp = icp_pairs(src, ref, coarse, icp_distance, icp_estimation, normals[P:] if icp_estimation == 'point_to_plane' else None,
+        icp = icp_pairs(src, ref, coarse_transforms, icp_distance, icp_estimation, normals[P:] if icp_estimation == 'point_to_plane' else None,
                         max_iteration=icp_max_iteration, device=dev, loss=icp_loss, loss_k=icp_loss_k)
-    return {'transforms': icp['transforms'] if icp is not None else coarse, 'ransac_transforms': coarse, 'src_points': src, 'ref_points': ref,
-            'src_normals': normals[:P], 'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'icp': icp}
+    return {'transforms': icp['transforms'] if icp is not None else coarse_transforms, 'coarse_transforms': coarse_transforms,
+            'ransac_transforms': coarse_transforms if ransac is not None else None, 'src_points': src, 'ref_points': ref, 'src_normals': normals[:P],
+            'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'fgr': fgr, 'icp': icp}

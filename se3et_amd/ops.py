@@ -2608,6 +2608,58 @@ def icp_loss_of(loss, loss_k, what):
     return (_ICP_LOSS_NONE if loss is None else ICP_LOSSES[loss]), k
 
 
+# ---- Fast Global Registration of stacked pairs (csrc/fgr.hip) ------------------------------------------------------------------------------------
+FGR_STATUS = {name[len('SE3_FGR_'):].lower(): value for name, value in ENUMS['se3_fgr_status'].items()}
+FGR_MAX_ITERATION = ENUMS['se3_fgr_limit']['SE3_FGR_MAX_ITERATION']
+FGR_MAX_CORRESPONDENCES = ENUMS['se3_fgr_limit']['SE3_FGR_MAX_CORRESPONDENCES']
+FGR_MAX_TUPLE_COUNT = ENUMS['se3_fgr_limit']['SE3_FGR_MAX_TUPLE_COUNT']
+FGR_TUPLE_CHUNK = ENUMS['se3_fgr_limit']['SE3_FGR_TUPLE_CHUNK']
+FGR_MAX_ANGLE = ENUMS['se3_fgr_limit']['SE3_FGR_MAX_ANGLE']
+_ws_fgr = Workspace(1 << 20)
+
+
+def fgr_stack(src_points, src_lengths, ref_points, ref_lengths, correspondences, corr_lengths, maximum_correspondence_distance=0.025,
+              division_factor=1.4, use_absolute_scale=False, decrease_mu=True, iteration_number=64, tuple_scale=0.95,
+              maximum_tuple_count=1000, tuple_test=True, seed=0, return_tuples=False):
+    """HIP: Fast Global Registration of up to PAIR_MAX_PAIRS stacked pairs in three launches, nothing read back (se3et_amd/fgr.py has the
+    contract).  src_points / ref_points (total, 3) float32 / float64 on the device, pair p on the next src_lengths[p] / ref_lengths[p]
+    rows; correspondences (K_total, 2) int64 on the device, pair-local (src row, ref row), pair p on the next corr_lengths[p] rows.
+    Returns a dict of device tensors: transforms (P, 4, 4) float64 (ref ~ T src), status (P,) int32 (a sum of the FGR_STATUS bits),
+    num_correspondences (|C'|), num_tuples (P,) int32, mu (P,) float64, and with return_tuples under the tuple test tuples
+    (P, 3 maximum_tuple_count, 2) and trials (P, maximum_tuple_count) int64, of which pair p's first num_correspondences[p] /
+    num_tuples[p] rows are written."""
+    s, selem = _pair_points(src_points, 'src_points')
+    q, qelem = _pair_points(ref_points, 'ref_points')
+    c = _req(correspondences, torch.int64, 'correspondences', 2)
+    P = len(src_lengths)
+    if c.shape[1] != 2 or q.device != s.device or c.device != s.device or len(ref_lengths) != P or len(corr_lengths) != P:
+        raise RuntimeError('fgr_stack: correspondences must be (K, 2), and the clouds and correspondences of %d pairs on %s' % (P, s.device))
+    if any(int(k) > FGR_MAX_CORRESPONDENCES for k in corr_lengths):
+        raise RuntimeError('fgr_stack: at most %d correspondences per pair' % FGR_MAX_CORRESPONDENCES)
+    so, qo = _pair_offsets(src_lengths, s.shape[0], 'fgr_stack'), _pair_offsets(ref_lengths, q.shape[0], 'fgr_stack')
+    co = _pair_offsets(corr_lengths, c.shape[0], 'fgr_stack')
+    cap, tuple_test = int(maximum_tuple_count), bool(tuple_test)
+    dev = s.device
+    f64, i32, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    out = {'transforms': torch.empty((P, 4, 4), **f64), 'status': torch.empty((P,), **i32), 'num_correspondences': torch.empty((P,), **i32),
+           'num_tuples': torch.empty((P,), **i32), 'mu': torch.empty((P,), **f64)}
+    tuples = trials = None
+    if return_tuples and tuple_test and 0 <= cap <= FGR_MAX_TUPLE_COUNT:
+        tuples, trials = torch.empty((P, 3 * cap, 2), **i64), torch.empty((P, cap), **i64)
+    nbytes = lib().se3_fgr_workspace_bytes(P, cap, int(tuple_test))
+    stream = _stream()
+    ws = _ws_fgr.get(dev, stream.value, nbytes)
+    check(lib().se3_fgr_stack(_dp(s), selem, so, _dp(q), qelem, qo, _dp(c), co, P, float(maximum_correspondence_distance), float(division_factor),
+                              int(bool(use_absolute_scale)), int(bool(decrease_mu)), int(iteration_number), float(tuple_scale), cap,
+                              int(tuple_test), int(seed) & ((1 << 64) - 1), _dp(out['transforms']), _dp(out['status']),
+                              _dp(out['num_correspondences']), _dp(out['num_tuples']), _dp(out['mu']),
+                              None if tuples is None else _dp(tuples), None if trials is None else _dp(trials), ws.data_ptr(), nbytes, stream),
+          'se3_fgr_stack')
+    if tuples is not None:
+        out['tuples'], out['trials'] = tuples, trials
+    return out
+
+
 # ---- keypoint selection: radius NMS in score order (csrc/keypoint_nms.hip) -----------------------------------------------------------------------
 _ws_keypoint_nms = Workspace(1 << 20)
 
