@@ -945,6 +945,8 @@ int se3_linear_stream_segments(const float* x, int64_t rows, int in_features, in
  *   se3_pair_ball_count_stack   row_offsets (nq + 1) int64 on the device: the exclusive scan of the per-row hit counts, the total last.
  *   se3_pair_ball_fill_stack    out (total, 2) int64: (i, j) of every hit, rows ascending in i, j ascending within a row; row_offsets and
  *                           total as the count call left them (the same grid, points and radius).
+ *   se3_pair_ball_count_radii_stack / se3_pair_ball_fill_radii_stack   the same two passes with one radius per pair: radii_host (num_pairs)
+ *                           float64 on the HOST, each finite and >= 0 (csrc/iss.hip: clouds whose default radii differ).
  *   se3_pair_overlap_stack  out (num_pairs) float64 = count(d * d < radius * radius) / rows of the pair's nearest-neighbour distances (NaN
  *                           for a pair without rows).
  *   se3_pair_info_covariance_stack   out (num_pairs, 6, 6) float64 = sum G^T G, G = [I3 | -[p]x], over the transformed src points
@@ -963,6 +965,11 @@ int se3_pair_ball_count_stack(const void* grid_workspace, size_t workspace_bytes
 int se3_pair_ball_fill_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                              const int64_t* q_offsets_host, int num_pairs, double radius, const int64_t* row_offsets, int64_t total,
                              int64_t* out, void* stream);
+int se3_pair_ball_count_radii_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                    const int64_t* q_offsets_host, int num_pairs, const double* radii_host, int64_t* row_offsets, void* stream);
+int se3_pair_ball_fill_radii_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                   const int64_t* q_offsets_host, int num_pairs, const double* radii_host, const int64_t* row_offsets,
+                                   int64_t total, int64_t* out, void* stream);
 int se3_pair_overlap_stack(const double* nn_distances, const int64_t* q_offsets_host, int num_pairs, double radius, double* out, void* stream);
 int se3_pair_info_covariance_stack(const void* src_points, int elem, const int64_t* s_offsets_host, const double* transforms_host,
                                    const int64_t* selected, const int64_t* selected_offsets_host, int num_pairs, double* out, void* stream);
@@ -1137,6 +1144,47 @@ int se3_fpfh_stack(const void* points, int elem, const double* spfh, const int64
 int se3_debug_fpfh_host(const void* points, const void* normals, int64_t n, int elem, int normals_elem, const int64_t* row_offsets,
                         const int64_t* pairs, int64_t total, double* out_spfh, double* out_fpfh, int* status);
 int se3_debug_fpfh_sectors_host(double* out);
+
+/* ---- ISS keypoints of stacked clouds (csrc/iss.hip, csrc/iss_core.h, csrc/cov3.h) ---------------------------------------------------------------
+ * Open3D's compute_iss_keypoints (the eigenvalue ratios of a neighbourhood's scatter matrix, a radius non-maximum test on the smallest
+ * eigenvalue) for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, all float64; the contract is the header comment of csrc/iss.hip.  Points are
+ * (rows, 3) on the device, float32 (elem 0) or float64 (elem 1), promoted on load; cloud c owns rows [offsets_host[c], offsets_host[c + 1])
+ * (HOST int64, num_clouds + 1 entries from 0).  The finite check of the points is se3_fpfh_check_stack with the points in both places.
+ *   se3_iss_saliency_stack  out_saliency (n_total) float64: rows [row_begin, row_begin + row_count) from their ball lists at salient_radius,
+ *                           row_offsets (row_count + 1, from 0) and pairs (total, 2) int64 as the ball query's count and fill calls leave
+ *                           them (members ascending within a row; only column 1 is read; an entry outside its cloud zeroes the row).
+ *                           gamma_21, gamma_32 positive and finite, min_neighbors >= 1.
+ *   se3_iss_select_stack    out_mask (n_total) bytes: 1 for a keypoint, on a grid built by se3_pair_grid_build over the clouds themselves
+ *                           (identity transforms, cell_hint = the largest radius); radii_host (num_clouds) float64 on the HOST: each
+ *                           cloud's non_max_radius, finite and >= 0; saliency (n_total) as the first pass left it.
+ *   se3_debug_iss_host      the same text for one cloud on HOST memory, no GPU, in the same summation order: every pointer a host pointer.
+ *                           out_eigenvalues (n, 3: l1 >= l2 >= l3, zeros without a member or for C = 0) and out_counts (n, 2: the member
+ *                           counts at the two radii) may be NULL; *status: 0, or bit 1 for a non-finite point (nothing is computed). */
+int se3_iss_saliency_stack(const void* points, int elem, const int64_t* offsets_host, int num_clouds, int64_t row_begin, int64_t row_count,
+                           const int64_t* row_offsets, const int64_t* pairs, int64_t total, double gamma_21, double gamma_32, int min_neighbors,
+                           double* out_saliency, void* stream);
+int se3_iss_select_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                         const int64_t* q_offsets_host, int num_clouds, const double* radii_host, const double* saliency, int min_neighbors,
+                         uint8_t* out_mask, void* stream);
+int se3_debug_iss_host(const void* points, int64_t n, int elem, double salient_radius, double non_max_radius, double gamma_21, double gamma_32,
+                       int min_neighbors, double* out_saliency, double* out_eigenvalues, int64_t* out_counts, uint8_t* out_mask, int* status);
+
+/* ---- outlier removal and model resolution of stacked clouds (csrc/outliers.hip, csrc/outliers_core.h, csrc/fixed_sum.h) -----------------------
+ * Open3D's remove_statistical_outlier for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, all float64; the contract is the header comment of
+ * csrc/outliers.hip.  (remove_radius_outlier is se3_pair_grid_build and se3_pair_ball_count_stack: a row is kept iff its count > nb_points.)
+ *   se3_knn_distance_stack  out (nq) float64 on a grid built over the clouds themselves (identity transforms, cell_hint 0), from each row's
+ *                           k nearest (k in [1, SE3_KNN_MAX]): column < 0: (the sum of the roots of the list's d^2 in list order) / the
+ *                           list's length; column in [0, k): the root of that column, 0 where the list is shorter.
+ *   se3_distance_stats_stack   out_stats (num_clouds, 4) float64: mean, std, thr = mean + std_ratio std, model resolution, from the row
+ *                           values a (n_total) in the fixed summation shape of csrc/fixed_sum.h; out_mask (n_total) bytes: a > 0 and
+ *                           a < thr.  std_ratio positive and finite.
+ *   se3_debug_*_host        the same text for one cloud on HOST memory, no GPU: every pointer a host pointer; out_mask may be NULL. */
+int se3_knn_distance_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                           const int64_t* q_offsets_host, int num_clouds, int k, int column, double* out, void* stream);
+int se3_distance_stats_stack(const double* a, const int64_t* offsets_host, int num_clouds, double std_ratio, double* out_stats, uint8_t* out_mask,
+                             void* stream);
+int se3_debug_knn_distance_host(const void* points, int64_t n, int elem, int k, int column, double* out);
+int se3_debug_distance_stats_host(const double* a, int64_t n, double std_ratio, double* out_stats, uint8_t* out_mask);
 
 /* ---- Fast Global Registration of stacked pairs (csrc/fgr.hip, csrc/fgr_core.h) ------------------------------------------------------------------
  * Open3D's registration_fgr_based_on_correspondence (Zhou, Park, Koltun, ECCV 2016: the tuple test, then graduated non-convexity over the

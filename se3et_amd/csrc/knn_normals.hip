@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "cov3.h"
 #include "pair_grid.h"
 
 namespace {
@@ -31,60 +32,8 @@ namespace {
 static_assert(kPairKnnMax == SE3_KNN_MAX, "pair_grid.h and include/se3et_hip.h name one limit");
 constexpr int kKnnWaves = 4;          // query rows per workgroup
 constexpr int64_t kKnnMaxRows = (1ll << 31) / kPairKnnMax;          // out_idx and out_d2 index row * k + column below 2^31
-constexpr int kJacobiSweeps = 10;     // (a 3x3 matrix is diagonal to rounding after 5 or 6)
 
-// ---- the normal of a neighbour list: the same text on the host and on the device --------------------------------------------------------------
-// mean and covariance of m points in list order; point(t, p) gives the t-th.  C: xx, xy, xz, yy, yz, zz.
-template <class Point>
-PG_HD void kn_covariance(int m, Point&& point, double* C) {
-#pragma clang fp contract(off)
-  double s[3] = {0.0, 0.0, 0.0}, p[3];
-  for (int t = 0; t < m; t++) {
-    point(t, p);
-    s[0] += p[0], s[1] += p[1], s[2] += p[2];
-  }
-  const double mx = s[0] / (double)m, my = s[1] / (double)m, mz = s[2] / (double)m;
-  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int t = 0; t < m; t++) {
-    point(t, p);
-    const double dx = p[0] - mx, dy = p[1] - my, dz = p[2] - mz;
-    const double xx = dx * dx, xy = dx * dy, xz = dx * dz, yy = dy * dy, yz = dy * dz, zz = dz * dz;
-    a[0] += xx, a[1] += xy, a[2] += xz, a[3] += yy, a[4] += yz, a[5] += zz;
-  }
-  for (int e = 0; e < 6; e++) C[e] = a[e] / (double)m;
-}
-
-// one Jacobi rotation that annihilates a[P][Q]; R is the third index
-template <int P, int Q, int R>
-PG_HD void kn_rotate(double (&a)[3][3], double (&v)[3][3]) {
-#pragma clang fp contract(off)
-  const double apq = a[P][Q];
-  if (apq == 0.0) return;
-  const double den = 2.0 * apq;
-  const double theta = (a[Q][Q] - a[P][P]) / den;
-  const double tt = theta * theta;
-  const double root = pg_sqrt(tt + 1.0);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + root);          // (an overflowing theta gives t = 0: nothing to rotate)
-  const double t2 = t * t;
-  const double c = 1.0 / pg_sqrt(t2 + 1.0);
-  const double s = t * c;
-  const double shift = t * apq;
-  a[P][P] = a[P][P] - shift;
-  a[Q][Q] = a[Q][Q] + shift;
-  a[P][Q] = a[Q][P] = 0.0;
-  const double arp = a[R][P], arq = a[R][Q];
-  const double u0 = c * arp, u1 = s * arq, w0 = s * arp, w1 = c * arq;
-  a[R][P] = a[P][R] = u0 - u1;
-  a[R][Q] = a[Q][R] = w0 + w1;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double vp = v[k][P], vq = v[k][Q];
-    const double x0 = c * vp, x1 = s * vq, y0 = s * vp, y1 = c * vq;
-    v[k][P] = x0 - x1;
-    v[k][Q] = y0 + y1;
-  }
-}
-
+// ---- the normal of a neighbour list: the same text on the host and on the device (kn_covariance, kn_rotate, kn_jacobi: csrc/cov3.h) ---------
 // unit eigenvector of the symmetric C for its smallest eigenvalue, canonical sign; (0, 0, 1) for m < 3 or C = 0
 PG_HD void kn_normal(int m, const double* C, double* n) {
 #pragma clang fp contract(off)
@@ -92,11 +41,7 @@ PG_HD void kn_normal(int m, const double* C, double* n) {
   if (m < 3 || (C[0] == 0.0 && C[1] == 0.0 && C[2] == 0.0 && C[3] == 0.0 && C[4] == 0.0 && C[5] == 0.0)) return;
   double a[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
   double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-  for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
-    kn_rotate<0, 1, 2>(a, v);
-    kn_rotate<0, 2, 1>(a, v);
-    kn_rotate<1, 2, 0>(a, v);
-  }
+  kn_jacobi(a, v);
   double x = v[0][0], y = v[1][0], z = v[2][0], best = a[0][0];
   if (a[1][1] < best) x = v[0][1], y = v[1][1], z = v[2][1], best = a[1][1];
   if (a[2][2] < best) x = v[0][2], y = v[1][2], z = v[2][2];
@@ -119,32 +64,6 @@ PG_HD void kn_orient(const double* view, const double* p, double* n) {
   const double a = n[0] * dx, b = n[1] * dy, c = n[2] * dz;
   if ((a + b) + c < 0.0) n[0] = -n[0], n[1] = -n[1], n[2] = -n[2];
 }
-
-// the wave's list: lane t holds the t-th best entry
-struct WaveKnnList {
-  double d2, kd;
-  int j, kj, k;
-  __device__ __forceinline__ void init(int k_) { k = k_, d2 = kd = INFINITY, j = kj = kPairKnnEmpty; }
-  __device__ __forceinline__ double kth_d2() const { return kd; }
-  __device__ __forceinline__ void offer(bool valid, double cd, int cj) {
-    unsigned long long mask = __ballot(valid && pg_knn_before(cd, cj, kd, kj));
-    while (mask) {                                                               // (few: about k ln(visited / k) per row)
-      const int src = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const double bd = __shfl(cd, src);
-      const int bj = __shfl(cj, src);
-      if (!pg_knn_before(bd, bj, kd, kj)) continue;                              // (an earlier candidate of this ballot moved the k-th)
-      const int pos = __popcll(__ballot(pg_knn_before(d2, j, bd, bj)));          // entries are sorted: the lanes that stay are a prefix
-      const double ud = __shfl_up(d2, 1);
-      const int uj = __shfl_up(j, 1);
-      const int l = se3_lane();
-      if (l == pos) d2 = bd, j = bj;
-      else if (l > pos) d2 = ud, j = uj;
-      kd = __shfl(d2, k - 1);
-      kj = __shfl(j, k - 1);
-    }
-  }
-};
 
 struct KnnViewpoints {
   double v[kPairMaxPairs][3];

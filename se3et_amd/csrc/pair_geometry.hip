@@ -127,16 +127,18 @@ __global__ __launch_bounds__(kNnWaves* SE3_WAVE) void pair_nearest_kernel(PairGr
 }
 
 __global__ __launch_bounds__(kBallThreads) void pair_ball_count_kernel(PairGridView g, const void* __restrict__ q, int elem, PairRows rows,
-                                                                       int64_t nq_total, double r, double r2, int64_t* __restrict__ row_offsets) {
+                                                                       int64_t nq_total, PairRadii radii, int64_t* __restrict__ row_offsets) {
   const int64_t i = (int64_t)blockIdx.x * kBallThreads + threadIdx.x;
   if (i >= nq_total) return;
+  const int p = pg_pair_of_row(rows, i);
+  const double r = radii.r[p];
   double qv[3];
   pg_load3(q, elem, i, qv);
-  row_offsets[i] = pg_ball_count(g, pg_pair_of_row(rows, i), qv, r, r2);
+  row_offsets[i] = pg_ball_count(g, p, qv, r, r * r);
 }
 
 __global__ __launch_bounds__(kBallThreads) void pair_ball_fill_kernel(PairGridView g, const void* __restrict__ q, int elem, PairRows rows,
-                                                                      int64_t nq_total, double r, double r2, const int64_t* __restrict__ row_offsets,
+                                                                      int64_t nq_total, PairRadii radii, const int64_t* __restrict__ row_offsets,
                                                                       int64_t total, int64_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * kBallThreads + threadIdx.x;
   if (i >= nq_total) return;
@@ -145,7 +147,8 @@ __global__ __launch_bounds__(kBallThreads) void pair_ball_fill_kernel(PairGridVi
   const int p = pg_pair_of_row(rows, i);
   double qv[3];
   pg_load3(q, elem, i, qv);
-  pg_ball_fill(g, p, qv, r, r2, i - rows.start[p], out + 2 * base, room);
+  const double r = radii.r[p];
+  pg_ball_fill(g, p, qv, r, r * r, i - rows.start[p], out + 2 * base, room);
 }
 
 __global__ __launch_bounds__(kRowThreads) void pair_overlap_kernel(const double* __restrict__ dist, PairRows rows, double r2,
@@ -273,36 +276,68 @@ extern "C" int se3_pair_nearest_neighbor_stack(const void* grid_workspace, size_
   return SE3_OK;
 }
 
-extern "C" int se3_pair_ball_count_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
-                                         const int64_t* q_offsets_host, int num_pairs, double radius, int64_t* row_offsets, void* stream) {
+// the ball query's two passes with one radius per pair (radii_host: num_pairs host doubles); the entries with one radius for all fill the table
+static int ball_count(const char* name, const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                      const int64_t* q_offsets_host, int num_pairs, const double* radii_host, double radius, int64_t* row_offsets, void* stream) {
   PairGridCall c;
-  if (const int rc = pg_grid_call("pair_ball_count_stack", "pairs", q_points && row_offsets, grid_workspace, workspace_bytes,
-                                  ns_total, elem, q_offsets_host, num_pairs, 1ll << 31, &c))
+  if (const int rc = pg_grid_call(name, "pairs", q_points && row_offsets, grid_workspace, workspace_bytes, ns_total, elem, q_offsets_host,
+                                  num_pairs, 1ll << 31, &c))
     return rc;
-  SE3_REQUIRE(pg_radius_ok(radius), SE3_ERR_INVALID_ARG, "pair_ball_count_stack: radius %g", radius);
+  PairRadii radii;
+  SE3_REQUIRE(pg_fill_radii(&radii, radii_host, radius, num_pairs), SE3_ERR_INVALID_ARG, "%s: radius %g", name, pg_bad_radius(radii));
   hipStream_t st = (hipStream_t)stream;
   if (c.n_total > 0)
     pair_ball_count_kernel<<<(unsigned)se3_cdiv(c.n_total, kBallThreads), kBallThreads, 0, st>>>(c.G.view(), q_points, elem, c.rows, c.n_total,
-                                                                                                 radius, radius * radius, row_offsets);
+                                                                                                 radii, row_offsets);
   se3_exclusive_scan_i64(row_offsets, c.n_total, st);
-  SE3_CHECK_LAUNCH("pair_ball_count_stack");
+  SE3_CHECK_LAUNCH(name);
   return SE3_OK;
+}
+
+static int ball_fill(const char* name, const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                     const int64_t* q_offsets_host, int num_pairs, const double* radii_host, double radius, const int64_t* row_offsets,
+                     int64_t total, int64_t* out, void* stream) {
+  PairGridCall c;
+  if (const int rc = pg_grid_call(name, "pairs", q_points && row_offsets && (out || total == 0), grid_workspace, workspace_bytes, ns_total, elem,
+                                  q_offsets_host, num_pairs, 1ll << 31, &c))
+    return rc;
+  PairRadii radii;
+  SE3_REQUIRE(pg_fill_radii(&radii, radii_host, radius, num_pairs) && total >= 0, SE3_ERR_INVALID_ARG, "%s: radius %g, total %lld", name,
+              pg_bad_radius(radii), (long long)total);
+  if (c.n_total == 0 || total == 0) return SE3_OK;
+  pair_ball_fill_kernel<<<(unsigned)se3_cdiv(c.n_total, kBallThreads), kBallThreads, 0, (hipStream_t)stream>>>(
+      c.G.view(), q_points, elem, c.rows, c.n_total, radii, row_offsets, total, out);
+  SE3_CHECK_LAUNCH(name);
+  return SE3_OK;
+}
+
+extern "C" int se3_pair_ball_count_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                         const int64_t* q_offsets_host, int num_pairs, double radius, int64_t* row_offsets, void* stream) {
+  return ball_count("pair_ball_count_stack", grid_workspace, workspace_bytes, ns_total, q_points, elem, q_offsets_host, num_pairs, nullptr, radius,
+                    row_offsets, stream);
 }
 
 extern "C" int se3_pair_ball_fill_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
                                         const int64_t* q_offsets_host, int num_pairs, double radius, const int64_t* row_offsets, int64_t total,
                                         int64_t* out, void* stream) {
-  PairGridCall c;
-  if (const int rc = pg_grid_call("pair_ball_fill_stack", "pairs", q_points && row_offsets && (out || total == 0), grid_workspace, workspace_bytes,
-                                  ns_total, elem, q_offsets_host, num_pairs, 1ll << 31, &c))
-    return rc;
-  SE3_REQUIRE(pg_radius_ok(radius) && total >= 0, SE3_ERR_INVALID_ARG, "pair_ball_fill_stack: radius %g, total %lld", radius,
-              (long long)total);
-  if (c.n_total == 0 || total == 0) return SE3_OK;
-  pair_ball_fill_kernel<<<(unsigned)se3_cdiv(c.n_total, kBallThreads), kBallThreads, 0, (hipStream_t)stream>>>(
-      c.G.view(), q_points, elem, c.rows, c.n_total, radius, radius * radius, row_offsets, total, out);
-  SE3_CHECK_LAUNCH("pair_ball_fill_stack");
-  return SE3_OK;
+  return ball_fill("pair_ball_fill_stack", grid_workspace, workspace_bytes, ns_total, q_points, elem, q_offsets_host, num_pairs, nullptr, radius,
+                   row_offsets, total, out, stream);
+}
+
+extern "C" int se3_pair_ball_count_radii_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                               const int64_t* q_offsets_host, int num_pairs, const double* radii_host, int64_t* row_offsets,
+                                               void* stream) {
+  SE3_REQUIRE(radii_host, SE3_ERR_INVALID_ARG, "pair_ball_count_radii_stack: null pointer");
+  return ball_count("pair_ball_count_radii_stack", grid_workspace, workspace_bytes, ns_total, q_points, elem, q_offsets_host, num_pairs, radii_host,
+                    0.0, row_offsets, stream);
+}
+
+extern "C" int se3_pair_ball_fill_radii_stack(const void* grid_workspace, size_t workspace_bytes, int64_t ns_total, const void* q_points, int elem,
+                                              const int64_t* q_offsets_host, int num_pairs, const double* radii_host, const int64_t* row_offsets,
+                                              int64_t total, int64_t* out, void* stream) {
+  SE3_REQUIRE(radii_host, SE3_ERR_INVALID_ARG, "pair_ball_fill_radii_stack: null pointer");
+  return ball_fill("pair_ball_fill_radii_stack", grid_workspace, workspace_bytes, ns_total, q_points, elem, q_offsets_host, num_pairs, radii_host,
+                   0.0, row_offsets, total, out, stream);
 }
 
 extern "C" int se3_pair_overlap_stack(const double* nn_distances, const int64_t* q_offsets_host, int num_pairs, double radius, double* out,

@@ -1,5 +1,5 @@
 // Uniform float64 grid over the TRANSFORMED support cloud of each pair of a stacked call, and the search core that every tool on it shares:
-// csrc/pair_geometry.hip (which also owns the device build, se3_pair_grid_build), knn_normals.hip, icp.hip, keypoint_nms.hip and fpfh.hip.
+// csrc/pair_geometry.hip (which also owns the device build, se3_pair_grid_build), knn_normals.hip, icp.hip, keypoint_nms.hip, fpfh.hip, iss.hip and outliers.hip.
 //
 // The grid is only an accelerator: every answer is defined by the arithmetic contract in pair_geometry.hip (transform by the documented fma
 // chain, d^2 = (dx dx + dy dy) + dz dz unfused, strict tests, the lowest index among equal distances), and the walks below visit every
@@ -312,6 +312,32 @@ struct PairKnnSerialList {
   }
 };
 
+// the list of a kernel that searches with one wave per query row (knn_normals.hip, outliers.hip): lane t holds the t-th best entry
+struct WaveKnnList {
+  double d2, kd;
+  int j, kj, k;
+  __device__ __forceinline__ void init(int k_) { k = k_, d2 = kd = INFINITY, j = kj = kPairKnnEmpty; }
+  __device__ __forceinline__ double kth_d2() const { return kd; }
+  __device__ __forceinline__ void offer(bool valid, double cd, int cj) {
+    unsigned long long mask = __ballot(valid && pg_knn_before(cd, cj, kd, kj));
+    while (mask) {                                                               // (few: about k ln(visited / k) per row)
+      const int src = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const double bd = __shfl(cd, src);
+      const int bj = __shfl(cj, src);
+      if (!pg_knn_before(bd, bj, kd, kj)) continue;                              // (an earlier candidate of this ballot moved the k-th)
+      const int pos = __popcll(__ballot(pg_knn_before(d2, j, bd, bj)));          // entries are sorted: the lanes that stay are a prefix
+      const double ud = __shfl_up(d2, 1);
+      const int uj = __shfl_up(j, 1);
+      const int l = se3_lane();
+      if (l == pos) d2 = bd, j = bj;
+      else if (l > pos) d2 = ud, j = uj;
+      kd = __shfl(d2, k - 1);
+      kj = __shfl(j, k - 1);
+    }
+  }
+};
+
 // ---- host side: the workspace, the entry check, the serial build ------------------------------------------------------------------------------
 struct PairGridLayout {
   PairGridMeta* meta;
@@ -359,6 +385,26 @@ inline int pg_grid_call(const char* name, const char* unit, bool pointers, const
 }
 
 inline bool pg_radius_ok(double radius) { return isfinite(radius) && radius >= 0.0; }
+
+// one ball radius per pair of a stacked call, passed to kernels by value
+struct PairRadii {
+  double r[kPairMaxPairs];
+};
+// radii_host[0, num_pairs), or `radius` for every pair when radii_host is NULL; false unless every radius is finite and >= 0
+inline bool pg_fill_radii(PairRadii* radii, const double* radii_host, double radius, int num_pairs) {
+  bool ok = true;
+  for (int p = 0; p < kPairMaxPairs; p++) {
+    radii->r[p] = radii_host ? (p < num_pairs ? radii_host[p] : 0.0) : radius;
+    ok = ok && pg_radius_ok(radii->r[p]);
+  }
+  return ok;
+}
+// the first radius that pg_fill_radii refused (for the message)
+inline double pg_bad_radius(const PairRadii& radii) {
+  for (int p = 0; p < kPairMaxPairs; p++)
+    if (!pg_radius_ok(radii.r[p])) return radii.r[p];
+  return 0.0;
+}
 
 // The grid build on host memory, serial, over a workspace laid out by pg_carve in `base` (the debug entries).
 inline void pg_build_host(const void* s_points, int elem, const PairRows& rows, const double* transforms, double cell_hint, PairGridLayout& G) {

@@ -5,7 +5,8 @@ fed with, as batched HIP kernels (csrc/fpfh.hip, csrc/fpfh_core.h) on the search
   compute_fpfh_clouds(points_list, normals_list, radius=None, max_nn=None, dtype=torch.float64)   list of (n_c, 33) tensors on the device
   spfh_clouds(points_list, normals_list, radius=None, max_nn=None)                                the first pass alone, float64
   compute_fpfh_feature(points, normals, radius=None, max_nn=None)                                 one cloud, numpy in, (n, 33) numpy out
-  global_registration_pairs(src_list, ref_list, voxel_size, ...)                                  downsample, normals, FPFH, RANSAC, ICP
+  global_registration_pairs(src_list, ref_list, voxel_size, ...)                                  (outlier removal,) downsample, normals, FPFH,
+                                                                                                  (ISS keypoints,) RANSAC or FGR, ICP
 
 The batched calls take GPU tensors only (there is no CPU path): points and normals (n, 3) float32 or float64, promoted on load; any number
 of clouds per call, chunked at the library's SE3_PAIR_MAX_PAIRS clouds and, within a chunk, at PAIR_BUDGET neighbour-list entries (16
@@ -88,19 +89,22 @@ def _refuse(what, a, words):
                                                    for c, w in enumerate(words[:-1]) if w))
 
 
-def _radius_lists(p, pl, r, words, what, a):
+def _radius_lists(p, pl, r, words, what, a, budget=None):
     """The chunk's neighbour lists from the ball query: a function that yields (row_begin, row_offsets, pairs) per slice of at most
-    PAIR_BUDGET entries (half of it plus one row's, where a chunk is cut), and whether there is more than one slice."""
+    PAIR_BUDGET entries (half of it plus one row's, where a chunk is cut), and whether there is more than one slice.  r: one radius, or
+    a list of one per cloud; budget: another family's own budget in place of PAIR_BUDGET (se3et_amd/iss.py runs its saliency pass over
+    the same lists, with a radius per cloud)."""
     n, offsets = p.shape[0], exclusive_offsets(pl)
-    grid = _ops.pair_grid_build(p, pl, identities(len(pl)), r)
+    budget = PAIR_BUDGET if budget is None else budget
+    grid = _ops.pair_grid_build(p, pl, identities(len(pl)), max(r, default=0.0) if isinstance(r, list) else r)
     ro = _ops.pair_ball_count_stack(grid, p, pl, r)
     host = torch.cat([ro[-1:], words.to(torch.int64)]).cpu().tolist()           # the ONE synchronisation of the chunk: the total, the status
     _refuse(what, a, host[1:])
     total = host[0]
-    if total <= PAIR_BUDGET:
+    if total <= budget:
         cuts, at = [0, n], [0, total]
     else:
-        half = max(1, PAIR_BUDGET // 2)
+        half = max(1, budget // 2)
         targets = torch.arange(half, total, half, dtype=torch.int64, device=p.device)
         rows = (torch.searchsorted(ro, targets, right=True) - 1).clamp(1, n)
         rows = torch.unique(torch.cat([rows.new_zeros(1), rows, rows.new_full((1,), n)]))
@@ -196,7 +200,8 @@ def compute_fpfh_feature(points, normals, radius=None, max_nn=None, device=None)
 def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpfh_radius=None, fpfh_max_nn=None, distance_threshold=None,
                               ransac_n=3, num_iterations=50000, mutual_filter=True, edge_length_similarity=0.9, check_distance=True,
                               icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None, icp_loss=None,
-                              icp_loss_k=None, coarse='ransac', fgr_distance=None, fgr_options=None):
+                              icp_loss_k=None, coarse='ransac', fgr_distance=None, fgr_options=None, outlier_removal=None, keypoints=None,
+                              iss_options=None):
     """The classical global registration of P pairs, a composition of the batched tools (no kernel of its own): voxel_downsample_clouds at
     voxel_size, estimate_normals_clouds (normal_knn), compute_fpfh_clouds (float32), ransac_from_feats_pairs, and with icp_distance
     icp_pairs from the RANSAC result on the downsampled clouds.  src_list / ref_list: (n, 3) float32 or float64 GPU tensors.
@@ -208,10 +213,16 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     with maximum_correspondence_distance = fgr_distance (None: distance_threshold; in normalised units unless fgr_options says
     use_absolute_scale) and fgr_options, a dict of further options of fgr.fgr_pairs; ransac_n, num_iterations, mutual_filter and the
     checkers are then not read.
+    outlier_removal: None, ('statistical', nb_neighbors, std_ratio) or ('radius', nb_points, radius): scan_prep's filter of that name on
+    the raw clouds before the voxel downsampling.  keypoints: None or 'iss': iss.iss_keypoints_clouds (iss_options: a dict of its
+    arguments) on the downsampled clouds; normals and FPFH are still computed on the whole downsampled clouds (the neighbourhoods need
+    them), only the keypoint rows of points and features go to the coarse method, and ICP refines on the whole downsampled clouds.
     Returns a dict: transforms (P, 4, 4) float64 on the device (ref ~ T src), coarse_transforms (the coarse method's), ransac_transforms
     (the same tensor under coarse='ransac', else None), src_points / ref_points / src_normals / ref_normals / src_feats / ref_feats (the
     intermediate lists), ransac (the dict of ransac_from_feats_pairs, or None), fgr (the dict of fgr_from_feats_pairs, or None) and icp
-    (that of icp_pairs or generalized_icp_pairs, or None)."""
+    (that of icp_pairs or generalized_icp_pairs, or None).  A call with outlier_removal or keypoints adds four keys: src_keypoints /
+    ref_keypoints (the lists of keypoint indices into src_points / ref_points, None without a detector) and src_kept / ref_kept (the
+    lists of the raw rows the outlier filter kept, None without one); a call with neither returns exactly the keys above."""
     from .icp import generalized_icp_pairs, icp_pairs
     from .ransac import ransac_from_feats_pairs
     from .scan_prep import estimate_normals_clouds, voxel_downsample_clouds
@@ -221,6 +232,11 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
         raise ValueError('%s: one source and one reference cloud per pair' % what)
     if coarse not in ('ransac', 'fgr'):
         raise ValueError("%s: coarse %r is not one of 'ransac', 'fgr'" % (what, coarse))
+    if keypoints not in (None, 'iss'):
+        raise ValueError("%s: keypoints %r is not None or 'iss'" % (what, keypoints))
+    if outlier_removal is not None and (len(outlier_removal) != 3 or outlier_removal[0] not in ('statistical', 'radius')):
+        raise ValueError("%s: outlier_removal %r is not None, ('statistical', nb_neighbors, std_ratio) or ('radius', nb_points, radius)"
+                         % (what, outlier_removal))
     v = float(voxel_size)
     if not (np.isfinite(v) and v > 0):
         raise ValueError('%s: voxel size %r is not a positive finite number' % (what, voxel_size))
@@ -229,10 +245,22 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     if distance_threshold is None:
         distance_threshold = 1.5 * v
     dev = device_of(device, src_list, ref_list)
-    clouds = voxel_downsample_clouds(list(src_list) + list(ref_list), v, device=dev)
+    raw, kept = list(src_list) + list(ref_list), None
+    if outlier_removal is not None:
+        from .scan_prep import remove_radius_outlier_clouds, remove_statistical_outlier_clouds
+        remove = remove_statistical_outlier_clouds if outlier_removal[0] == 'statistical' else remove_radius_outlier_clouds
+        kept = remove(raw, outlier_removal[1], outlier_removal[2], device=dev)
+        raw = [c[k] for c, k in zip(raw, kept)]
+    clouds = voxel_downsample_clouds(raw, v, device=dev)
     normals = estimate_normals_clouds(clouds, normal_knn, device=dev)
     feats = compute_fpfh_clouds(clouds, normals, fpfh_radius, fpfh_max_nn, torch.float32, device=dev)
     src, ref = clouds[:P], clouds[P:]
+    keys, full = None, (src, ref, feats)
+    if keypoints == 'iss':
+        from .iss import iss_keypoints_clouds
+        keys = iss_keypoints_clouds(clouds, device=dev, **(iss_options or {}))
+        src, ref = [c[k] for c, k in zip(src, keys[:P])], [c[k] for c, k in zip(ref, keys[P:])]
+        feats = [f[k] for f, k in zip(feats, keys)]
     ransac, fgr = None, None
     if coarse == 'fgr':
         from .fgr import fgr_from_feats_pairs
@@ -245,6 +273,7 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
                                          distance_threshold, ransac_n, num_iterations, mutual_filter, seed, edge_length_similarity,
                                          check_distance)
         coarse_transforms = ransac['transforms'].to(torch.float64)
+    src, ref, feats = full
     icp = None
     if icp_distance is not None and icp_estimation == 'generalized':
         icp = generalized_icp_pairs(src, ref, coarse_transforms, icp_distance, normals[:P], normals[P:], loss=icp_loss, loss_k=icp_loss_k,
@@ -252,6 +281,10 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     elif icp_distance is not None:
         icp = icp_pairs(src, ref, coarse_transforms, icp_distance, icp_estimation, normals[P:] if icp_estimation == 'point_to_plane' else None,
                         max_iteration=icp_max_iteration, device=dev, loss=icp_loss, loss_k=icp_loss_k)
-    return {'transforms': icp['transforms'] if icp is not None else coarse_transforms, 'coarse_transforms': coarse_transforms,
-            'ransac_transforms': coarse_transforms if ransac is not None else None, 'src_points': src, 'ref_points': ref, 'src_normals': normals[:P],
-            'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'fgr': fgr, 'icp': icp}
+    out = {'transforms': icp['transforms'] if icp is not None else coarse_transforms, 'coarse_transforms': coarse_transforms,
+           'ransac_transforms': coarse_transforms if ransac is not None else None, 'src_points': src, 'ref_points': ref, 'src_normals': normals[:P],
+           'ref_normals': normals[P:], 'src_feats': feats[:P], 'ref_feats': feats[P:], 'ransac': ransac, 'fgr': fgr, 'icp': icp}
+    if keypoints is not None or outlier_removal is not None:
+        out.update(src_keypoints=keys[:P] if keys is not None else None, ref_keypoints=keys[P:] if keys is not None else None,
+                   src_kept=kept[:P] if kept is not None else None, ref_kept=kept[P:] if kept is not None else None)
+    return out

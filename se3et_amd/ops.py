@@ -2363,10 +2363,25 @@ def pair_nearest_neighbor_stack(grid, q_points, q_lengths):
     return dist, idx
 
 
+def _pair_radii(radius, P, what):
+    """None for one radius, else the (P,) float64 host array of a radius per pair."""
+    if not isinstance(radius, (list, tuple)):
+        return None
+    if len(radius) != P:
+        raise RuntimeError('%s: one radius per pair: %d given for %d pairs' % (what, len(radius), P))
+    return (ctypes.c_double * max(P, 1))(*[float(r) for r in radius])
+
+
 def pair_ball_count_stack(grid, q_points, q_lengths, radius):
-    """HIP: pass 1 of the ball query.  Returns row_offsets (nq + 1,) int64 on the device: the exclusive scan of the hits per query row."""
+    """HIP: pass 1 of the ball query.  radius: one number, or a list of one per pair.  Returns row_offsets (nq + 1,) int64 on the device:
+    the exclusive scan of the hits per query row."""
     q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'pair_ball_count_stack')
     row_offsets = torch.empty((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
+    radii = _pair_radii(radius, grid.num_pairs, 'pair_ball_count_stack')
+    if radii is not None:
+        check(lib().se3_pair_ball_count_radii_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, radii,
+                                                    row_offsets.data_ptr(), _stream()), 'se3_pair_ball_count_radii_stack')
+        return row_offsets
     check(lib().se3_pair_ball_count_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
                                           float(radius), row_offsets.data_ptr(), _stream()), 'se3_pair_ball_count_stack')
     return row_offsets
@@ -2379,6 +2394,11 @@ def pair_ball_fill_stack(grid, q_points, q_lengths, radius, row_offsets, total):
     if row_offsets.shape[0] != q.shape[0] + 1 or row_offsets.device != q.device:
         raise RuntimeError('pair_ball_fill_stack: row_offsets of pair_ball_count_stack expected')
     out = torch.empty((int(total), 2), dtype=torch.int64, device=q.device)
+    radii = _pair_radii(radius, grid.num_pairs, 'pair_ball_fill_stack')
+    if radii is not None:
+        check(lib().se3_pair_ball_fill_radii_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, radii,
+                                                   row_offsets.data_ptr(), int(total), _dp(out), _stream()), 'se3_pair_ball_fill_radii_stack')
+        return out
     check(lib().se3_pair_ball_fill_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
                                          float(radius), row_offsets.data_ptr(), int(total), _dp(out), _stream()),
           'se3_pair_ball_fill_stack')
@@ -2741,3 +2761,67 @@ def fpfh_stack(points, spfh, lengths, row_offsets, pairs, out, row_begin=0):
     check(lib().se3_fpfh_stack(_dp(p), elem, _dp(spfh), offsets, len(lengths), int(row_begin), rows, ro.data_ptr(), _dp(pr), pr.shape[0], _dp(out),
                                _stream()), 'se3_fpfh_stack')
     return out
+
+
+# ---- ISS keypoints of stacked clouds (csrc/iss.hip) --------------------------------------------------------------------------------------------------
+def points_check_stack(points, lengths):
+    """HIP: the finite check of stacked clouds without normals (se3_fpfh_check_stack with the points in both places).  Returns words
+    (len(lengths) + 1,) int32 on the DEVICE: bit 1 of word c for a non-finite point of cloud c, the last word the OR of all."""
+    return fpfh_check_stack(points, points, lengths)
+
+
+def iss_saliency_stack(points, lengths, row_offsets, pairs, gamma_21, gamma_32, min_neighbors, out, row_begin=0):
+    """HIP: the ISS saliencies of rows [row_begin, row_begin + len(row_offsets) - 1) of stacked clouds into out (total rows,) float64, from
+    the ball lists at the salient radius (row_offsets from 0, pairs (total, 2) int64 as pair_ball_fill_stack leaves them)."""
+    p, elem = _pair_points(points, 'points')
+    offsets = _pair_offsets(lengths, p.shape[0], 'iss_saliency_stack')
+    ro, pr, rows = _fpfh_list(row_offsets, pairs, row_begin, p.shape[0], p.device, 'iss_saliency_stack')
+    if tuple(out.shape) != (p.shape[0],) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != p.device:
+        raise RuntimeError('iss_saliency_stack: out must be (%d,) float64 on %s' % (p.shape[0], p.device))
+    check(lib().se3_iss_saliency_stack(_dp(p), elem, offsets, len(lengths), int(row_begin), rows, ro.data_ptr(), _dp(pr), pr.shape[0],
+                                       float(gamma_21), float(gamma_32), int(min_neighbors), _dp(out), _stream()), 'se3_iss_saliency_stack')
+    return out
+
+
+def iss_select_stack(grid, points, lengths, radii, saliency, min_neighbors):
+    """HIP: the ISS selection.  grid: pair_grid_build over the clouds themselves with identity transforms and cell_hint = the largest
+    radius; radii: each cloud's non_max_radius (a list), or one number for all.  Returns the mask (total rows,) uint8: 1 for a keypoint."""
+    q, elem, offsets = _pair_query(grid, points, lengths, 'iss_select_stack')
+    s = _req(saliency, torch.float64, 'saliency', 1)
+    if s.shape[0] != q.shape[0] or s.device != q.device or grid.ns_total != q.shape[0]:
+        raise RuntimeError('iss_select_stack: one saliency per row, on %s, and a grid over the same %d rows expected' % (q.device, q.shape[0]))
+    mask = torch.empty((q.shape[0],), dtype=torch.uint8, device=q.device)
+    check(lib().se3_iss_select_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs,
+                                     _pair_radii(list(radii) if isinstance(radii, (list, tuple)) else [radii] * grid.num_pairs, grid.num_pairs, 'iss_select_stack'), _dp(s),
+                                     int(min_neighbors), _dp(mask), _stream()), 'se3_iss_select_stack')
+    return mask
+
+
+# ---- outlier removal and model resolution of stacked clouds (csrc/outliers.hip) -----------------------------------------------------------------
+DISTANCE_STATS = 4          # per cloud: mean, std, thr, model resolution
+
+
+def knn_distance_stack(grid, q_points, q_lengths, k, column=-1):
+    """HIP: one float64 per row from its k nearest in its own cloud of `grid` (pair_grid_build with identity transforms and cell_hint 0):
+    column < 0: the mean of the list's distances (the row itself at 0 among them); column >= 0: the distance of that column, 0 where the
+    list is shorter."""
+    q, elem, offsets = _pair_query(grid, q_points, q_lengths, 'knn_distance_stack')
+    k = _knn_k(k, 'knn_distance_stack')
+    if int(column) >= k:
+        raise RuntimeError('knn_distance_stack: column %d not below k = %d' % (column, k))
+    out = torch.empty((q.shape[0],), dtype=torch.float64, device=q.device)
+    check(lib().se3_knn_distance_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, k, int(column),
+                                       _dp(out), _stream()), 'se3_knn_distance_stack')
+    return out
+
+
+def distance_stats_stack(a, lengths, std_ratio=1.0):
+    """HIP: (stats (clouds, 4) float64: mean, std, thr = mean + std_ratio std, model resolution; mask (total rows,) uint8: a > 0 and
+    a < thr) of the stacked row values a, in the fixed summation shape of csrc/fixed_sum.h."""
+    a = _req(a, torch.float64, 'a', 1)
+    offsets = _pair_offsets(lengths, a.shape[0], 'distance_stats_stack')
+    stats = torch.empty((len(lengths), DISTANCE_STATS), dtype=torch.float64, device=a.device)
+    mask = torch.empty((a.shape[0],), dtype=torch.uint8, device=a.device)
+    check(lib().se3_distance_stats_stack(_dp(a), offsets, len(lengths), float(std_ratio), _dp(stats), _dp(mask), _stream()),
+          'se3_distance_stats_stack')
+    return stats, mask

@@ -6,7 +6,10 @@ csrc/pair_grid.h) in place of Open3D's host passes.
   knn_clouds(support_list, k, queries_list=None)                        lists of (n, k) int64 indices and (n, k) float64 squared distances
   estimate_normals_clouds(points_list, knn=33, viewpoints=None)         list of (n, 3) float64
   regularize_normals(points, normals, positive=True)                    tensor or numpy
+  remove_statistical_outlier_clouds(points_list, nb_neighbors=20, std_ratio=2.0, return_stats=False)   list of kept-row index tensors, ascending
+  remove_radius_outlier_clouds(points_list, nb_points, radius)          the same
   voxel_downsample / estimate_normals                                   the reference's names and signatures: one cloud, numpy in and out
+  remove_statistical_outlier / remove_radius_outlier                    Open3D's names: one cloud, numpy in, (points, indices) out
 
 The batched calls take GPU tensors only (there is no CPU path), any number of clouds per call, and chunk internally at the library's
 SE3_PAIR_MAX_PAIRS clouds per launch; voxel_downsample_clouds synchronises with the host once per chunk (the output counts and the status
@@ -38,6 +41,24 @@ Normals (knn = 33 by default).  Over the row's m = min(knn, n) neighbours in lis
 C = sum (p - mean)(p - mean)^T / m are each a sequential sum in list order, contraction off.  The normal is a unit eigenvector of C for its
 smallest eigenvalue, in float64, with the canonical sign: z > 0, or z == 0 and y > 0, or z == y == 0 and x > 0.  It is exactly (0, 0, 1)
 when m < 3 or C is the zero matrix (Open3D's fallback).  With viewpoints each normal is then oriented so that n . (viewpoint - p) >= 0.
+Statistical outlier removal (csrc/outliers.hip carries the same text), Open3D's RemoveStatisticalOutliers including its quirks; float64,
+contraction off, float32 points promoted on load.
+  Per-row mean distance.  m = min(nb_neighbors, n); the row's list is knn_clouds' (the m nearest INCLUDING the row itself at d = 0,
+    (d^2, index) ascending); a_i = (the sequential sum in list order of the roots of d2_t) / m.
+  Cloud mean.  mean = (sum of a_i over the rows with a_i > 0) / n.
+  Standard deviation.  std = sqrt((sum over the same rows of (a_i - mean)^2) / (n - 1)).
+  Threshold and test.  thr = mean + std_ratio std (the product rounded, then the sum).  A row is kept iff a_i > 0 and a_i < thr.
+  Summation.  Both cloud sums have the shape of csrc/fixed_sum.h: lane l of 256 adds its rows l, l + 256, .. in ascending order from 0.0
+    (a row with a_i <= 0 adds nothing), then sh[l] = sh[l] + sh[l + o] for o = 128, 64, .., 1; the sum is sh[0].
+  Small clouds.  n < 2 keeps nothing: n = 1 has a_0 = 0; the statistics of n = 0 and the std of n = 1 are NaN, as the formulas give.
+  Arguments.  nb_neighbors in [1, SE3_KNN_MAX = 64], std_ratio positive and finite; anything else is a ValueError.  A non-finite point is
+    a ValueError naming the cloud (a device flag, read with the clouds' cuts after the kernels).
+  Determinism.  No float atomics: a cloud's values are bit-identical alone, anywhere in a batch, and from run to run.
+Radius outlier removal: a row is kept iff the member count of its radius ball (d^2 < r r strict, r r in float64, the row itself and
+duplicates included) is > nb_points: Open3D's strict test on the project's strict ball; pair_grid_build and pair_ball_count_stack, exact
+integer work, no kernel of its own.  radius positive and finite, nb_points an integer >= 0.
+Both filters return indices; the compaction of the mask is a nonzero on the device and one small copy of the clouds' cuts per chunk.
+
 regularize_normals reproduces utils/pointcloud.py:25-37 literally: dot = -sum p n, direction = dot > 0 strict, so a row with dot == 0 is
 flipped for positive=True.
 This is not Open3D's arithmetic (single-pass cumulants and an analytic 3x3 solver; here two passes and a cyclic Jacobi iteration): only a
@@ -47,7 +68,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from .stacking import chunks, device_of, gpu_rows_each, identities, lengths, stack, upload
+from .stacking import chunks, device_of, gpu_rows_each, identities, lengths, mask_indices, stack, upload
 
 _FAMILY = 'scan preparation'
 _STATUS = {1: 'a point (or normal) is not finite', 2: 'an axis would need 2^21 voxels or more at this voxel size'}
@@ -125,6 +146,60 @@ def estimate_normals_clouds(points_list, knn=33, viewpoints=None, device=None):
     return out
 
 
+def _refuse_points(what, a, words):
+    if words[-1]:
+        raise ValueError('%s: ' % what + '; '.join('cloud %d: a point is not finite' % (a + c) for c, w in enumerate(words[:-1]) if w))
+
+
+@torch.no_grad()
+def remove_statistical_outlier_clouds(points_list, nb_neighbors=20, std_ratio=2.0, return_stats=False, device=None):
+    """Open3D's remove_statistical_outlier for a list of clouds.  Returns the list of kept-row index tensors (int64, ascending, on the
+    device), and with return_stats a (clouds, 3) float64 tensor of mean, std and thr."""
+    what = 'remove_statistical_outlier_clouds'
+    if int(nb_neighbors) != nb_neighbors or not 1 <= int(nb_neighbors) <= _ops.KNN_MAX:
+        raise ValueError("%s: nb_neighbors %r is not an integer in [1, SE3_KNN_MAX = %d]" % (what, nb_neighbors, _ops.KNN_MAX))
+    ratio = float(std_ratio)
+    if not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError('%s: std_ratio %r is not a positive finite number' % (what, std_ratio))
+    dev = device_of(device, points_list)
+    pts = gpu_rows_each(points_list, dev, what + ': cloud', _FAMILY)
+    kept, stats = [], []
+    for a, b in chunks(len(pts)):
+        p, pl = stack(pts[a:b]), lengths(pts[a:b])
+        words = _ops.points_check_stack(p, pl)
+        grid = _ops.pair_grid_build(p, pl, identities(b - a), 0.0)
+        st, mask = _ops.distance_stats_stack(_ops.knn_distance_stack(grid, p, pl, int(nb_neighbors), -1), pl, ratio)
+        kept += mask_indices(mask, pl)
+        _refuse_points(what, a, words.cpu().tolist())
+        stats.append(st[:, :3])
+    if not return_stats:
+        return kept
+    return kept, torch.cat(stats) if stats else torch.zeros((0, 3), dtype=torch.float64, device=dev)
+
+
+@torch.no_grad()
+def remove_radius_outlier_clouds(points_list, nb_points, radius, device=None):
+    """Open3D's remove_radius_outlier for a list of clouds: the rows whose radius ball holds more than nb_points members, itself
+    included.  Returns the list of kept-row index tensors (int64, ascending, on the device)."""
+    what = 'remove_radius_outlier_clouds'
+    if int(nb_points) != nb_points or int(nb_points) < 0:
+        raise ValueError('%s: nb_points %r is not an integer >= 0' % (what, nb_points))
+    r = float(radius)
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError('%s: radius %r is not a positive finite number' % (what, radius))
+    dev = device_of(device, points_list)
+    pts = gpu_rows_each(points_list, dev, what + ': cloud', _FAMILY)
+    kept = []
+    for a, b in chunks(len(pts)):
+        p, pl = stack(pts[a:b]), lengths(pts[a:b])
+        words = _ops.points_check_stack(p, pl)
+        grid = _ops.pair_grid_build(p, pl, identities(b - a), r)
+        ro = _ops.pair_ball_count_stack(grid, p, pl, r)
+        kept += mask_indices(ro[1:] - ro[:-1] > int(nb_points), pl)
+        _refuse_points(what, a, words.cpu().tolist())
+    return kept
+
+
 def regularize_normals(points, normals, positive=True):
     """utils/pointcloud.py:25-37, literally, on tensors or numpy arrays: dot = -sum p n, direction = dot > 0 (strict: a row with dot == 0
     is flipped for positive=True)."""
@@ -149,3 +224,17 @@ def voxel_downsample(points, voxel_size, normals=None, device=None):
 def estimate_normals(points, knn=33, device=None):
     """geotransformer.utils.open3d.estimate_normals: (n, 3) float64 numpy."""
     return estimate_normals_clouds([upload(points, device)], knn)[0].cpu().numpy()
+
+
+def remove_statistical_outlier(points, nb_neighbors=20, std_ratio=2.0, device=None):
+    """Open3D's remove_statistical_outlier on one cloud: (the kept points (k, 3), their row indices (k,) int64), numpy."""
+    p = np.asarray(points).reshape(-1, 3)
+    idx = remove_statistical_outlier_clouds([upload(p, device)], nb_neighbors, std_ratio)[0].cpu().numpy()
+    return p[idx], idx
+
+
+def remove_radius_outlier(points, nb_points, radius, device=None):
+    """Open3D's remove_radius_outlier on one cloud: (the kept points (k, 3), their row indices (k,) int64), numpy."""
+    p = np.asarray(points).reshape(-1, 3)
+    idx = remove_radius_outlier_clouds([upload(p, device)], nb_points, radius)[0].cpu().numpy()
+    return p[idx], idx

@@ -8,6 +8,7 @@ scan_prep, icp, feature_matching, ransac, benchmark and the stacked wrappers of 
   upload(array, device, cols, dtype)            numpy -> device, for the numpy-in, numpy-out wrappers
   exclusive_offsets / device_offsets            [0, n0, n0 + n1, ...] as a Python list / as int64 on the device (to_device)
   lengths / stack / chunks                      stacking a chunk's tensors or joining the chunks' results, and the chunk bounds
+  mask_indices(mask, counts)                    a stacked byte mask -> the list of each cloud's ascending local indices (nonzero on the device)
   transforms_of / identities                    one (4, 4) transform per pair from a tensor, an array, a list of either, or None
 
 The two input contracts stay apart: pair ground truth, scan preparation, ICP and feature matching refuse what is not a GPU tensor of the
@@ -100,6 +101,15 @@ def stack(tensors, empty=None):
     if any(t.dtype != tensors[0].dtype for t in tensors):
         tensors = [t.to(torch.float64) for t in tensors]
     return torch.cat(tensors, 0)
+
+
+def mask_indices(mask, counts):
+    """The cloud-local indices of the set bytes of a stacked mask, ascending, int64, one tensor per cloud.  The compaction is one nonzero
+    on the device (which waits for its size) and one small copy of the clouds' cuts."""
+    offsets = exclusive_offsets(counts)
+    idx = torch.nonzero(mask).reshape(-1)
+    cuts = torch.searchsorted(idx, to_device(offsets, torch.int64, mask.device)).cpu().tolist()
+    return [idx[cuts[c]:cuts[c + 1]] - offsets[c] for c in range(len(counts))]
 
 
 def chunks(P, limit=PAIR_MAX_PAIRS):
