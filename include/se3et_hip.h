@@ -1237,6 +1237,82 @@ int se3_debug_fgr_host(const void* src_points, int64_t ns, int src_elem, const v
                        int* out_num_correspondences, int* out_num_tuples, double* out_mu, int64_t* out_tuples, int64_t* out_trials);
 int se3_debug_fgr_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos);
 
+/* ---- Multiway registration: information matrices and pose graphs (csrc/pose_graph.hip, csrc/pose_graph_core.h) ------------------------------
+ * Open3D's get_information_matrix_from_point_clouds and global_optimization (GlobalOptimization.cpp: Levenberg-Marquardt with a line
+ * process, pruning, a second optimisation) for up to SE3_PAIR_MAX_PAIRS stacked pairs / graphs per call, all float64, nothing read back;
+ * the contract is the header comment of csrc/pose_graph.hip.
+ *   se3_pair_information_stack   grid: se3_pair_grid_build over the REFERENCE clouds with identity transforms and cell_hint = the
+ *                           correspondence distance; src_points (rows, 3) float32 (elem 0) / float64 (elem 1) on the device, pair p on
+ *                           rows [src_offsets_host[p], src_offsets_host[p + 1]); transforms (P, 4, 4) float64 on the DEVICE, ref ~ T src.
+ *                           out_information (P, 6, 6) float64, out_count (P) float64 (= information[5][5]), out_status (P): NONFINITE (a NaN
+ *                           matrix) or EMPTY (the zero matrix).  workspace: se3_pair_information_workspace_bytes.
+ *   se3_debug_pair_information_host   the same text for one pair on HOST memory; out_correspondences (n) int64 or NULL: the reference row of
+ *                           every source row, -1 for none.
+ *   se3_pose_graph_optimize_stack   graph g owns the nodes [node_offsets_host[g], node_offsets_host[g + 1]) of poses (nodes, 4, 4) and the
+ *                           edges [edge_offsets_host[g], ..) of edges (E, 2) int64 graph-local (source node, target node), transforms
+ *                           (E, 4, 4), informations (E, 6, 6), uncertain (E) bytes, all on the DEVICE; at most SE3_PGO_MAX_NODES nodes and
+ *                           SE3_PGO_MAX_EDGES edges per graph.  reference_nodes_host (num_graphs) HOST ints, -1 for none, or NULL for none
+ *                           at all.  max_iteration in [0, SE3_PGO_MAX_ITERATION], max_iteration_lm in [0, SE3_PGO_MAX_ITERATION_LM]; the
+ *                           doubles are checked on the device (a non-finite one refuses every graph: NONFINITE).  One workgroup of 256
+ *                           threads per graph, one launch.  out_poses (nodes, 4, 4); out_confidence (2, E) the line process after each pass
+ *                           (a pruned edge has 0 in the second row); out_kept (E) bytes; out_status (G) a sum of SE3_PGO_* bits; out_info
+ *                           (G, 6) ints: stop reason, iterations, trials of pass 1, then of pass 2; out_residuals (G, 2) the accepted
+ *                           residual of each pass.  workspace: se3_pose_graph_workspace_bytes of the same offsets (0 for
+ *                           offsets or sizes that the call would refuse).
+ *   se3_debug_pose_graph_host   the same text for one graph on HOST memory, run serially over the lanes.  trace: NULL, or (trace_rows, 4)
+ *                           float64: per trial lambda, rho, accepted (1 / 0), the trial's residual (NaN where none was formed);
+ *                           out_trace_count (2): the trials of each pass that were written, pass 2's after pass 1's.
+ *   se3_debug_pgo_atan2_host   the residual's arc tangent on n HOST pairs (y, x). */
+enum se3_pgo_status {              /* (NAMED: the shared names carry ICP's and FGR's values) */
+  SE3_PGO_NONFINITE = 1,
+  SE3_PGO_SINGULAR = 4,
+  SE3_PGO_EMPTY = 8,
+  SE3_PGO_STEP_REFUSED = 16,
+  SE3_PGO_BAD_INDEX = 32
+};
+enum se3_pgo_limit {
+  SE3_PGO_MAX_NODES = 64,
+  SE3_PGO_MAX_EDGES = 2016,        /* the complete graph on 64 nodes */
+  SE3_PGO_MAX_ITERATION = 1000,
+  SE3_PGO_MAX_ITERATION_LM = 100,
+  SE3_PGO_MAX_ANGLE = 4            /* rad: FGR's sine and cosine */
+};
+enum se3_pgo_stop {                /* why a pass ended: the first test that fired */
+  SE3_PGO_STOP_NONE = 0,
+  SE3_PGO_STOP_RIGHT_TERM = 1,
+  SE3_PGO_STOP_RELATIVE_INCREMENT = 2,
+  SE3_PGO_STOP_RELATIVE_RESIDUAL = 3,
+  SE3_PGO_STOP_RESIDUAL = 4,
+  SE3_PGO_STOP_MAX_ITERATION = 5,
+  SE3_PGO_STOP_MAX_ITERATION_LM = 6,
+  SE3_PGO_STOP_REFUSED = 7
+};
+size_t se3_pair_information_workspace_bytes(int64_t nsrc_total, int num_pairs);
+int se3_pair_information_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
+                               const int64_t* src_offsets_host, int num_pairs, const double* transforms, double max_correspondence_distance,
+                               double* out_information, double* out_count, int* out_status, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int se3_debug_pair_information_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const double* transform,
+                                    double max_correspondence_distance, double* out_information, double* out_count, int* out_status,
+                                    int64_t* out_correspondences);
+size_t se3_pose_graph_workspace_bytes(const int64_t* node_offsets_host, const int64_t* edge_offsets_host, int num_graphs);
+int se3_pose_graph_optimize_stack(const double* poses, const int64_t* node_offsets_host, const int64_t* edges, const double* transforms,
+                                  const double* informations, const uint8_t* uncertain, const int64_t* edge_offsets_host, int num_graphs,
+                                  const int* reference_nodes_host, int max_iteration, int max_iteration_lm, double min_relative_increment,
+                                  double min_relative_residual_increment, double min_right_term, double min_residual,
+                                  double upper_scale_factor, double lower_scale_factor, double max_correspondence_distance,
+                                  double edge_prune_threshold, double preference_loop_closure, double* out_poses, double* out_confidence,
+                                  uint8_t* out_kept, int* out_status, int* out_info, double* out_residuals, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int se3_debug_pose_graph_host(const double* poses, int64_t num_nodes, const int64_t* edges, const double* transforms,
+                              const double* informations, const uint8_t* uncertain, int64_t num_edges, int reference_node, int max_iteration,
+                              int max_iteration_lm, double min_relative_increment, double min_relative_residual_increment,
+                              double min_right_term, double min_residual, double upper_scale_factor, double lower_scale_factor,
+                              double max_correspondence_distance, double edge_prune_threshold, double preference_loop_closure,
+                              double* out_poses, double* out_confidence, uint8_t* out_kept, int* out_status, int* out_info,
+                              double* out_residuals, double* trace, int64_t trace_rows, int* out_trace_count);
+int se3_debug_pgo_atan2_host(const double* y, const double* x, int64_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif

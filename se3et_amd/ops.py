@@ -2680,6 +2680,89 @@ def fgr_stack(src_points, src_lengths, ref_points, ref_lengths, correspondences,
     return out
 
 
+# ---- multiway registration: information matrices and pose graphs (csrc/pose_graph.hip) ---------------------------------------------------------------
+PGO_STATUS = {name[len('SE3_PGO_'):].lower(): value for name, value in ENUMS['se3_pgo_status'].items()}
+PGO_STOP = {name[len('SE3_PGO_STOP_'):].lower(): value for name, value in ENUMS['se3_pgo_stop'].items()}
+PGO_MAX_NODES = ENUMS['se3_pgo_limit']['SE3_PGO_MAX_NODES']
+PGO_MAX_EDGES = ENUMS['se3_pgo_limit']['SE3_PGO_MAX_EDGES']
+PGO_MAX_ITERATION = ENUMS['se3_pgo_limit']['SE3_PGO_MAX_ITERATION']
+PGO_MAX_ITERATION_LM = ENUMS['se3_pgo_limit']['SE3_PGO_MAX_ITERATION_LM']
+_ws_pair_information, _ws_pose_graph = Workspace(1 << 20), Workspace(1 << 22)
+
+
+def pair_information_stack(grid, src_points, src_lengths, transforms, max_correspondence_distance):
+    """HIP: the information matrix of up to PAIR_MAX_PAIRS stacked pairs (se3et_amd/pose_graph.py has the contract).  grid:
+    pair_grid_build over the REFERENCE clouds with identity transforms and cell_hint = max_correspondence_distance; src_points (total, 3)
+    float32 / float64, pair p on the next src_lengths[p] rows; transforms (P, 4, 4) float64 on the DEVICE, ref ~ T src.  Returns a dict of
+    device tensors: information (P, 6, 6) float64, count (P,) float64, status (P,) int32 (0, or the nonfinite / empty bit of PGO_STATUS)."""
+    s, elem = _pair_points(src_points, 'src_points')
+    P = len(src_lengths)
+    if s.device != grid.device or P != grid.num_pairs:
+        raise RuntimeError('pair_information_stack: %d pairs on %s expected' % (grid.num_pairs, grid.device))
+    offsets = _pair_offsets(src_lengths, s.shape[0], 'pair_information_stack')
+    T = _req(transforms, torch.float64, 'transforms', 3)
+    if tuple(T.shape) != (P, 4, 4) or T.device != s.device:
+        raise RuntimeError('pair_information_stack: transforms must be (%d, 4, 4) on %s' % (P, s.device))
+    dev = s.device
+    out = {'information': torch.empty((P, 6, 6), dtype=torch.float64, device=dev), 'count': torch.empty((P,), dtype=torch.float64, device=dev),
+           'status': torch.empty((P,), dtype=torch.int32, device=dev)}
+    nbytes = lib().se3_pair_information_workspace_bytes(s.shape[0], P)
+    stream = _stream()
+    ws = _ws_pair_information.get(dev, stream.value, nbytes)
+    check(lib().se3_pair_information_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(s), elem, offsets, P, _dp(T),
+                                           float(max_correspondence_distance), _dp(out['information']), _dp(out['count']), _dp(out['status']),
+                                           ws.data_ptr(), nbytes, stream), 'se3_pair_information_stack')
+    return out
+
+
+def pose_graph_optimize_stack(poses, node_lengths, edges, transforms, informations, uncertain, edge_lengths, reference_nodes=None,
+                              max_iteration=100, max_iteration_lm=20, min_relative_increment=1e-6, min_relative_residual_increment=1e-6,
+                              min_right_term=1e-6, min_residual=1e-6, upper_scale_factor=2.0 / 3.0, lower_scale_factor=1.0 / 3.0,
+                              max_correspondence_distance=0.075, edge_prune_threshold=0.25, preference_loop_closure=1.0):
+    """HIP: the global optimisation of up to PAIR_MAX_PAIRS stacked pose graphs in ONE launch, one workgroup per graph, nothing read back
+    (se3et_amd/pose_graph.py has the contract).  poses (nodes, 4, 4) float64, graph g on the next node_lengths[g] rows; edges (E, 2) int64
+    graph-local (source node, target node), transforms (E, 4, 4) and informations (E, 6, 6) float64, uncertain (E,) uint8, graph g on the
+    next edge_lengths[g] rows; all on the device.  reference_nodes: None, or one node per graph (-1 for none).  Returns a dict of device
+    tensors: poses (nodes, 4, 4), confidence (2, E) (the line process after each pass), kept (E,) uint8, status (G,) int32 (a sum of the
+    PGO_STATUS bits), info (G, 6) int32 (stop reason -- a value of PGO_STOP --, iterations, trials of pass 1, then of pass 2), residuals
+    (G, 2) float64."""
+    what = 'pose_graph_optimize_stack'
+    X = _req(poses, torch.float64, 'poses', 3)
+    e = _req(edges, torch.int64, 'edges', 2)
+    T = _req(transforms, torch.float64, 'transforms', 3)
+    L = _req(informations, torch.float64, 'informations', 3)
+    u = _req(uncertain, torch.uint8, 'uncertain', 1)
+    G, E, dev = len(node_lengths), e.shape[0], X.device
+    if tuple(X.shape[1:]) != (4, 4) or tuple(e.shape) != (E, 2) or tuple(T.shape) != (E, 4, 4) or tuple(L.shape) != (E, 6, 6) or u.shape[0] != E \
+            or len(edge_lengths) != G or any(t.device != dev for t in (e, T, L, u)):
+        raise RuntimeError('%s: poses (nodes, 4, 4), edges (E, 2), transforms (E, 4, 4), informations (E, 6, 6) and uncertain (E,) of %d '
+                           'graphs on %s expected' % (what, G, dev))
+    if any(int(n) > PGO_MAX_NODES for n in node_lengths) or any(int(n) > PGO_MAX_EDGES for n in edge_lengths):
+        raise RuntimeError('%s: at most %d nodes and %d edges per graph' % (what, PGO_MAX_NODES, PGO_MAX_EDGES))
+    no, eo = _pair_offsets(node_lengths, X.shape[0], what), _pair_offsets(edge_lengths, E, what)
+    ref = None
+    if reference_nodes is not None:
+        if len(reference_nodes) != G:
+            raise RuntimeError('%s: one reference node per graph' % what)
+        ref = (ctypes.c_int * max(G, 1))(*[int(r) for r in reference_nodes])
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    out = {'poses': torch.empty((X.shape[0], 4, 4), **f64), 'confidence': torch.empty((2, E), **f64),
+           'kept': torch.empty((E,), dtype=torch.uint8, device=dev), 'status': torch.empty((G,), **i32), 'info': torch.empty((G, 6), **i32),
+           'residuals': torch.empty((G, 2), **f64)}
+    nbytes = lib().se3_pose_graph_workspace_bytes(no, eo, G)
+    if nbytes == 0:
+        raise RuntimeError('%s: the library refuses these graph sizes' % what)
+    stream = _stream()
+    ws = _ws_pose_graph.get(dev, stream.value, nbytes)
+    check(lib().se3_pose_graph_optimize_stack(_dp(X), no, _dp(e), _dp(T), _dp(L), _dp(u), eo, G, ref, int(max_iteration), int(max_iteration_lm),
+                                              float(min_relative_increment), float(min_relative_residual_increment), float(min_right_term),
+                                              float(min_residual), float(upper_scale_factor), float(lower_scale_factor),
+                                              float(max_correspondence_distance), float(edge_prune_threshold), float(preference_loop_closure),
+                                              _dp(out['poses']), _dp(out['confidence']), _dp(out['kept']), _dp(out['status']), _dp(out['info']),
+                                              _dp(out['residuals']), ws.data_ptr(), nbytes, stream), 'se3_pose_graph_optimize_stack')
+    return out
+
+
 # ---- keypoint selection: radius NMS in score order (csrc/keypoint_nms.hip) -----------------------------------------------------------------------
 _ws_keypoint_nms = Workspace(1 << 20)
 
