@@ -1095,6 +1095,57 @@ int se3_debug_icp_weighted_host(const void* src_points, int64_t n, const void* r
                                 double* out_rmse, int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences,
                                 int64_t* trace);
 
+/* ---- coloured ICP of stacked pairs (csrc/color_gradient.hip, csrc/icp.hip, csrc/icp_colored_core.h) ---------------------------------------------
+ * Open3D's registration_colored_icp (Park, Zhou, Koltun, ICCV 2017) for up to SE3_PAIR_MAX_PAIRS stacked pairs per call, all float64 and
+ * resident on the device: the colour gradients of the reference clouds once per call, then se3_icp_stack's loop with one more row per
+ * correspondence; the contracts are the header comments of csrc/color_gradient.hip and csrc/icp.hip.  Points, normals and colours are
+ * (rows, 3) on the device, float32 (elem 0) or float64 (elem 1), promoted on load; an intensity is ((c0 + c1) + c2) / 3.0.
+ *   se3_color_gradient_stack   cloud c owns rows [offsets_host[c], offsets_host[c + 1]) (HOST int64, num_clouds + 1 entries from 0).
+ *                           knn_idx (rows, k) int64 cloud-local and knn_d2 (rows, k) float64: se3_knn_stack's tables of the clouds searched
+ *                           in themselves, k in [1, SE3_KNN_MAX] (Open3D's 30).  radius finite and >= 0: of a row's list the entries with
+ *                           d^2 < radius^2 are its m members, the others of them than the row itself its neighbours.  out_gradients
+ *                           (rows, 3) float64: the least-squares gradient of the intensity in the row's tangent plane (the neighbours
+ *                           projected along the normal as given, the row (m - 1) n with right-hand side 0, a 3x3 Cholesky solve); zero for
+ *                           m < 4 or a pivot not above 1e-13 of its diagonal entry.  status (num_clouds + 1) DEVICE int: zeroed, then bit 1
+ *                           of word c for a non-finite point, normal or colour of cloud c, and of the last word for any; the rows of such
+ *                           a cloud are not to be read.  One thread per row, no atomics.
+ *   se3_debug_color_gradient_host   the same text for one cloud on HOST memory, no GPU, the list from se3_debug_knn_host's search: every
+ *                           pointer a host pointer; *status: bit 1 as above (nothing is computed).
+ *   se3_icp_colored_stack   se3_icp_stack's arguments with, in addition: src_colors (stacked source rows, 3) and ref_colors (nref_total, 3)
+ *                           of their elems; ref_gradients (nref_total, 3) float64 from se3_color_gradient_stack over the reference clouds;
+ *                           lambda_geometric in [0, 1] (Open3D's default 0.968); loss and loss_k as se3_icp_weighted_stack (NONE: no weight
+ *                           code).  ref_normals is required.  With a = sqrt(lambda), b = sqrt(1 - lambda), p the moved source row, q its
+ *                           reference row, nt, g, I_t that row's normal, gradient and intensity, I_s the source row's intensity:
+ *                           r_g = a (p - q) . nt, J_g = a [p x nt, nt];  p' = p - ((p - q) . nt) nt, r_c = b (I_s - g . (p' - q) - I_t),
+ *                           d = -(g - (nt . g) nt), J_c = b [p x d, d];  (sum w_g J_g J_g^T + w_c J_c J_c^T) x = -sum (w_g J_g r_g +
+ *                           w_c J_c r_c), solved, refused and applied as a point-to-plane step.  Evaluation, loop, results and status bits
+ *                           are se3_icp_stack's; TOO_FEW below 6 correspondences; a non-finite point, normal, colour, gradient or T0 sets
+ *                           NONFINITE for that pair alone.
+ *   se3_icp_colored_workspace_bytes   its workspace (that of se3_icp_stack).
+ *   se3_debug_icp_colored_host   the same text for one pair on HOST memory, with the trace of se3_debug_icp_host. */
+enum se3_icp_colored_option {      /* (a NAMED enum of its own: the mode tables of the entries above stay as they are) */
+  SE3_ICP_COLORED = 3              /* mode, beside SE3_ICP_POINT_TO_POINT, SE3_ICP_POINT_TO_PLANE and SE3_ICP_GENERALIZED: the coloured entries alone */
+};
+int se3_color_gradient_stack(const void* points, int elem, const void* normals, int normals_elem, const void* colors, int colors_elem,
+                             const int64_t* offsets_host, int num_clouds, const int64_t* knn_idx, const double* knn_d2, int k, double radius,
+                             double* out_gradients, int* status, void* stream);
+int se3_debug_color_gradient_host(const void* points, const void* normals, const void* colors, int64_t n, int elem, int normals_elem,
+                                  int colors_elem, int k, double radius, double* out_gradients, int* status);
+size_t se3_icp_colored_workspace_bytes(int64_t nsrc_total, int num_pairs);
+int se3_icp_colored_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
+                          const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem, const void* src_colors,
+                          int src_colors_elem, const void* ref_colors, int ref_colors_elem, const double* ref_gradients, const double* T0,
+                          double max_correspondence_distance, double lambda_geometric, int loss, double loss_k, double relative_fitness,
+                          double relative_rmse, int max_iteration, double* out_transforms, double* out_fitness, double* out_rmse,
+                          int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int se3_debug_icp_colored_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
+                               int normals_elem, const void* src_colors, int src_colors_elem, const void* ref_colors, int ref_colors_elem,
+                               const double* ref_gradients, const double* T0, double max_correspondence_distance, double lambda_geometric,
+                               int loss, double loss_k, double relative_fitness, double relative_rmse, int max_iteration, double* out_transform,
+                               double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged, int* out_status,
+                               int64_t* out_correspondences, int64_t* trace);
+
 /* ---- keypoint selection: radius non-maximum suppression in score order (csrc/keypoint_nms.hip) -------------------------------------------------
  * The loop of the reference's sample_keypoints_with_nms / random_sample_keypoints_with_nms (utils/pointcloud.py:191-248) in an exact parallel
  * form, for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, one workgroup per cloud; the contract is the header comment of

@@ -60,13 +60,28 @@
 //     count is 6; fitness and inlier_rmse stay Euclidean, as Open3D's result fields are.  A non-finite source normal refuses the pair.
 //     The loss acts on the Mahalanobis residual: w = w(sqrt(d^T M^-1 d)).  Open3D weights the three rows of M^(-1/2) d one by one, which
 //     needs a matrix square root; with l2 the two systems are the same in exact arithmetic.
-//   No coloured ICP, no captured graphs.
+//   Coloured ICP (se3_icp_colored_stack; csrc/icp_colored_core.h, the gradients from csrc/color_gradient.hip).  Open3D's
+//     registration_colored_icp: TransformationEstimationForColoredICP(lambda_geometric, kernel).  Evaluation, the loop and the convergence
+//     rule, the application of the accumulated T_k to the original source, the 256-lane serial sums with the fixed tree, the 6x6 Cholesky
+//     solve with its 1e-13 pivot rule, the update matrix and its shared sin / cos series, the 1 rad refusal, the status bits and the
+//     correspondences are the text above; only the per-correspondence term is new.  For a correspondence under T = [R | t]: p the moved
+//     source row, q its reference row, nt that row's normal as given, I_t its intensity, g its gradient (color_gradient.hip), I_s the
+//     source row's intensity (an intensity is ((c0 + c1) + c2) / 3.0), lambda = lambda_geometric in [0, 1] (Open3D's default 0.968),
+//     a = sqrt(lambda), b = sqrt(1 - lambda).
+//     Geometric row.  r_g = a (p - q) . nt, J_g = a [p x nt, nt].
+//     Photometric row.  p' = p - ((p - q) . nt) nt, I_proj = g . (p' - q) + I_t, r_c = b (I_s - I_proj), d = -(M g) with
+//       M = I - nt nt^T, J_c = b [p x d, d].
+//     System.  (sum w_g J_g J_g^T + w_c J_c J_c^T) x = -sum (w_g J_g r_g + w_c J_c r_c), w_g = w(r_g), w_c = w(r_c) from the loss table
+//       above; SE3_ICP_LOSS_NONE gives weights 1 and no weight code.  The 27 sums are formed in one pass, as generalized ICP's.
+//     Degenerate cases follow point-to-plane: fewer than 6 correspondences SE3_ICP_TOO_FEW, a failed pivot SE3_ICP_SINGULAR, an empty
+//       cloud SE3_ICP_EMPTY; a non-finite point, normal, colour, gradient or T0 sets SE3_ICP_NONFINITE for that pair alone.
+//   No captured graphs.
 #include <math.h>
 
 #include <vector>
 
 #include "common.h"
-#include "icp_core.h"          // (and through it pair_grid.h and kabsch.h)
+#include "icp_colored_core.h"  // (and through it icp_core.h, pair_grid.h and kabsch.h)
 
 namespace {
 
@@ -168,6 +183,44 @@ IcpStepKernel icp_step_kernel_of(const IcpCriteria& crit) {
   return weighted ? icp_step_kernel<true, false> : icp_step_kernel<false, false>;
 }
 
+// coloured ICP: the stacked colours and gradients of a call, beside IcpCall
+struct IcpColorCall {
+  const void* src_colors;         // stacked source rows
+  int src_colors_elem;
+  const void* ref_colors;         // stacked reference rows
+  int ref_colors_elem;
+  const double* gradients;        // stacked reference rows
+  double a, b;
+};
+
+__host__ __device__ IcpColors icp_colors_of(const IcpColorCall& cc, const IcpCall& c, const PairGridMeta* meta, int p) {
+  IcpColors v;
+  const int64_t s0 = c.rows.start[p], r0 = meta[p].s_start;
+  v.src_colors = cc.src_colors_elem ? (const void*)((const double*)cc.src_colors + 3 * s0) : (const void*)((const float*)cc.src_colors + 3 * s0);
+  v.src_colors_elem = cc.src_colors_elem;
+  v.ref_colors = cc.ref_colors_elem ? (const void*)((const double*)cc.ref_colors + 3 * r0) : (const void*)((const float*)cc.ref_colors + 3 * r0);
+  v.ref_colors_elem = cc.ref_colors_elem;
+  v.gradients = cc.gradients + 3 * r0;
+  v.a = cc.a, v.b = cc.b;
+  return v;
+}
+
+__global__ __launch_bounds__(kIcpLanes) void icp_colored_init_kernel(IcpCall c, IcpColorCall cc, const PairGridMeta* __restrict__ meta,
+                                                                     const double* __restrict__ T0) {
+  __shared__ double sh[kIcpLanes];
+  const IcpPair v = icp_pair_of(c, meta, blockIdx.x);
+  icp_colored_pair_init(v, icp_colors_of(cc, c, meta, blockIdx.x), T0 + 16 * blockIdx.x, threadIdx.x, threadIdx.x + 1, sh,
+                        [] { __syncthreads(); });
+}
+
+template <bool kWeighted>
+__global__ __launch_bounds__(kIcpLanes) void icp_colored_step_kernel(IcpCall c, IcpColorCall cc, const PairGridMeta* __restrict__ meta,
+                                                                     IcpCriteria crit, int k) {
+  __shared__ double sh[kIcpGeneralSums * kIcpLanes];
+  const IcpPair v = icp_pair_of(c, meta, blockIdx.x);
+  icp_colored_pair_step<kWeighted>(v, icp_colors_of(cc, c, meta, blockIdx.x), crit, k, threadIdx.x, threadIdx.x + 1, sh, [] { __syncthreads(); });
+}
+
 // one step of the host entries
 void icp_host_step(const IcpPair& v, const IcpCriteria& crit, int k, double* sh) {
   const bool weighted = crit.loss != SE3_ICP_LOSS_NONE;
@@ -212,7 +265,7 @@ int icp_stack_run(const char* what, const IcpCriteria& crit, const void* grid_wo
                   const void* src_points, int elem, const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem,
                   const void* src_normals, int src_normals_elem, const double* T0, double* out_transforms, double* out_fitness, double* out_rmse,
                   int* out_iterations, int* out_converged, int* out_status, int64_t* out_correspondences, void* workspace,
-                  size_t workspace_bytes, void* stream) {
+                  size_t workspace_bytes, void* stream, const IcpColorCall* colors = nullptr) {
   SE3_REQUIRE(grid_workspace && src_points && src_offsets_host && T0 && workspace, SE3_ERR_INVALID_ARG, "%s: null pointer", what);
   SE3_REQUIRE(out_transforms && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
               "%s: null result pointer", what);
@@ -240,6 +293,17 @@ int icp_stack_run(const char* what, const IcpCriteria& crit, const void* grid_wo
   c.T = out_transforms, c.fitness = out_fitness, c.rmse = out_rmse, c.iterations = out_iterations, c.converged = out_converged;
   c.status = out_status, c.corr = out_correspondences;
   hipStream_t st = (hipStream_t)stream;
+  if (colors) {                   // se3_icp_colored_stack: its own init and step kernels round the same search
+    const bool weighted = crit.loss != SE3_ICP_LOSS_NONE;
+    icp_colored_init_kernel<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, *colors, G.meta, T0);
+    for (int k = 0; k <= crit.max_iteration; k++) {
+      if (n_total > 0) icp_nearest_kernel<<<(unsigned)se3_cdiv(n_total, kIcpNnWaves), kIcpNnWaves * SE3_WAVE, 0, st>>>(G.view(), c, n_total);
+      if (weighted) icp_colored_step_kernel<true><<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, *colors, G.meta, crit, k);
+      else icp_colored_step_kernel<false><<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, *colors, G.meta, crit, k);
+    }
+    SE3_CHECK_LAUNCH(what);
+    return SE3_OK;
+  }
   const IcpStepKernel step = icp_step_kernel_of(crit);
   icp_init_kernel<<<(unsigned)num_pairs, kIcpLanes, 0, st>>>(c, G.meta, T0, crit.mode);
   for (int k = 0; k <= crit.max_iteration; k++) {
@@ -295,7 +359,7 @@ namespace {
 int icp_host_run(const char* what, const IcpCriteria& crit, const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem,
                  const void* ref_normals, int normals_elem, const void* src_normals, int src_normals_elem, const double* T0,
                  double max_correspondence_distance, double* out_transform, double* out_fitness, double* out_rmse, int* out_iterations,
-                 int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace) {
+                 int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace, const IcpColorCall* colors = nullptr) {
   SE3_REQUIRE(src_points && ref_points && T0, SE3_ERR_INVALID_ARG, "%s: null pointer", what);
   SE3_REQUIRE(out_transform && out_fitness && out_rmse && out_iterations && out_converged && out_status, SE3_ERR_INVALID_ARG,
               "%s: null result pointer", what);
@@ -320,7 +384,13 @@ int icp_host_run(const char* what, const IcpCriteria& crit, const void* src_poin
   c.status = out_status, c.corr = out_correspondences;
   const IcpPair v = icp_pair_of(c, G.meta, 0);
   const PairGridView g = G.view();
-  icp_pair_init(v, T0, crit.mode, 0, kIcpLanes, sh.data(), [] {});
+  IcpColors col{};
+  if (colors) {
+    col = icp_colors_of(*colors, c, G.meta, 0);
+    icp_colored_pair_init(v, col, T0, 0, kIcpLanes, sh.data(), [] {});
+  } else {
+    icp_pair_init(v, T0, crit.mode, 0, kIcpLanes, sh.data(), [] {});
+  }
   for (int k = 0; k <= crit.max_iteration && !done; k++) {
     for (int64_t i = 0; i < n; i++) {
       double qv[3];
@@ -328,7 +398,9 @@ int icp_host_run(const char* what, const IcpCriteria& crit, const void* src_poin
       pg_nearest(g, 0, qv, 0, 1, [](double*, int*) {}, &nn_d2[(size_t)i], &nn_idx[(size_t)i]);
       if (trace) trace[(int64_t)k * n + i] = nn_d2[(size_t)i] < crit.r2 ? nn_idx[(size_t)i] : -1;
     }
-    icp_host_step(v, crit, k, sh.data());
+    if (!colors) icp_host_step(v, crit, k, sh.data());
+    else if (crit.loss != SE3_ICP_LOSS_NONE) icp_colored_pair_step<true>(v, col, crit, k, 0, kIcpLanes, sh.data(), [] {});
+    else icp_colored_pair_step<false>(v, col, crit, k, 0, kIcpLanes, sh.data(), [] {});
   }
   return SE3_OK;
 }
@@ -364,6 +436,69 @@ extern "C" int se3_debug_icp_weighted_host(const void* src_points, int64_t n, co
   return icp_host_run("debug_icp_weighted_host", crit, src_points, n, ref_points, nref, elem, ref_normals, normals_elem, src_normals,
                       src_normals_elem, T0, max_correspondence_distance, out_transform, out_fitness, out_rmse, out_iterations, out_converged,
                       out_status, out_correspondences, trace);
+}
+
+// ---- coloured ICP: the entries (the contract is in the header comment) ---------------------------------------------------------------------------
+namespace {
+
+// the criteria and the colour call of the coloured entries (`what` words the errors)
+int icp_colored_args(const char* what, IcpCriteria* crit, IcpColorCall* cc, const void* ref_normals, const void* src_colors, int src_colors_elem,
+                     const void* ref_colors, int ref_colors_elem, const double* ref_gradients, double max_correspondence_distance,
+                     double lambda_geometric, int loss, double loss_k, double relative_fitness, double relative_rmse, int max_iteration) {
+  SE3_REQUIRE(icp_criteria(crit, max_correspondence_distance, SE3_ICP_POINT_TO_PLANE, relative_fitness, relative_rmse, max_iteration),
+              SE3_ERR_INVALID_ARG, "%s: distance %g, criteria %g %g %d (at most %d iterations)", what, max_correspondence_distance, relative_fitness,
+              relative_rmse, max_iteration, SE3_ICP_MAX_ITERATION);
+  SE3_REQUIRE(icp_loss_criteria(crit, loss, loss_k, 1.0), SE3_ERR_INVALID_ARG, "%s: loss %d, loss_k %g (positive and finite)", what, loss, loss_k);
+  SE3_REQUIRE(lambda_geometric >= 0.0 && lambda_geometric <= 1.0, SE3_ERR_INVALID_ARG, "%s: lambda_geometric %g is not in [0, 1]", what,
+              lambda_geometric);
+  SE3_REQUIRE(ref_normals && src_colors && ref_colors && ref_gradients, SE3_ERR_INVALID_ARG,
+              "%s: coloured ICP needs the reference normals, the colours of both clouds and the reference gradients", what);
+  SE3_REQUIRE((src_colors_elem == 0 || src_colors_elem == 1) && (ref_colors_elem == 0 || ref_colors_elem == 1), SE3_ERR_INVALID_ARG,
+              "%s: src_colors_elem %d, ref_colors_elem %d", what, src_colors_elem, ref_colors_elem);
+  crit->mode = SE3_ICP_COLORED;
+  cc->src_colors = src_colors, cc->src_colors_elem = src_colors_elem, cc->ref_colors = ref_colors, cc->ref_colors_elem = ref_colors_elem;
+  cc->gradients = ref_gradients, cc->a = pg_sqrt(lambda_geometric), cc->b = pg_sqrt(1.0 - lambda_geometric);
+  return SE3_OK;
+}
+
+}  // namespace
+
+extern "C" size_t se3_icp_colored_workspace_bytes(int64_t nsrc_total, int num_pairs) { return se3_icp_workspace_bytes(nsrc_total, num_pairs); }
+
+extern "C" int se3_icp_colored_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t nref_total, const void* src_points, int elem,
+                                     const int64_t* src_offsets_host, int num_pairs, const void* ref_normals, int normals_elem,
+                                     const void* src_colors, int src_colors_elem, const void* ref_colors, int ref_colors_elem,
+                                     const double* ref_gradients, const double* T0, double max_correspondence_distance, double lambda_geometric,
+                                     int loss, double loss_k, double relative_fitness, double relative_rmse, int max_iteration,
+                                     double* out_transforms, double* out_fitness, double* out_rmse, int* out_iterations, int* out_converged,
+                                     int* out_status, int64_t* out_correspondences, void* workspace, size_t workspace_bytes, void* stream) {
+  IcpCriteria crit;
+  IcpColorCall cc;
+  if (const int rc = icp_colored_args("icp_colored_stack", &crit, &cc, ref_normals, src_colors, src_colors_elem, ref_colors, ref_colors_elem,
+                                      ref_gradients, max_correspondence_distance, lambda_geometric, loss, loss_k, relative_fitness, relative_rmse,
+                                      max_iteration))
+    return rc;
+  return icp_stack_run("icp_colored_stack", crit, grid_workspace, grid_workspace_bytes, nref_total, src_points, elem, src_offsets_host, num_pairs,
+                       ref_normals, normals_elem, nullptr, 0, T0, out_transforms, out_fitness, out_rmse, out_iterations, out_converged, out_status,
+                       out_correspondences, workspace, workspace_bytes, stream, &cc);
+}
+
+// the coloured entry on host memory: se3_icp_colored_stack's text for one pair, with se3_debug_icp_host's trace
+extern "C" int se3_debug_icp_colored_host(const void* src_points, int64_t n, const void* ref_points, int64_t nref, int elem, const void* ref_normals,
+                                          int normals_elem, const void* src_colors, int src_colors_elem, const void* ref_colors,
+                                          int ref_colors_elem, const double* ref_gradients, const double* T0, double max_correspondence_distance,
+                                          double lambda_geometric, int loss, double loss_k, double relative_fitness, double relative_rmse,
+                                          int max_iteration, double* out_transform, double* out_fitness, double* out_rmse, int* out_iterations,
+                                          int* out_converged, int* out_status, int64_t* out_correspondences, int64_t* trace) {
+  IcpCriteria crit;
+  IcpColorCall cc;
+  if (const int rc = icp_colored_args("debug_icp_colored_host", &crit, &cc, ref_normals, src_colors, src_colors_elem, ref_colors, ref_colors_elem,
+                                      ref_gradients, max_correspondence_distance, lambda_geometric, loss, loss_k, relative_fitness, relative_rmse,
+                                      max_iteration))
+    return rc;
+  return icp_host_run("debug_icp_colored_host", crit, src_points, n, ref_points, nref, elem, ref_normals, normals_elem, nullptr, 0, T0,
+                      max_correspondence_distance, out_transform, out_fitness, out_rmse, out_iterations, out_converged, out_status,
+                      out_correspondences, trace, &cc);
 }
 
 extern "C" int se3_debug_icp_sincos_host(const double* x, int64_t n, double* out_sin, double* out_cos) {

@@ -1,5 +1,5 @@
 // Uniform float64 grid over the TRANSFORMED support cloud of each pair of a stacked call, and the search core that every tool on it shares:
-// csrc/pair_geometry.hip (which also owns the device build, se3_pair_grid_build), knn_normals.hip, icp.hip, keypoint_nms.hip, fpfh.hip, iss.hip and outliers.hip.
+// csrc/pair_geometry.hip (which also owns the device build, se3_pair_grid_build), knn_normals.hip, icp.hip, keypoint_nms.hip, fpfh.hip, iss.hip, outliers.hip and color_gradient.hip.
 //
 // The grid is only an accelerator: every answer is defined by the arithmetic contract in pair_geometry.hip (transform by the documented fma
 // chain, d^2 = (dx dx + dy dy) + dz dz unfused, strict tests, the lowest index among equal distances), and the walks below visit every

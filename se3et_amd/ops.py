@@ -2628,6 +2628,79 @@ def icp_loss_of(loss, loss_k, what):
     return (_ICP_LOSS_NONE if loss is None else ICP_LOSSES[loss]), k
 
 
+# ---- coloured ICP: colour gradients and the coloured entry (csrc/color_gradient.hip, csrc/icp.hip) ----------------------------------------------
+# the coloured mode has an enum and a constant of its own: ICP_MODES and ICP_WEIGHTED_MODES stay the tables of their entries
+ICP_COLORED = ENUMS['se3_icp_colored_option']['SE3_ICP_COLORED']
+COLOR_GRADIENT_STATUS = {1: 'a point, normal or colour is not finite'}
+
+
+def color_gradient_stack(points, normals, colors, lengths, knn_idx, knn_d2, radius):
+    """HIP: the colour gradient of every row of stacked clouds from the (rows, k) tables of knn_stack over the clouds searched in
+    themselves.  points / normals / colors (total, 3) float32 / float64 on the device, cloud c on the next lengths[c] rows (host ints);
+    radius finite and >= 0.  Returns (gradients (total, 3) float64, words (len(lengths) + 1,) int32 on the DEVICE: bit 1 of word c for a
+    non-finite point, normal or colour of cloud c, the last word for any)."""
+    p, elem = _pair_points(points, 'points')
+    nr, nelem = _pair_points(normals, 'normals')
+    col, celem = _pair_points(colors, 'colors')
+    if nr.shape != p.shape or col.shape != p.shape or nr.device != p.device or col.device != p.device:
+        raise RuntimeError('color_gradient_stack: normals and colors must have the shape and device of the points')
+    idx, d2 = _req(knn_idx, torch.int64, 'knn_idx', 2), _req(knn_d2, torch.float64, 'knn_d2', 2)
+    k = _knn_k(idx.shape[1], 'color_gradient_stack')
+    if idx.shape != (p.shape[0], k) or d2.shape != idx.shape or idx.device != p.device or d2.device != p.device:
+        raise RuntimeError('color_gradient_stack: knn_idx and knn_d2 must be (%d, k) tables of knn_stack on %s' % (p.shape[0], p.device))
+    C = len(lengths)
+    offsets = _pair_offsets(lengths, p.shape[0], 'color_gradient_stack')
+    out = torch.empty((p.shape[0], 3), dtype=torch.float64, device=p.device)
+    words = torch.empty((C + 1,), dtype=torch.int32, device=p.device)
+    check(lib().se3_color_gradient_stack(_dp(p), elem, _dp(nr), nelem, _dp(col), celem, offsets, C, _dp(idx), _dp(d2), k, float(radius),
+                                         _dp(out), words.data_ptr(), _stream()), 'se3_color_gradient_stack')
+    return out, words
+
+
+def icp_colored_stack(grid, src_points, src_lengths, init_transforms, max_correspondence_distance, ref_normals, src_colors, ref_colors,
+                      ref_gradients, lambda_geometric=0.968, loss=None, loss_k=None, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
+                      return_correspondences=False):
+    """HIP: coloured ICP of up to PAIR_MAX_PAIRS stacked pairs: icp_stack's grid, source, transforms and results, with ref_normals
+    (grid.ns_total, 3), src_colors (total source rows, 3), ref_colors (grid.ns_total, 3), all float32 / float64, ref_gradients
+    (grid.ns_total, 3) float64 from color_gradient_stack over the reference clouds, lambda_geometric in [0, 1], and loss / loss_k as
+    icp_weighted_stack (None: the instantiation without weight code)."""
+    s, elem = _pair_points(src_points, 'src_points')
+    P = len(src_lengths)
+    if s.device != grid.device or P != grid.num_pairs:
+        raise RuntimeError('icp_colored_stack: %d pairs on %s expected' % (grid.num_pairs, grid.device))
+    lam = float(lambda_geometric)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError('icp_colored_stack: lambda_geometric %r is not in [0, 1]' % (lambda_geometric,))
+    loss_id, k = icp_loss_of(loss, loss_k, 'icp_colored_stack')
+    offsets = _pair_offsets(src_lengths, s.shape[0], 'icp_colored_stack')
+    T0 = _req(init_transforms, torch.float64, 'init_transforms', 3)
+    if tuple(T0.shape) != (P, 4, 4) or T0.device != s.device:
+        raise RuntimeError('icp_colored_stack: init_transforms must be (%d, 4, 4) on %s' % (P, s.device))
+    nr, nelem = _pair_points(ref_normals, 'ref_normals')
+    sc, scelem = _pair_points(src_colors, 'src_colors')
+    rc, rcelem = _pair_points(ref_colors, 'ref_colors')
+    g = _req(ref_gradients, torch.float64, 'ref_gradients', 2)
+    for t, rows, name in ((nr, grid.ns_total, 'ref_normals'), (sc, s.shape[0], 'src_colors'), (rc, grid.ns_total, 'ref_colors'),
+                          (g, grid.ns_total, 'ref_gradients')):
+        if tuple(t.shape) != (rows, 3) or t.device != s.device:
+            raise RuntimeError('icp_colored_stack: %s must be (%d, 3) on %s' % (name, rows, s.device))
+    dev = s.device
+    out = icp_outputs(P, dev)
+    corr = torch.empty((s.shape[0],), dtype=torch.int64, device=dev) if return_correspondences else None
+    nbytes = lib().se3_icp_colored_workspace_bytes(s.shape[0], P)
+    stream = _stream()
+    ws = _ws_icp.get(dev, stream.value, nbytes)
+    check(lib().se3_icp_colored_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(s), elem, offsets, P, _dp(nr), nelem, _dp(sc), scelem,
+                                      _dp(rc), rcelem, _dp(g), _dp(T0), float(max_correspondence_distance), lam, loss_id, k,
+                                      float(relative_fitness), float(relative_rmse), int(max_iteration), _dp(out['transforms']),
+                                      _dp(out['fitness']), _dp(out['inlier_rmse']), _dp(out['iterations']), _dp(out['converged']),
+                                      _dp(out['status']), None if corr is None else _dp(corr), ws.data_ptr(), nbytes, stream),
+          'se3_icp_colored_stack')
+    if corr is not None:
+        out['correspondences'] = corr
+    return out
+
+
 # ---- Fast Global Registration of stacked pairs (csrc/fgr.hip) ------------------------------------------------------------------------------------
 FGR_STATUS = {name[len('SE3_FGR_'):].lower(): value for name, value in ENUMS['se3_fgr_status'].items()}
 FGR_MAX_ITERATION = ENUMS['se3_fgr_limit']['SE3_FGR_MAX_ITERATION']
