@@ -1364,6 +1364,47 @@ int se3_debug_pose_graph_host(const double* poses, int64_t num_nodes, const int6
                               double* out_residuals, double* trace, int64_t trace_rows, int* out_trace_count);
 int se3_debug_pgo_atan2_host(const double* y, const double* x, int64_t n, double* out);
 
+/* ---- Plane segmentation and DBSCAN clustering of stacked clouds (csrc/plane.hip, csrc/plane_core.h, csrc/dbscan.hip, csrc/dbscan_core.h) ------
+ * Open3D's segment_plane and cluster_dbscan for up to SE3_PAIR_MAX_PAIRS stacked clouds per call, float64, nothing read back; the contracts
+ * are the header comments of csrc/plane.hip and csrc/dbscan.hip.  points (rows, 3) float32 (elem 0) / float64 (elem 1) on the device, cloud
+ * c on rows [offsets_host[c], offsets_host[c + 1]) (HOST int64, num_clouds + 1 entries from 0).
+ *   se3_plane_segment_stack   distance_threshold positive and finite, ransac_n in [3, SE3_PLANE_MAX_SAMPLE], num_iterations in
+ *                           [1, SE3_PLANE_MAX_ITERATIONS].  out_planes (P, 4) float64 (a, b, c, d), out_mask (rows) bytes: 1 for an inlier of
+ *                           the returned plane, out_counts (P) ints, out_fitness and out_rmse (P) float64, out_status (P): SE3_PLANE_OK,
+ *                           SE3_PLANE_TOO_FEW (fewer than ransac_n rows) or SE3_PLANE_NONE (no hypothesis with 3 inliers), out_best (P) the
+ *                           winning hypothesis, -1 for none.  Optional (both or neither NULL): out_hyp_counts (P, num_iterations) ints and
+ *                           out_hyp_errs (P, num_iterations) float64, every hypothesis' inlier count and error sum.  Every output is on
+ *                           the DEVICE.  workspace: se3_plane_segment_workspace_bytes of the same offsets (0 for what the call refuses).
+ *   se3_dbscan_stack        grid: se3_pair_grid_build over the clouds themselves with identity transforms and cell_hint = eps (ns_total =
+ *                           the rows of the clouds).  eps positive and finite, min_points >= 1.  out_labels (rows) ints: -1 noise, clusters
+ *                           0 .. k - 1 per cloud; out_num_clusters (P) int64.  workspace: se3_dbscan_workspace_bytes(rows).
+ *   se3_debug_plane_host / se3_debug_dbscan_host   the same text for one cloud on HOST memory, no GPU, run serially over the lanes: every
+ *                           pointer a host pointer. */
+enum se3_plane_status {            /* (NAMED: the flat table of #defines and anonymous enumerators stays as it is) */
+  SE3_PLANE_OK = 0,
+  SE3_PLANE_TOO_FEW = 2,
+  SE3_PLANE_NONE = 64
+};
+enum se3_plane_limit {
+  SE3_PLANE_MAX_SAMPLE = 16,       /* ransac_n at most */
+  SE3_PLANE_TILE = 128,            /* hypotheses per scoring workgroup */
+  SE3_PLANE_SEGMENT = 1024,        /* rows per segment of the error sum */
+  SE3_PLANE_MAX_ITERATIONS = 1048576
+};
+size_t se3_plane_segment_workspace_bytes(const int64_t* offsets_host, int num_clouds, int num_iterations);
+int se3_plane_segment_stack(const void* points, int elem, const int64_t* offsets_host, int num_clouds, double distance_threshold, int ransac_n,
+                            int num_iterations, uint64_t seed, double* out_planes, uint8_t* out_mask, int* out_counts, double* out_fitness,
+                            double* out_rmse, int* out_status, int* out_best, int* out_hyp_counts, double* out_hyp_errs, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int se3_debug_plane_host(const void* points, int64_t n, int elem, double distance_threshold, int ransac_n, int num_iterations, uint64_t seed,
+                         double* out_plane, uint8_t* out_mask, int* out_count, double* out_fitness, double* out_rmse, int* out_status,
+                         int* out_best, int* out_hyp_counts, double* out_hyp_errs);
+size_t se3_dbscan_workspace_bytes(int64_t n_total);
+int se3_dbscan_stack(const void* grid_workspace, size_t grid_workspace_bytes, int64_t ns_total, const void* points, int elem,
+                     const int64_t* offsets_host, int num_clouds, double eps, int64_t min_points, int* out_labels, int64_t* out_num_clusters,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_dbscan_host(const void* points, int64_t n, int elem, double eps, int64_t min_points, int* out_labels, int64_t* out_num_clusters);
+
 #ifdef __cplusplus
 }
 #endif

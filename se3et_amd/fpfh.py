@@ -5,8 +5,9 @@ fed with, as batched HIP kernels (csrc/fpfh.hip, csrc/fpfh_core.h) on the search
   compute_fpfh_clouds(points_list, normals_list, radius=None, max_nn=None, dtype=torch.float64)   list of (n_c, 33) tensors on the device
   spfh_clouds(points_list, normals_list, radius=None, max_nn=None)                                the first pass alone, float64
   compute_fpfh_feature(points, normals, radius=None, max_nn=None)                                 one cloud, numpy in, (n, 33) numpy out
-  global_registration_pairs(src_list, ref_list, voxel_size, ...)                                  (outlier removal,) downsample, normals, FPFH,
-                                                                                                  (ISS keypoints,) RANSAC or FGR, ICP
+  global_registration_pairs(src_list, ref_list, voxel_size, ...)                                  (outlier removal,) downsample, (planes out,
+                                                                                                  clusters kept,) normals, FPFH, (ISS keypoints,)
+                                                                                                  RANSAC or FGR, ICP
 
 The batched calls take GPU tensors only (there is no CPU path): points and normals (n, 3) float32 or float64, promoted on load; any number
 of clouds per call, chunked at the library's SE3_PAIR_MAX_PAIRS clouds and, within a chunk, at PAIR_BUDGET neighbour-list entries (16
@@ -201,7 +202,7 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
                               ransac_n=3, num_iterations=50000, mutual_filter=True, edge_length_similarity=0.9, check_distance=True,
                               icp_distance=None, icp_estimation='point_to_point', icp_max_iteration=30, seed=0, device=None, icp_loss=None,
                               icp_loss_k=None, coarse='ransac', fgr_distance=None, fgr_options=None, outlier_removal=None, keypoints=None,
-                              iss_options=None):
+                              iss_options=None, remove_planes=0, plane_options=None, keep_clusters=None, dbscan_options=None):
     """The classical global registration of P pairs, a composition of the batched tools (no kernel of its own): voxel_downsample_clouds at
     voxel_size, estimate_normals_clouds (normal_knn), compute_fpfh_clouds (float32), ransac_from_feats_pairs, and with icp_distance
     icp_pairs from the RANSAC result on the downsampled clouds.  src_list / ref_list: (n, 3) float32 or float64 GPU tensors.
@@ -222,7 +223,16 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     intermediate lists), ransac (the dict of ransac_from_feats_pairs, or None), fgr (the dict of fgr_from_feats_pairs, or None) and icp
     (that of icp_pairs or generalized_icp_pairs, or None).  A call with outlier_removal or keypoints adds four keys: src_keypoints /
     ref_keypoints (the lists of keypoint indices into src_points / ref_points, None without a detector) and src_kept / ref_kept (the
-    lists of the raw rows the outlier filter kept, None without one); a call with neither returns exactly the keys above."""
+    lists of the raw rows the outlier filter kept, None without one); a call with neither returns exactly the keys above.
+    remove_planes: how many dominant planes segmentation.segment_planes_clouds peels off every downsampled cloud (0: none; plane_options:
+    a dict of its further arguments, distance_threshold 0.5 voxel_size unless given there).  keep_clusters: None, or the least size of a
+    DBSCAN cluster (segmentation.cluster_dbscan_clouds; dbscan_options: eps, 2.5 voxel_size unless given, and min_points, 5 unless given)
+    whose rows are kept; noise and smaller clusters are dropped.  Both apply to the downsampled clouds before the normals, the planes
+    first, and only the kept rows go on to every later stage.  A call with either adds eight keys: src_segment_rows / ref_segment_rows
+    (the lists of the kept rows' indices into the downsampled clouds, int64, ascending), src_plane_labels / ref_plane_labels and
+    src_planes / ref_planes (the labels per downsampled row and the (P, remove_planes, 4) planes of segment_planes_clouds; None without
+    remove_planes), src_cluster_labels / ref_cluster_labels (the DBSCAN labels of the rows the planes left; None without keep_clusters).
+    With both at their defaults the result has exactly the keys above and the same bits."""
     from .icp import generalized_icp_pairs, icp_pairs
     from .ransac import ransac_from_feats_pairs
     from .scan_prep import estimate_normals_clouds, voxel_downsample_clouds
@@ -237,6 +247,10 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     if outlier_removal is not None and (len(outlier_removal) != 3 or outlier_removal[0] not in ('statistical', 'radius')):
         raise ValueError("%s: outlier_removal %r is not None, ('statistical', nb_neighbors, std_ratio) or ('radius', nb_points, radius)"
                          % (what, outlier_removal))
+    if int(remove_planes) != remove_planes or int(remove_planes) < 0:
+        raise ValueError('%s: remove_planes %r is not an integer >= 0' % (what, remove_planes))
+    if keep_clusters is not None and (int(keep_clusters) != keep_clusters or int(keep_clusters) < 1):
+        raise ValueError('%s: keep_clusters %r is not None or an integer >= 1' % (what, keep_clusters))
     v = float(voxel_size)
     if not (np.isfinite(v) and v > 0):
         raise ValueError('%s: voxel size %r is not a positive finite number' % (what, voxel_size))
@@ -252,6 +266,25 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
         kept = remove(raw, outlier_removal[1], outlier_removal[2], device=dev)
         raw = [c[k] for c, k in zip(raw, kept)]
     clouds = voxel_downsample_clouds(raw, v, device=dev)
+    segment = None
+    if remove_planes or keep_clusters is not None:
+        from .segmentation import cluster_dbscan_clouds, segment_planes_clouds
+        rows = [torch.arange(c.shape[0], dtype=torch.int64, device=c.device) for c in clouds]
+        plane_labels = plane_models = cluster_labels = None
+        if remove_planes:
+            options = dict(plane_options or {})
+            options.setdefault('distance_threshold', 0.5 * v)
+            options.setdefault('seed', seed)
+            plane_labels, plane_models, _ = segment_planes_clouds(clouds, max_planes=int(remove_planes), device=dev, **options)
+            rows = [r[lab < 0] for r, lab in zip(rows, plane_labels)]
+        if keep_clusters is not None:
+            options = dict(dbscan_options or {})
+            cluster_labels, _ = cluster_dbscan_clouds([c[r] for c, r in zip(clouds, rows)], options.pop('eps', 2.5 * v),
+                                                      options.pop('min_points', 5), device=dev, **options)
+            big = [torch.bincount(lab[lab >= 0].to(torch.int64), minlength=1) >= int(keep_clusters) for lab in cluster_labels]
+            rows = [r[(lab >= 0) & b[lab.clamp(min=0).to(torch.int64)]] for r, lab, b in zip(rows, cluster_labels, big)]
+        clouds = [c[r] for c, r in zip(clouds, rows)]
+        segment = (rows, plane_labels, plane_models, cluster_labels)
     normals = estimate_normals_clouds(clouds, normal_knn, device=dev)
     feats = compute_fpfh_clouds(clouds, normals, fpfh_radius, fpfh_max_nn, torch.float32, device=dev)
     src, ref = clouds[:P], clouds[P:]
@@ -287,4 +320,7 @@ def global_registration_pairs(src_list, ref_list, voxel_size, normal_knn=33, fpf
     if keypoints is not None or outlier_removal is not None:
         out.update(src_keypoints=keys[:P] if keys is not None else None, ref_keypoints=keys[P:] if keys is not None else None,
                    src_kept=kept[:P] if kept is not None else None, ref_kept=kept[P:] if kept is not None else None)
+    if segment is not None:
+        for key, value in zip(('segment_rows', 'plane_labels', 'planes', 'cluster_labels'), segment):
+            out['src_' + key], out['ref_' + key] = (None, None) if value is None else (value[:P], value[P:])
     return out

@@ -2981,3 +2981,52 @@ def distance_stats_stack(a, lengths, std_ratio=1.0):
     check(lib().se3_distance_stats_stack(_dp(a), offsets, len(lengths), float(std_ratio), _dp(stats), _dp(mask), _stream()),
           'se3_distance_stats_stack')
     return stats, mask
+
+
+# ---- plane segmentation and DBSCAN clustering of stacked clouds (csrc/plane.hip, csrc/dbscan.hip) ------------------------------------------------
+PLANE_STATUS = {name[len('SE3_PLANE_'):].lower(): value for name, value in ENUMS['se3_plane_status'].items()}
+PLANE_MAX_SAMPLE = ENUMS['se3_plane_limit']['SE3_PLANE_MAX_SAMPLE']
+PLANE_TILE = ENUMS['se3_plane_limit']['SE3_PLANE_TILE']
+PLANE_SEGMENT = ENUMS['se3_plane_limit']['SE3_PLANE_SEGMENT']
+PLANE_MAX_ITERATIONS = ENUMS['se3_plane_limit']['SE3_PLANE_MAX_ITERATIONS']
+_ws_plane, _ws_dbscan = Workspace(1 << 22), Workspace(1 << 20)
+
+
+def plane_segment_stack(points, lengths, distance_threshold, ransac_n=3, num_iterations=100, seed=0, per_hypothesis=False):
+    """HIP (csrc/plane.hip): the dominant plane of each of the stacked clouds, three launches and nothing read back.  Returns a dict of
+    device tensors: planes (P, 4) float64, mask (rows,) uint8, counts (P,) int32, fitness and inlier_rmse (P,) float64, status (P,) int32
+    (PLANE_STATUS), best_hypothesis (P,) int32 (-1: none); with per_hypothesis also hyp_counts (P, H) int32 and hyp_errs (P, H) float64."""
+    p, elem = _pair_points(points, 'points')
+    P, H = len(lengths), int(num_iterations)
+    offsets = _pair_offsets(lengths, p.shape[0], 'plane_segment_stack')
+    dev = p.device
+    out = dict(planes=torch.empty((P, 4), dtype=torch.float64, device=dev), mask=torch.empty((p.shape[0],), dtype=torch.uint8, device=dev),
+               counts=torch.empty((P,), dtype=torch.int32, device=dev), fitness=torch.empty((P,), dtype=torch.float64, device=dev),
+               inlier_rmse=torch.empty((P,), dtype=torch.float64, device=dev), status=torch.empty((P,), dtype=torch.int32, device=dev),
+               best_hypothesis=torch.empty((P,), dtype=torch.int32, device=dev))
+    if per_hypothesis:
+        out['hyp_counts'] = torch.empty((P, max(H, 0)), dtype=torch.int32, device=dev)
+        out['hyp_errs'] = torch.empty((P, max(H, 0)), dtype=torch.float64, device=dev)
+    nbytes = lib().se3_plane_segment_workspace_bytes(offsets, P, H)
+    stream = _stream()
+    ws = _ws_plane.get(dev, stream.value, max(nbytes, 256))
+    check(lib().se3_plane_segment_stack(_dp(p), elem, offsets, P, float(distance_threshold), int(ransac_n), H, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        _dp(out['planes']), _dp(out['mask']), _dp(out['counts']), _dp(out['fitness']), _dp(out['inlier_rmse']),
+                                        _dp(out['status']), _dp(out['best_hypothesis']), _dp(out['hyp_counts']) if per_hypothesis else None,
+                                        _dp(out['hyp_errs']) if per_hypothesis else None, ws.data_ptr(), nbytes, stream), 'se3_plane_segment_stack')
+    return out
+
+
+def dbscan_stack(grid, points, lengths, eps, min_points):
+    """HIP (csrc/dbscan.hip): DBSCAN labels of the stacked clouds.  grid: pair_grid_build over the clouds themselves with identity
+    transforms and cell_hint = eps.  Returns (labels (rows,) int32: -1 noise, clusters 0 .. k - 1 per cloud; num_clusters (P,) int64), on
+    the device."""
+    q, elem, offsets = _pair_query(grid, points, lengths, 'dbscan_stack')
+    labels = torch.empty((q.shape[0],), dtype=torch.int32, device=q.device)
+    num = torch.empty((len(lengths),), dtype=torch.int64, device=q.device)
+    nbytes = lib().se3_dbscan_workspace_bytes(q.shape[0])
+    stream = _stream()
+    ws = _ws_dbscan.get(q.device, stream.value, nbytes)
+    check(lib().se3_dbscan_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, float(eps), int(min_points),
+                                 _dp(labels), _dp(num), ws.data_ptr(), nbytes, stream), 'se3_dbscan_stack')
+    return labels, num
