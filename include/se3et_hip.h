@@ -1405,6 +1405,55 @@ int se3_dbscan_stack(const void* grid_workspace, size_t grid_workspace_bytes, in
                      void* workspace, size_t workspace_bytes, void* stream);
 int se3_debug_dbscan_host(const void* points, int64_t n, int elem, double eps, int64_t min_points, int* out_labels, int64_t* out_num_clusters);
 
+/* ---- TSDF fusion of depth frames and depth images as clouds (csrc/tsdf.hip, csrc/tsdf_core.h) ---------------------------------------------------
+ * Open3D's UniformTSDFVolume (integrate, extract_point_cloud) for up to SE3_PAIR_MAX_PAIRS volumes per call, and the reference's
+ * convert_depth_mat_to_points / Open3D's create_from_depth_image for any number of images; the contract is the header comment of
+ * csrc/tsdf.hip.  A volume is resolution^3 voxels, planar, voxel [x, y, z] at (x R + y) R + z: tsdf and weight (V, R, R, R) float32, color
+ * (V, 3, R, R, R) float32 or NULL, origins (V, 3) float64, all on the DEVICE.
+ *   se3_tsdf_integrate_stack  depths (F, H, W) uint16 (depth_elem 0) / float32 (1); colors NULL (color_elem 0), (F, H, W, 3) uint8 (1) /
+ *                           float32 (2), required exactly when color is given; frames (F, SE3_TSDF_FRAME_WORDS) float32: the 3 x 4
+ *                           world-to-camera extrinsic by rows, then fx, fy, cx, cy; volume v takes the frames [frame_offsets_host[v],
+ *                           frame_offsets_host[v + 1]) in ascending order (HOST int64, V + 1 entries from 0).  One launch: every voxel is
+ *                           read once and written once, and only where a frame touched it.
+ *   se3_tsdf_extract_stack  two passes over the same state.  out_points NULL: the count pass and the scan; row_offsets (V R R + 1) int64
+ *                           becomes the exclusive offsets of the rows (v, x, y) and the total.  Otherwise the write pass: out_points,
+ *                           out_normals and (with color) out_colors (capacity, 3) float64, volume v's rows at [row_offsets[v R R],
+ *                           row_offsets[(v + 1) R R]); nothing is written at or past `capacity`.
+ *   se3_depth_points_stack  the same two passes over the rows of F images: row_offsets (F H + 1) int64; intrinsics (F, 4) float64 (fx, fy,
+ *                           cx, cy) on the device; convention SE3_DEPTH_REFERENCE or SE3_DEPTH_OPEN3D.
+ *   se3_debug_tsdf_integrate_host / se3_debug_tsdf_extract_host / se3_debug_depth_points_host   the same text for one volume / one image on
+ *                           HOST memory, no GPU, serially: every pointer a host pointer.  out_points NULL: *out_count alone. */
+enum se3_tsdf_limit {              /* (NAMED) */
+  SE3_TSDF_MIN_RESOLUTION = 4,
+  SE3_TSDF_MAX_RESOLUTION = 1024,
+  SE3_TSDF_MAX_IMAGE = 8192,       /* height and width of an image at most */
+  SE3_TSDF_MAX_TRUNC_VOXELS = 64,  /* sdf_trunc in (0, this many voxel lengths] */
+  SE3_TSDF_FRAME_TILE = 64,        /* frames of the table staged through LDS at a time */
+  SE3_TSDF_FRAME_WORDS = 16        /* float32 words of a frame's row of the table */
+};
+enum se3_depth_convention {
+  SE3_DEPTH_REFERENCE = 0,
+  SE3_DEPTH_OPEN3D = 1
+};
+int se3_tsdf_integrate_stack(float* tsdf, float* weight, float* color, int num_volumes, int resolution, double voxel_length, double sdf_trunc,
+                             const double* origins, const void* depths, int depth_elem, const void* colors, int color_elem, int height,
+                             int width, const float* frames, const int64_t* frame_offsets_host, double depth_scale, double depth_trunc,
+                             void* stream);
+int se3_tsdf_extract_stack(const float* tsdf, const float* weight, const float* color, int num_volumes, int resolution, double voxel_length,
+                           const double* origins, int64_t* row_offsets, int64_t capacity, double* out_points, double* out_normals,
+                           double* out_colors, void* stream);
+int se3_depth_points_stack(const void* depths, int depth_elem, int64_t num_images, int height, int width, const double* intrinsics,
+                           double scaling_factor, double distance_limit, int convention, int64_t* row_offsets, int64_t capacity,
+                           double* out_points, void* stream);
+int se3_debug_tsdf_integrate_host(float* tsdf, float* weight, float* color, int resolution, double voxel_length, double sdf_trunc,
+                                  const double* origin, const void* depths, int depth_elem, const void* colors, int color_elem,
+                                  int64_t num_frames, int height, int width, const float* frames, double depth_scale, double depth_trunc);
+int se3_debug_tsdf_extract_host(const float* tsdf, const float* weight, const float* color, int resolution, double voxel_length,
+                                const double* origin, int64_t capacity, double* out_points, double* out_normals, double* out_colors,
+                                int64_t* out_count);
+int se3_debug_depth_points_host(const void* depth, int depth_elem, int height, int width, const double* intrinsics, double scaling_factor,
+                                double distance_limit, int convention, int64_t capacity, double* out_points, int64_t* out_count);
+
 #ifdef __cplusplus
 }
 #endif

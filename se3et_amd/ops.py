@@ -3030,3 +3030,109 @@ def dbscan_stack(grid, points, lengths, eps, min_points):
     check(lib().se3_dbscan_stack(grid.ws.data_ptr(), grid.nbytes, grid.ns_total, _dp(q), elem, offsets, grid.num_pairs, float(eps), int(min_points),
                                  _dp(labels), _dp(num), ws.data_ptr(), nbytes, stream), 'se3_dbscan_stack')
     return labels, num
+
+
+# ---- TSDF fusion of depth frames and depth images as clouds (csrc/tsdf.hip) ------------------------------------------------------------------------
+TSDF_LIMITS = {name[len('SE3_TSDF_'):].lower(): value for name, value in ENUMS['se3_tsdf_limit'].items()}
+DEPTH_CONVENTIONS = {name[len('SE3_DEPTH_'):].lower(): value for name, value in ENUMS['se3_depth_convention'].items()}
+_DEPTH_ELEM = {torch.uint16: 0, torch.float32: 1}
+_COLOR_ELEM = {torch.uint8: 1, torch.float32: 2}
+
+
+def _tsdf_images(depths, colors, what):
+    """(depths, depth_elem, colors or None, color_elem) of (F, H, W) uint16 / float32 depths and (F, H, W, 3) uint8 / float32 colours."""
+    if not torch.is_tensor(depths) or depths.dtype not in _DEPTH_ELEM:
+        raise RuntimeError('%s: depths must be a uint16 or float32 tensor' % what)
+    d = _req(depths, depths.dtype, 'depths', 3)
+    if colors is None:
+        return d, _DEPTH_ELEM[d.dtype], None, 0
+    if not torch.is_tensor(colors) or colors.dtype not in _COLOR_ELEM:
+        raise RuntimeError('%s: colors must be a uint8 or float32 tensor' % what)
+    c = _req(colors, colors.dtype, 'colors', 4)
+    if tuple(c.shape) != tuple(d.shape) + (3,) or c.device != d.device:
+        raise RuntimeError('%s: colors must be %s on %s, got %s on %s' % (what, tuple(d.shape) + (3,), d.device, tuple(c.shape), c.device))
+    return d, _DEPTH_ELEM[d.dtype], c, _COLOR_ELEM[c.dtype]
+
+
+def _tsdf_state(tsdf, weight, color, what):
+    t = _req(tsdf, torch.float32, 'tsdf', 4)
+    V, R = t.shape[0], t.shape[1]
+    w = _req(weight, torch.float32, 'weight', 4)
+    if tuple(t.shape) != (V, R, R, R) or w.shape != t.shape or w.device != t.device or V > PAIR_MAX_PAIRS:
+        raise RuntimeError('%s: tsdf and weight must both be (V, R, R, R) on one device, V at most %d' % (what, PAIR_MAX_PAIRS))
+    if color is not None:
+        color = _req(color, torch.float32, 'color', 5)
+        if tuple(color.shape) != (V, 3, R, R, R) or color.device != t.device:
+            raise RuntimeError('%s: color must be (V, 3, R, R, R) on %s' % (what, t.device))
+    return t, w, color, V, R
+
+
+def tsdf_integrate_stack(tsdf, weight, color, voxel_length, sdf_trunc, origins, depths, frames, frame_counts, colors=None, depth_scale=1000.0,
+                         depth_trunc=3.0):
+    """HIP (csrc/tsdf.hip): the frames' depth images integrated into the volumes, in place, one launch.  tsdf, weight (V, R, R, R) float32,
+    color (V, 3, R, R, R) float32 or None, origins (V, 3) float64, depths (F, H, W) uint16 or float32, colors (F, H, W, 3) uint8 or float32
+    (exactly when color is given), frames (F, TSDF_LIMITS['frame_words']) float32: the 3 x 4 extrinsic by rows, then fx, fy, cx, cy;
+    frame_counts: the number of frames of each volume, in order."""
+    what = 'tsdf_integrate_stack'
+    t, w, color, V, R = _tsdf_state(tsdf, weight, color, what)
+    d, depth_elem, c, color_elem = _tsdf_images(depths, colors, what)
+    o = _req(origins, torch.float64, 'origins', 2)
+    fr = _req(frames, torch.float32, 'frames', 2)
+    F = d.shape[0]
+    if tuple(o.shape) != (V, 3) or tuple(fr.shape) != (F, TSDF_LIMITS['frame_words']) or any(x.device != t.device for x in (o, fr, d)):
+        raise RuntimeError('%s: origins (V, 3), frames (F, %d) and depths (F, H, W) on %s expected' % (what, TSDF_LIMITS['frame_words'], t.device))
+    offsets = _pair_offsets(frame_counts, F, what)
+    if len(frame_counts) != V:
+        raise RuntimeError('%s: one frame count per volume' % what)
+    check(lib().se3_tsdf_integrate_stack(_dp(t), _dp(w), None if color is None else _dp(color), V, R, float(voxel_length), float(sdf_trunc), _dp(o),
+                                         _dp(d), depth_elem, None if c is None else _dp(c), color_elem, int(d.shape[1]), int(d.shape[2]), _dp(fr),
+                                         offsets, float(depth_scale), float(depth_trunc), _stream()), 'se3_tsdf_integrate_stack')
+
+
+def tsdf_extract_stack(tsdf, weight, color, voxel_length, origins):
+    """HIP (csrc/tsdf.hip): the surface points of the volumes: a count pass, a scan, one host read of the volumes' counts, a write pass.
+    Returns (points (n, 3) float64, normals (n, 3) float64, colors (n, 3) float64 or None, counts: a list of V ints); volume v owns the
+    next counts[v] rows."""
+    what = 'tsdf_extract_stack'
+    t, w, color, V, R = _tsdf_state(tsdf, weight, color, what)
+    o = _req(origins, torch.float64, 'origins', 2)
+    if tuple(o.shape) != (V, 3) or o.device != t.device:
+        raise RuntimeError('%s: origins (V, 3) on %s expected' % (what, t.device))
+    dev = t.device
+    rows = torch.empty((V * R * R + 1,), dtype=torch.int64, device=dev)
+    stream = _stream()
+    cptr = None if color is None else _dp(color)
+    check(lib().se3_tsdf_extract_stack(_dp(t), _dp(w), cptr, V, R, float(voxel_length), _dp(o), _dp(rows), 0, None, None, None, stream),
+          'se3_tsdf_extract_stack')
+    cuts = rows[::R * R].cpu().tolist()          # (the one host read: the volumes' offsets)
+    total = cuts[-1]
+    out = [torch.empty((total, 3), dtype=torch.float64, device=dev) for _ in range(2 if color is None else 3)]
+    if total:
+        check(lib().se3_tsdf_extract_stack(_dp(t), _dp(w), cptr, V, R, float(voxel_length), _dp(o), _dp(rows), total, _dp(out[0]), _dp(out[1]),
+                                           None if color is None else _dp(out[2]), stream), 'se3_tsdf_extract_stack')
+    return out[0], out[1], None if color is None else out[2], [cuts[v + 1] - cuts[v] for v in range(V)]
+
+
+def depth_points_stack(depths, intrinsics, scaling_factor=1000.0, distance_limit=6.0, convention='reference'):
+    """HIP (csrc/tsdf.hip): the points of F depth images.  depths (F, H, W) uint16 or float32, intrinsics (F, 4) float64 (fx, fy, cx, cy).
+    Returns (points (n, 3) float64 in image order, row-major pixel order within an image; counts: a list of F ints)."""
+    what = 'depth_points_stack'
+    d, elem, _, _ = _tsdf_images(depths, None, what)
+    K = _req(intrinsics, torch.float64, 'intrinsics', 2)
+    F, H, W = (int(s) for s in d.shape)
+    if tuple(K.shape) != (F, 4) or K.device != d.device:
+        raise RuntimeError('%s: intrinsics (F, 4) on %s expected' % (what, d.device))
+    if convention not in DEPTH_CONVENTIONS:
+        raise RuntimeError('%s: convention %r is not one of %s' % (what, convention, ', '.join(sorted(DEPTH_CONVENTIONS))))
+    conv = DEPTH_CONVENTIONS[convention]
+    rows = torch.empty((F * H + 1,), dtype=torch.int64, device=d.device)
+    stream = _stream()
+    check(lib().se3_depth_points_stack(_dp(d), elem, F, H, W, _dp(K), float(scaling_factor), float(distance_limit), conv, _dp(rows), 0, None, stream),
+          'se3_depth_points_stack')
+    cuts = rows[::H].cpu().tolist()
+    total = cuts[-1]
+    out = torch.empty((total, 3), dtype=torch.float64, device=d.device)
+    if total:
+        check(lib().se3_depth_points_stack(_dp(d), elem, F, H, W, _dp(K), float(scaling_factor), float(distance_limit), conv, _dp(rows), total,
+                                           _dp(out), stream), 'se3_depth_points_stack')
+    return out, [cuts[i + 1] - cuts[i] for i in range(F)]
