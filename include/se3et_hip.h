@@ -1454,6 +1454,69 @@ int se3_debug_tsdf_extract_host(const float* tsdf, const float* weight, const fl
 int se3_debug_depth_points_host(const void* depth, int depth_elem, int height, int width, const double* intrinsics, double scaling_factor,
                                 double distance_limit, int convention, int64_t capacity, double* out_points, int64_t* out_count);
 
+/* ---- RGB-D odometry of frame pairs (csrc/rgbd_odometry.hip, csrc/rgbd_odometry_core.h) -----------------------------------------------------------
+ * Open3D's legacy ComputeRGBDOdometry (hybrid and colour Jacobians) with CreateInformationMatrix for up to SE3_PAIR_MAX_PAIRS pairs of frames
+ * per call, nothing read back; the contract is the header comment of csrc/rgbd_odometry.hip.  Frames are the unit of preparation: a call
+ * prepares the pyramids of all F frames once, and pairs name frames.
+ *   se3_rgbd_odometry_stack   depths (F, H, W) uint16 (depth_elem 0) / float32 (1); colors (F, H, W, color_channels) uint8 (color_elem 1) /
+ *                           float32 (2), color_channels 3 or 1; target_flags (F) bytes on the DEVICE: 1 for a frame that is some pair's
+ *                           target (it gets Sobel images).  prepare 1: the pyramids are built into frames_workspace first; 0: they are
+ *                           there from an earlier call with the same frames (the next chunk of pairs).  pairs_host (P, 2) HOST ints
+ *                           (source frame, target frame), intrinsics_host (P, 4) HOST float64 (fx, fy, cx, cy) of level 0,
+ *                           init_transforms (P, 4, 4) float64 on the DEVICE, iterations_host (num_levels) HOST ints, coarsest level first.
+ *                           out_transforms (P, 4, 4) source camera to target camera, out_success (P) bytes, out_status (P) a sum of
+ *                           SE3_RGBD_* bits, out_information (P, 6, 6), out_count (P) int64, all on the DEVICE.  The whole schedule is
+ *                           issued on `stream`: 3 launches per iteration.  Workspaces: se3_rgbd_frames_workspace_bytes and
+ *                           se3_rgbd_pairs_workspace_bytes (0 for sizes that the call would refuse).
+ *   se3_debug_rgbd_odometry_host   the same text on HOST memory, serially, any number of pairs up to SE3_PAIR_MAX_PAIRS.  stop: SE3_RGBD_STOP_*;
+ *                           PREPARED ends after the pyramids (out_pyramids (SE3_RGBD_IMAGES, F, S) float32, S the pixels of all levels, a
+ *                           level after the one before it); CLAIMED after one correspondence pass at stop_level under the initial
+ *                           transform (out_map (P, H W) 64-bit words: all ones, or hi32(q_z) << 32 | source index, a level's H_l W_l
+ *                           entries first); EVALUATED after the normalisation and one iteration at stop_level (out_sums (P,
+ *                           SE3_RGBD_SUMS), out_scales (P, 2), out_transforms the updated transform).  The last four may be NULL. */
+enum se3_rgbd_limit {              /* (NAMED) */
+  SE3_RGBD_MAX_LEVELS = 4,
+  SE3_RGBD_MAX_IMAGE = 8192,       /* height and width of an image at most: SE3_TSDF_MAX_IMAGE */
+  SE3_RGBD_MIN_SIDE = 3,           /* height and width of the coarsest level at least */
+  SE3_RGBD_CHUNK = 2048,           /* target pixels per accumulation workgroup */
+  SE3_RGBD_SUMS = 29,              /* 21 of J^T J, 6 of J^T r, the squared residual, the count */
+  SE3_RGBD_IMAGES = 6,             /* images a frame's pyramid holds per level: I, D, Ix, Iy, Dx, Dy */
+  SE3_RGBD_MAX_ITERATIONS = 1000   /* iterations of one level at most */
+};
+enum se3_rgbd_status {             /* (NAMED: the shared names carry ICP's values) */
+  SE3_RGBD_NONFINITE = 1,
+  SE3_RGBD_TOO_FEW = 2,
+  SE3_RGBD_SINGULAR = 4,
+  SE3_RGBD_EMPTY = 8,              /* no correspondence under the initial transform */
+  SE3_RGBD_STEP_REFUSED = 16
+};
+enum se3_rgbd_method {
+  SE3_RGBD_HYBRID = 0,
+  SE3_RGBD_COLOR = 1
+};
+enum se3_rgbd_stop {
+  SE3_RGBD_STOP_NONE = 0,
+  SE3_RGBD_STOP_PREPARED = 1,
+  SE3_RGBD_STOP_CLAIMED = 2,
+  SE3_RGBD_STOP_EVALUATED = 3
+};
+size_t se3_rgbd_frames_workspace_bytes(int64_t num_frames, int height, int width, int num_levels);
+size_t se3_rgbd_pairs_workspace_bytes(int num_pairs, int height, int width);
+int se3_rgbd_odometry_stack(const void* depths, int depth_elem, const void* colors, int color_elem, int color_channels, int64_t num_frames,
+                            int height, int width, const uint8_t* target_flags, int prepare, const int* pairs_host,
+                            const double* intrinsics_host, int num_pairs, const double* init_transforms, int method,
+                            const int* iterations_host, int num_levels, double depth_scale, double depth_trunc, double min_depth,
+                            double max_depth, double max_depth_diff, double* out_transforms, uint8_t* out_success, int* out_status,
+                            double* out_information, int64_t* out_count, void* frames_workspace, size_t frames_workspace_bytes,
+                            void* pairs_workspace, size_t pairs_workspace_bytes, void* stream);
+int se3_debug_rgbd_odometry_host(const void* depths, int depth_elem, const void* colors, int color_elem, int color_channels,
+                                 int64_t num_frames, int height, int width, const uint8_t* target_flags, const int* pairs,
+                                 const double* intrinsics, int num_pairs, const double* init_transforms, int method, const int* iterations,
+                                 int num_levels, double depth_scale, double depth_trunc, double min_depth, double max_depth,
+                                 double max_depth_diff, int stop, int stop_level, double* out_transforms, uint8_t* out_success,
+                                 int* out_status, double* out_information, int64_t* out_count, float* out_pyramids, uint64_t* out_map,
+                                 double* out_sums, double* out_scales);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3136,3 +3136,72 @@ def depth_points_stack(depths, intrinsics, scaling_factor=1000.0, distance_limit
         check(lib().se3_depth_points_stack(_dp(d), elem, F, H, W, _dp(K), float(scaling_factor), float(distance_limit), conv, _dp(rows), total,
                                            _dp(out), stream), 'se3_depth_points_stack')
     return out, [cuts[i + 1] - cuts[i] for i in range(F)]
+
+
+# ---- RGB-D odometry of frame pairs (csrc/rgbd_odometry.hip) -----------------------------------------------------------------------------------------
+RGBD_LIMITS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_limit'].items()}
+RGBD_STATUS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_status'].items()}
+RGBD_METHODS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_method'].items()}
+RGBD_STOPS = {name[len('SE3_RGBD_STOP_'):].lower(): value for name, value in ENUMS['se3_rgbd_stop'].items()}
+_ws_rgbd = Workspace(1 << 20)
+
+
+def rgbd_frames_workspace(depths, num_levels):
+    """The tensor that holds the pyramids of the frames of depths (F, H, W) for rgbd_odometry_stack: one per call of the public function,
+    shared by its chunks of pairs."""
+    F, H, W = (int(s) for s in depths.shape)
+    nbytes = lib().se3_rgbd_frames_workspace_bytes(F, H, W, int(num_levels))
+    return torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=depths.device)
+
+
+def rgbd_odometry_stack(depths, colors, target_flags, frames_workspace, prepare, pairs, intrinsics, init_transforms, method, iterations,
+                        depth_scale=1000.0, depth_trunc=3.0, min_depth=0.0, max_depth=4.0, max_depth_diff=0.03):
+    """HIP (csrc/rgbd_odometry.hip): RGB-D odometry of up to PAIR_MAX_PAIRS pairs of the F frames, the whole schedule from one C call and
+    nothing read back.  depths (F, H, W) uint16 or float32, colors (F, H, W, 3) or (F, H, W) uint8 or float32, target_flags (F,) uint8 on
+    the device, frames_workspace: rgbd_frames_workspace(depths, len(iterations)); prepare: build the pyramids first (False: they are there
+    from the call before).  pairs: P host tuples (source frame, target frame); intrinsics: P host rows (fx, fy, cx, cy);
+    init_transforms (P, 4, 4) float64 on the device; method: a key of RGBD_METHODS; iterations: per level, coarsest first.  Returns a dict
+    of device tensors: transforms (P, 4, 4) float64, success (P,) bool, status (P,) int32 (RGBD_STATUS bits), information (P, 6, 6)
+    float64, correspondences (P,) int64."""
+    what = 'rgbd_odometry_stack'
+    d, depth_elem, c, color_elem = _rgbd_images(depths, colors, what)
+    F, H, W = (int(s) for s in d.shape)
+    dev = d.device
+    flags = _req(target_flags, torch.uint8, 'target_flags', 1)
+    T0 = _req(init_transforms, torch.float64, 'init_transforms', 3)
+    P, L = len(pairs), len(iterations)
+    if method not in RGBD_METHODS:
+        raise RuntimeError('%s: method %r is not one of %s' % (what, method, ', '.join(sorted(RGBD_METHODS))))
+    if P > PAIR_MAX_PAIRS or tuple(T0.shape) != (P, 4, 4) or len(intrinsics) != P or flags.shape[0] != F or any(x.device != dev for x in (flags, T0)):
+        raise RuntimeError('%s: at most %d pairs per call, with init_transforms (P, 4, 4), P rows of intrinsics and target_flags (F,) on %s'
+                           % (what, PAIR_MAX_PAIRS, dev))
+    pair_table = (ctypes.c_int * max(2 * P, 1))(*[int(f) for pair in pairs for f in pair])
+    K = (ctypes.c_double * max(4 * P, 1))(*[float(k) for row in intrinsics for k in row])
+    its = (ctypes.c_int * max(L, 1))(*[int(n) for n in iterations])
+    out = dict(transforms=torch.empty((P, 4, 4), dtype=torch.float64, device=dev), success=torch.empty((P,), dtype=torch.uint8, device=dev),
+               status=torch.empty((P,), dtype=torch.int32, device=dev), information=torch.empty((P, 6, 6), dtype=torch.float64, device=dev),
+               correspondences=torch.empty((P,), dtype=torch.int64, device=dev))
+    nbytes = lib().se3_rgbd_pairs_workspace_bytes(P, H, W)
+    stream = _stream()
+    ws = _ws_rgbd.get(dev, stream.value, max(nbytes, 256))
+    check(lib().se3_rgbd_odometry_stack(_dp(d), depth_elem, _dp(c), color_elem, 3 if c.dim() == 4 else 1, F, H, W, _dp(flags), 1 if prepare else 0,
+                                        pair_table, K, P, _dp(T0), RGBD_METHODS[method], its, L, float(depth_scale), float(depth_trunc),
+                                        float(min_depth), float(max_depth), float(max_depth_diff), _dp(out['transforms']), _dp(out['success']),
+                                        _dp(out['status']), _dp(out['information']), _dp(out['correspondences']), frames_workspace.data_ptr(),
+                                        frames_workspace.numel(), ws.data_ptr(), nbytes, stream), 'se3_rgbd_odometry_stack')
+    out['success'] = out['success'].to(torch.bool)
+    return out
+
+
+def _rgbd_images(depths, colors, what):
+    """(depths, depth_elem, colors, color_elem) of (F, H, W) uint16 / float32 depths and (F, H, W, 3) or (F, H, W) uint8 / float32 colours."""
+    if not torch.is_tensor(depths) or depths.dtype not in _DEPTH_ELEM:
+        raise RuntimeError('%s: depths must be a uint16 or float32 tensor' % what)
+    d = _req(depths, depths.dtype, 'depths', 3)
+    if not torch.is_tensor(colors) or colors.dtype not in _COLOR_ELEM or colors.dim() not in (3, 4):
+        raise RuntimeError('%s: colors must be a uint8 or float32 tensor (F, H, W, 3) or (F, H, W)' % what)
+    c = _req(colors, colors.dtype, 'colors', colors.dim())
+    if tuple(c.shape) not in (tuple(d.shape), tuple(d.shape) + (3,)) or c.device != d.device:
+        raise RuntimeError('%s: colors must be %s or %s on %s, got %s on %s' % (what, tuple(d.shape) + (3,), tuple(d.shape), d.device, tuple(c.shape),
+                                                                              c.device))
+    return d, _DEPTH_ELEM[d.dtype], c, _COLOR_ELEM[c.dtype]
