@@ -1454,6 +1454,61 @@ int se3_debug_tsdf_extract_host(const float* tsdf, const float* weight, const fl
 int se3_debug_depth_points_host(const void* depth, int depth_elem, int height, int width, const double* intrinsics, double scaling_factor,
                                 double distance_limit, int convention, int64_t capacity, double* out_points, int64_t* out_count);
 
+/* ---- block-sparse TSDF volumes (csrc/tsdf_sparse.hip, csrc/tsdf_sparse_core.h) ---------------------------------------------------------------------
+ * Open3D's ScalableTSDFVolume (integrate, extract_point_cloud) for up to SE3_PAIR_MAX_PAIRS volumes per object; the contract is the header
+ * comment of csrc/tsdf_sparse.hip.  A block is SE3_STSDF_BLOCK^3 voxels; the storage is tsdf, weight (S, 16, 16, 16) float32 and color
+ * (S, 3, 16, 16, 16) float32 or NULL in slots; the directory is the blocks' int64 keys, ascending (5 bits of volume above 3 x
+ * SE3_STSDF_COORD_BITS bits of coordinate + 2^18), with each block's slot (int).  Everything on the DEVICE unless it is called _host.
+ *   se3_stsdf_touch_groups   the pixel tiles of a call: the length of group_offsets is this + 1 (0 for sizes that the call would refuse).
+ *   se3_stsdf_touch_stack    depths (F, H, W) uint16 (depth_elem 0) / float32 (1); poses (F, SE3_STSDF_POSE_WORDS) float64: the 3 x 4
+ *                           camera-to-world pose by rows, then fx, fy, cx, cy; volume v owns the frames [frame_offsets_host[v],
+ *                           frame_offsets_host[v + 1]) (HOST int64).  out_keys NULL: the count pass and the scan; group_offsets becomes the
+ *                           exclusive offsets of the tiles and the total; bad_frames (F) ints, zeroed by the caller, gets a 1 for every
+ *                           frame that touches a block coordinate out of range.  Otherwise the write pass: the (key, frame) records of
+ *                           tile g at [group_offsets[g], group_offsets[g + 1]), in frame order, nothing at or past `capacity`.  The records
+ *                           are a multiset: the caller sorts them (stably, by key) and drops duplicates.
+ *   se3_stsdf_neighbors      out_neighbors (B, 27) ints: the slot of block b + d at [(dx + 1) 9 + (dy + 1) 3 + (dz + 1)], -1 where absent.
+ *   se3_stsdf_integrate_stack  the touched blocks' keys and slots (num_blocks) and their frame lists in CSR form: block i takes the frames
+ *                           block_frames[block_frame_offsets[i], block_frame_offsets[i + 1]) (indices among the call's images, ascending)
+ *                           with the frame table of se3_tsdf_integrate_stack.  A slot outside [0, num_slots) is not touched.
+ *   se3_stsdf_extract_stack  two passes, as se3_tsdf_extract_stack: group_offsets (16 B + 1) int64 over the groups (block, x) in key order.
+ *   se3_debug_stsdf_*_host   the same text on HOST memory, serially: every pointer a host pointer.  The touch entry returns the records
+ *                           sorted by (key, frame) without duplicates (out_keys NULL: *out_count alone) and *out_bad_frame, the first
+ *                           frame out of range or -1; the extract entry finds the neighbours itself and returns the blocks' offsets
+ *                           (B + 1) (out_points NULL: those alone). */
+enum se3_stsdf_limit {             /* (NAMED) */
+  SE3_STSDF_BLOCK = 16,            /* voxels per block side */
+  SE3_STSDF_COORD_BITS = 19,       /* a block coordinate lies in [-2^18, 2^18) */
+  SE3_STSDF_MAX_TRUNC_VOXELS = 16, /* sdf_trunc in (0, this many voxel lengths]: one block at most */
+  SE3_STSDF_MAX_STRIDE = 64,       /* largest allocation stride */
+  SE3_STSDF_POSE_WORDS = 16        /* float64 words of a frame's row of the pose table */
+};
+int64_t se3_stsdf_touch_groups(int64_t num_frames, int height, int width, int stride);
+int se3_stsdf_touch_stack(const void* depths, int depth_elem, int64_t num_frames, int height, int width, const double* poses,
+                          const int64_t* frame_offsets_host, int num_volumes, double voxel_length, double sdf_trunc, int stride,
+                          double depth_scale, double depth_trunc, int64_t* group_offsets, int* bad_frames, int64_t capacity, int64_t* out_keys,
+                          int* out_frames, void* stream);
+int se3_stsdf_neighbors(const int64_t* keys, const int* slots, int64_t num_blocks, int* out_neighbors, void* stream);
+int se3_stsdf_integrate_stack(float* tsdf, float* weight, float* color, int64_t num_slots, const int64_t* block_keys, const int* block_slots,
+                              int64_t num_blocks, const int64_t* block_frame_offsets, const int* block_frames, double voxel_length,
+                              double sdf_trunc, const void* depths, int depth_elem, const void* colors, int color_elem, int64_t num_frames,
+                              int height, int width, const float* frames, double depth_scale, double depth_trunc, void* stream);
+int se3_stsdf_extract_stack(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* neighbors,
+                            int64_t num_blocks, double voxel_length, int64_t* group_offsets, int64_t capacity, double* out_points,
+                            double* out_normals, double* out_colors, void* stream);
+int se3_debug_stsdf_touch_host(const void* depths, int depth_elem, int64_t num_frames, int height, int width, const double* poses,
+                               const int64_t* frame_offsets, int num_volumes, double voxel_length, double sdf_trunc, int stride,
+                               double depth_scale, double depth_trunc, int64_t capacity, int64_t* out_keys, int* out_frames, int64_t* out_count,
+                               int64_t* out_bad_frame);
+int se3_debug_stsdf_integrate_host(float* tsdf, float* weight, float* color, int64_t num_slots, const int64_t* block_keys,
+                                   const int* block_slots, int64_t num_blocks, const int64_t* block_frame_offsets, const int* block_frames,
+                                   double voxel_length, double sdf_trunc, const void* depths, int depth_elem, const void* colors,
+                                   int color_elem, int64_t num_frames, int height, int width, const float* frames, double depth_scale,
+                                   double depth_trunc);
+int se3_debug_stsdf_extract_host(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* slots,
+                                 int64_t num_blocks, double voxel_length, int64_t capacity, double* out_points, double* out_normals,
+                                 double* out_colors, int64_t* out_block_offsets);
+
 /* ---- RGB-D odometry of frame pairs (csrc/rgbd_odometry.hip, csrc/rgbd_odometry_core.h) -----------------------------------------------------------
  * Open3D's legacy ComputeRGBDOdometry (hybrid and colour Jacobians) with CreateInformationMatrix for up to SE3_PAIR_MAX_PAIRS pairs of frames
  * per call, nothing read back; the contract is the header comment of csrc/rgbd_odometry.hip.  Frames are the unit of preparation: a call

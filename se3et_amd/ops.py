@@ -3138,6 +3138,119 @@ def depth_points_stack(depths, intrinsics, scaling_factor=1000.0, distance_limit
     return out, [cuts[i + 1] - cuts[i] for i in range(F)]
 
 
+# ---- block-sparse TSDF volumes (csrc/tsdf_sparse.hip) ------------------------------------------------------------------------------------------------
+STSDF_LIMITS = {name[len('SE3_STSDF_'):].lower(): value for name, value in ENUMS['se3_stsdf_limit'].items()}
+STSDF_BLOCK = STSDF_LIMITS['block']
+
+
+def _stsdf_storage(tsdf, weight, color, what):
+    t = _req(tsdf, torch.float32, 'tsdf', 4)
+    w = _req(weight, torch.float32, 'weight', 4)
+    B = STSDF_BLOCK
+    if tuple(t.shape[1:]) != (B, B, B) or w.shape != t.shape or w.device != t.device:
+        raise RuntimeError('%s: tsdf and weight must both be (S, %d, %d, %d) on one device' % (what, B, B, B))
+    if color is not None:
+        color = _req(color, torch.float32, 'color', 5)
+        if tuple(color.shape) != (t.shape[0], 3, B, B, B) or color.device != t.device:
+            raise RuntimeError('%s: color must be (S, 3, %d, %d, %d) on %s' % (what, B, B, B, t.device))
+    return t, w, color
+
+
+def _stsdf_directory(keys, slots, what, device):
+    k, s = _req(keys, torch.int64, 'keys', 1), _req(slots, torch.int32, 'slots', 1)
+    if k.shape != s.shape or k.device != device or s.device != device:
+        raise RuntimeError('%s: keys (B,) int64 and slots (B,) int32 on %s expected' % (what, device))
+    return k, s
+
+
+def stsdf_touch_stack(depths, poses, frame_counts, voxel_length, sdf_trunc, stride=4, depth_scale=1000.0, depth_trunc=3.0):
+    """HIP (csrc/tsdf_sparse.hip): the blocks that the frames touch (contract A).  depths (F, H, W) uint16 or float32, poses
+    (F, STSDF_LIMITS['pose_words']) float64: the 3 x 4 camera pose by rows, then fx, fy, cx, cy; frame_counts: the frames of each volume.
+    A count pass, one host read (the records and the first frame out of range), a write pass; then a stable sort by key and the removal
+    of duplicates in torch.  Returns (keys (n,) int64, frames (n,) int32, bad_frame): the records ascending in (key, frame), each once;
+    bad_frame is -1, or the first frame that touches a block coordinate out of range (the records are empty then)."""
+    what = 'stsdf_touch_stack'
+    d, depth_elem, _, _ = _tsdf_images(depths, None, what)
+    P = _req(poses, torch.float64, 'poses', 2)
+    F, H, W = (int(s) for s in d.shape)
+    if tuple(P.shape) != (F, STSDF_LIMITS['pose_words']) or P.device != d.device:
+        raise RuntimeError('%s: poses (F, %d) on %s expected' % (what, STSDF_LIMITS['pose_words'], d.device))
+    offsets = _pair_offsets(frame_counts, F, what)
+    dev = d.device
+    groups = lib().se3_stsdf_touch_groups(F, H, W, int(stride))
+    rows = torch.empty((groups + 1,), dtype=torch.int64, device=dev)
+    bad = torch.zeros((F + 1,), dtype=torch.int32, device=dev)
+    stream = _stream()
+    args = (_dp(d), depth_elem, F, H, W, _dp(P), offsets, len(frame_counts), float(voxel_length), float(sdf_trunc), int(stride), float(depth_scale),
+            float(depth_trunc), _dp(rows))
+    check(lib().se3_stsdf_touch_stack(*args, _dp(bad), 0, None, None, stream), 'se3_stsdf_touch_stack')
+    bad[F] = 1
+    total, first_bad = torch.stack([rows[groups], torch.argmax(bad).to(torch.int64)]).cpu().tolist()          # (the one host read)
+    keys = torch.empty((0 if first_bad < F else total,), dtype=torch.int64, device=dev)
+    frames = torch.empty((keys.shape[0],), dtype=torch.int32, device=dev)
+    if first_bad < F or total == 0:
+        return keys, frames, (first_bad if first_bad < F else -1)
+    check(lib().se3_stsdf_touch_stack(*args, None, total, _dp(keys), _dp(frames), stream), 'se3_stsdf_touch_stack')
+    keys, order = torch.sort(keys, stable=True)          # (the records come in frame order: each key's frames stay ascending)
+    frames = frames[order]
+    first = torch.ones_like(keys, dtype=torch.bool)
+    first[1:] = (keys[1:] != keys[:-1]) | (frames[1:] != frames[:-1])
+    return keys[first].contiguous(), frames[first].contiguous(), -1
+
+
+def stsdf_neighbors(keys, slots):
+    """HIP (csrc/tsdf_sparse.hip): (B, 27) int32, the slots of the 27 blocks around each block of the sorted directory, -1 where absent."""
+    k, s = _stsdf_directory(keys, slots, 'stsdf_neighbors', keys.device)
+    out = torch.empty((k.shape[0], 27), dtype=torch.int32, device=k.device)
+    check(lib().se3_stsdf_neighbors(_dp(k), _dp(s), int(k.shape[0]), _dp(out), _stream()), 'se3_stsdf_neighbors')
+    return out
+
+
+def stsdf_integrate_stack(tsdf, weight, color, keys, slots, frame_offsets, frame_ids, voxel_length, sdf_trunc, depths, frames, colors=None,
+                          depth_scale=1000.0, depth_trunc=3.0):
+    """HIP (csrc/tsdf_sparse.hip): the touched blocks integrate their frames, in place, one launch (contract B).  tsdf, weight
+    (S, 16, 16, 16), color (S, 3, 16, 16, 16) or None: the storage; keys, slots (n,): the touched blocks; block i takes the frames
+    frame_ids[frame_offsets[i]:frame_offsets[i + 1]] (int64 (n + 1,), int32); depths, frames, colors as tsdf_integrate_stack."""
+    what = 'stsdf_integrate_stack'
+    t, w, color = _stsdf_storage(tsdf, weight, color, what)
+    k, s = _stsdf_directory(keys, slots, what, t.device)
+    d, depth_elem, c, color_elem = _tsdf_images(depths, colors, what)
+    fr = _req(frames, torch.float32, 'frames', 2)
+    csr, ids = _req(frame_offsets, torch.int64, 'frame_offsets', 1), _req(frame_ids, torch.int32, 'frame_ids', 1)
+    F, n = int(d.shape[0]), int(k.shape[0])
+    if tuple(fr.shape) != (F, TSDF_LIMITS['frame_words']) or csr.shape[0] != n + 1 or any(x.device != t.device for x in (fr, d, csr, ids)):
+        raise RuntimeError('%s: frames (F, %d), frame_offsets (n + 1,) and frame_ids on %s expected' % (what, TSDF_LIMITS['frame_words'], t.device))
+    check(lib().se3_stsdf_integrate_stack(_dp(t), _dp(w), None if color is None else _dp(color), int(t.shape[0]), _dp(k), _dp(s), n, _dp(csr),
+                                          _dp(ids), float(voxel_length), float(sdf_trunc), _dp(d), depth_elem, None if c is None else _dp(c),
+                                          color_elem, F, int(d.shape[1]), int(d.shape[2]), _dp(fr), float(depth_scale), float(depth_trunc),
+                                          _stream()), 'se3_stsdf_integrate_stack')
+
+
+def stsdf_extract_stack(tsdf, weight, color, keys, neighbors, voxel_length, block_cuts):
+    """HIP (csrc/tsdf_sparse.hip): the surface points of the blocks in key order (contract C): a count pass, a scan, one host read, a write
+    pass.  neighbors: stsdf_neighbors of the directory; block_cuts (V + 1,) int64 on the device: volume v owns the blocks
+    [block_cuts[v], block_cuts[v + 1]).  Returns (points, normals, colors or None, counts: a list of V ints)."""
+    what = 'stsdf_extract_stack'
+    t, w, color = _stsdf_storage(tsdf, weight, color, what)
+    k, nb = _req(keys, torch.int64, 'keys', 1), _req(neighbors, torch.int32, 'neighbors', 2)
+    n = int(k.shape[0])
+    if tuple(nb.shape) != (n, 27) or k.device != t.device or nb.device != t.device:
+        raise RuntimeError('%s: keys (B,) and neighbors (B, 27) on %s expected' % (what, t.device))
+    dev = t.device
+    rows = torch.empty((n * STSDF_BLOCK + 1,), dtype=torch.int64, device=dev)
+    stream = _stream()
+    cptr = None if color is None else _dp(color)
+    check(lib().se3_stsdf_extract_stack(_dp(t), _dp(w), cptr, _dp(k), _dp(nb), n, float(voxel_length), _dp(rows), 0, None, None, None, stream),
+          'se3_stsdf_extract_stack')
+    cuts = rows[block_cuts * STSDF_BLOCK].cpu().tolist()          # (the one host read: the volumes' offsets)
+    total = cuts[-1]
+    out = [torch.empty((total, 3), dtype=torch.float64, device=dev) for _ in range(2 if color is None else 3)]
+    if total:
+        check(lib().se3_stsdf_extract_stack(_dp(t), _dp(w), cptr, _dp(k), _dp(nb), n, float(voxel_length), _dp(rows), total, _dp(out[0]),
+                                            _dp(out[1]), None if color is None else _dp(out[2]), stream), 'se3_stsdf_extract_stack')
+    return out[0], out[1], None if color is None else out[2], [cuts[v + 1] - cuts[v] for v in range(len(cuts) - 1)]
+
+
 # ---- RGB-D odometry of frame pairs (csrc/rgbd_odometry.hip) -----------------------------------------------------------------------------------------
 RGBD_LIMITS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_limit'].items()}
 RGBD_STATUS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_status'].items()}

@@ -1,0 +1,299 @@
+"""Block-sparse TSDF volumes on the device: Open3D's ScalableTSDFVolume (integrate, extract_point_cloud) for a batch of scenes, and the
+recipe of its integrate_scene.py, as HIP kernels (csrc/tsdf_sparse.hip with csrc/tsdf_sparse_core.h; everything per voxel is
+csrc/tsdf_core.h, the text of the uniform volumes of se3et_amd/tsdf.py).  Blocks of 16^3 voxels exist only where a frame saw a surface.
+
+  SparseTSDFVolumes(num_volumes, voxel_length, sdf_trunc, color=False, stride=4, device=None)
+        .integrate(depths, intrinsics, extrinsics, frame_counts=None, colors=None, depth_scale=1000.0, depth_trunc=3.0)   returns self
+        .num_blocks, .block_coords (B, 4) int64 (volume, bx, by, bz) in key order
+        .state()                     tsdf, weight (B, 16, 16, 16) and color (B, 3, 16, 16, 16) or None, in the same order (copies)
+        .extract_point_clouds()      three lists, one entry per volume, as TSDFVolumes.extract_point_clouds
+        .allocate_blocks(coords)     blocks by hand, zeros; .tsdf, .weight, .color are the storage, block i of the directory at .slots[i]
+  fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_length, sdf_trunc, colors_list=None, stride=4, ...)
+        construct, integrate and extract for a list of scenes: (points_list, normals_list, colors_list or None)
+  integrate_scene_rgbd(depths_list, colors_list, intrinsics, frame_poses, fragment_poses, voxel_length, sdf_trunc, ...)
+        integrate_scene.py: every frame of every fragment into one scene volume: points, normals, colours and the volume
+
+The calls take GPU tensors only (there is no CPU path) and at most ops.PAIR_MAX_PAIRS volumes per object.  What a call refuses is a
+ValueError raised before any state changes: what TSDFVolumes.integrate refuses, an sdf_trunc beyond one block, a stride outside
+ops.STSDF_LIMITS, an extrinsic that cannot be inverted, a frame that touches a block coordinate out of range (the error names the frame).
+Storage grows geometrically; the host reads counts only: a call's records, its new blocks, the volumes' points.
+
+State.  A block is 16^3 voxels of length vl; block (v, b) of volume v has its corner at o_a = L f64(b_a), L = 16 vl, and is a uniform
+volume of resolution 16 there.  The key packs 5 bits of volume above 3 x 19 bits of b_a + 2^18 into a non-negative int64, so key order
+is (volume, bx, by, bz) lexicographic.
+
+Contract A: allocation (the kernel file carries the same text).  Float64 unless said.  Frame f of volume v has extrinsic E (world to
+camera) and camera pose P, its inverse, computed once on the host in float64 (camera_poses).
+  1. Sampled pixels are rows i and columns j that are multiples of `stride` (default 4, Open3D's depth_sampling_stride).
+  2. d = f32(raw) / f32(depth_scale) in float32; d >= f32(depth_trunc) makes d = 0; the pixel is skipped unless d > 0: item 4 of the
+     uniform integration, so allocation and integration agree on which pixels exist.
+  3. z = f64(d), x = ((j - cx) z) / fx, y = ((i - cy) z) / fy, with the float64 intrinsics.
+  4. q_a = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3].  A pixel with a non-finite q is skipped.
+  5. lo_a = floor((q_a - sdf_trunc) / L), hi_a = floor((q_a + sdf_trunc) / L).  Frame f touches every block (v, b) with lo <= b <= hi.
+     sdf_trunc is at most L, so a pixel touches 27 blocks or fewer (64 where the two quotients round apart).
+  6. A touched coordinate outside [-2^18, 2^18) makes the call raise ValueError, naming the frame, before any state changes.
+A block exists from the first call in which a frame touches it, starts as zeros and never disappears.
+
+Contract B: integration.  Block (v, b) integrates exactly the frames that touch it (Open3D's rule), in ascending frame order, as the
+uniform contract of se3et_amd/tsdf.py does for a volume of resolution 16 with origin o: its tsdf, weight and colour are bit-identical to
+TSDFVolumes(1, 16, vl, trunc, origins=[o]) given that frame subset.  The result does not depend on how the frames are split over calls,
+on the other volumes of the batch, or on when the storage grew.
+
+Contract C: extraction.  Float64.
+  1. Output order is ascending key, then (x, y, z, axis) inside a block.
+  2. Usability and the sign test are those of the uniform extraction.  There is no border exclusion.
+  3. The neighbour of local voxel idx along axis i is idx + e_i in the same block, and voxel idx_i = 0 of block b + e_i when idx_i = 15.
+     An absent block gives no point.
+  4. Point, colour and normal follow items 3 and 4 of the uniform extraction in block-local coordinates: p0_a = vl / 2 + vl idx_a, and the
+     returned point is p + o.
+  5. T(q) has g_a = q_a / vl - 0.5 in [-0.99, 16.99], so floor(g_a) is in [-1, 16] and the far corner of the stencil is at most 17: every
+     read falls in the block or one of its 26 neighbours.
+  6. A corner in an absent block reads 0, like an unobserved voxel.
+
+Departures from Open3D.  Open3D allocates through a hash map, so the order of its units follows the order of insertion; here the order is
+the key order, and the order in which a call's records are deduplicated is irrelevant.  Allocation and integration share one depth rule
+(item 2; Open3D back-projects a float depth image with its own truncation).  integrate_scene_rgbd inverts a camera pose as a rigid
+transform (R^T, -R^T t), not as a general matrix.  Weights have no cap, colours are stored in [0, 1], the surface test is a sign test."""
+import numpy as np
+import torch
+
+from . import ops as _ops
+from .stacking import PAIR_MAX_PAIRS, as_tensor, device_of, exclusive_offsets, to_device, transforms_of
+from .tsdf import _COLOR_DTYPES, _DEPTH_DTYPES, _gpu_only, _images, _intrinsics, _join, _positive
+
+_FAMILY = 'sparse TSDF fusion'
+_LIMITS = _ops.STSDF_LIMITS
+_BLOCK = _LIMITS['block']
+_BITS = _LIMITS['coord_bits']
+_BIAS = 1 << (_BITS - 1)
+_MIN_SLOTS = 64
+
+
+def block_keys(coords):
+    """(n, 4) integers (volume, bx, by, bz) -> (n,) int64 keys, where they are."""
+    c = as_tensor(coords).to(torch.int64).reshape(-1, 4)
+    return (c[:, 0] << (3 * _BITS)) | ((c[:, 1] + _BIAS) << (2 * _BITS)) | ((c[:, 2] + _BIAS) << _BITS) | (c[:, 3] + _BIAS)
+
+
+def key_coords(keys):
+    """(n,) int64 keys -> (n, 4) int64 (volume, bx, by, bz)."""
+    mask = (1 << _BITS) - 1
+    return torch.stack([keys >> (3 * _BITS), ((keys >> (2 * _BITS)) & mask) - _BIAS, ((keys >> _BITS) & mask) - _BIAS, (keys & mask) - _BIAS], 1)
+
+
+def camera_poses(extrinsics, what='camera_poses'):
+    """(F, 4, 4) float64 numpy: the inverses of the extrinsics, on the host (contract A).  ValueError for one that cannot be inverted."""
+    E = np.ascontiguousarray(as_tensor(extrinsics).detach().cpu().to(torch.float64).numpy()).reshape(-1, 4, 4)
+    P = np.empty_like(E)
+    for f in range(len(E)):
+        try:
+            with np.errstate(all='ignore'):
+                P[f] = np.linalg.inv(E[f])
+        except np.linalg.LinAlgError:
+            P[f] = np.nan
+        if not np.isfinite(P[f]).all():
+            raise ValueError('%s: the extrinsic of frame %d cannot be inverted' % (what, f))
+    return P
+
+
+def rigid_inverse(T):
+    """(n, 4, 4) -> (n, 4, 4): (R^T, -R^T t), where the transforms are."""
+    R, t = T[:, :3, :3].transpose(1, 2), T[:, :3, 3:]
+    out = torch.zeros_like(T)
+    out[:, :3, :3], out[:, :3, 3:], out[:, 3, 3] = R, -(R @ t), 1.0
+    return out
+
+
+class SparseTSDFVolumes:
+    """V block-sparse TSDF volumes on the device (the module docstring carries the contract).  .keys (B,) int64 is the directory in key
+    order and .slots (B,) int32 each block's place in the storage .tsdf, .weight (S, 16, 16, 16) and .color (S, 3, 16, 16, 16) or None,
+    S >= B; slots are handed out in the order of allocation and never move."""
+
+    def __init__(self, num_volumes, voxel_length, sdf_trunc, color=False, stride=4, device=None):
+        what = 'SparseTSDFVolumes'
+        if int(num_volumes) != num_volumes or not 0 <= int(num_volumes) <= PAIR_MAX_PAIRS:
+            raise ValueError('%s: num_volumes %r is not an integer in [0, %d]' % (what, num_volumes, PAIR_MAX_PAIRS))
+        self.voxel_length = _positive(what, 'voxel_length', voxel_length)
+        trunc = float(sdf_trunc)
+        if not (np.isfinite(trunc) and trunc > 0 and trunc <= _LIMITS['max_trunc_voxels'] * self.voxel_length and np.float32(trunc) > 0):
+            raise ValueError('%s: sdf_trunc %r is not in (0, %d voxel lengths]' % (what, sdf_trunc, _LIMITS['max_trunc_voxels']))
+        if int(stride) != stride or not 1 <= int(stride) <= _LIMITS['max_stride']:
+            raise ValueError('%s: stride %r is not an integer in [1, %d]' % (what, stride, _LIMITS['max_stride']))
+        self.num_volumes, self.sdf_trunc, self.stride, self.device = int(num_volumes), trunc, int(stride), device_of(device)
+        self.has_color = bool(color)
+        self.keys = torch.zeros((0,), dtype=torch.int64, device=self.device)
+        self.slots = torch.zeros((0,), dtype=torch.int32, device=self.device)
+        self.tsdf = self.weight = self.color = None
+        self._reserve(0)
+        self._neighbors = None
+
+    # ---- storage and directory ------------------------------------------------------------------------------------------------------------
+    def _reserve(self, blocks):
+        """Room for `blocks` slots: at least twice the storage there is, zeros behind the blocks in use, the blocks in use as they are."""
+        have = 0 if self.tsdf is None else int(self.tsdf.shape[0])
+        if self.tsdf is not None and blocks <= have:
+            return
+        size = max(blocks, 2 * have, _MIN_SLOTS if blocks else 0)
+        used = self.num_blocks
+
+        def grown(old, *shape):
+            new = torch.zeros((size,) + shape, dtype=torch.float32, device=self.device)
+            if old is not None and used:
+                new[:used].copy_(old[:used])
+            return new
+        self.tsdf, self.weight = grown(self.tsdf, _BLOCK, _BLOCK, _BLOCK), grown(self.weight, _BLOCK, _BLOCK, _BLOCK)
+        if self.has_color:
+            self.color = grown(self.color, 3, _BLOCK, _BLOCK, _BLOCK)
+
+    def _add_keys(self, keys):
+        """The sorted, distinct keys join the directory; returns the slots of `keys`.  One host read: the number of new blocks."""
+        at = torch.searchsorted(self.keys, keys)
+        known = torch.zeros_like(keys, dtype=torch.bool)
+        if self.num_blocks:
+            known = self.keys[at.clamp(max=self.num_blocks - 1)] == keys
+        fresh = keys[~known]
+        n = int(fresh.shape[0])          # (the host waits for the count)
+        if n:
+            used = self.num_blocks
+            self._reserve(used + n)
+            merged, order = torch.sort(torch.cat([self.keys, fresh]))
+            self.slots = torch.cat([self.slots, torch.arange(used, used + n, dtype=torch.int32, device=self.device)])[order].contiguous()
+            self.keys = merged.contiguous()
+            self._neighbors = None
+        return self.slots[torch.searchsorted(self.keys, keys)].contiguous()
+
+    @property
+    def num_blocks(self):
+        return int(self.keys.shape[0])
+
+    @property
+    def block_coords(self):
+        return key_coords(self.keys)
+
+    @torch.no_grad()
+    def allocate_blocks(self, coords):
+        """Make the blocks (n, 4) (volume, bx, by, bz) exist, as zeros where they are new.  Returns their slots (n,) int32, in the order given."""
+        what = 'SparseTSDFVolumes.allocate_blocks'
+        c = as_tensor(coords).to(torch.int64).reshape(-1, 4)
+        if c.numel() and (int(c[:, 0].min()) < 0 or int(c[:, 0].max()) >= self.num_volumes or int(c[:, 1:].min()) < -_BIAS or int(c[:, 1:].max()) >= _BIAS):
+            raise ValueError('%s: (volume, bx, by, bz) with the volume in [0, %d) and coordinates in [%d, %d) expected' % (what, self.num_volumes, -_BIAS,
+                                                                                                                         _BIAS))
+        keys = block_keys(c).to(self.device)
+        self._add_keys(torch.unique(keys))
+        return self.slots[torch.searchsorted(self.keys, keys)]
+
+    def state(self):
+        """(tsdf, weight (B, 16, 16, 16), color (B, 3, 16, 16, 16) or None) in key order: copies."""
+        at = self.slots.long()
+        return self.tsdf[at], self.weight[at], None if self.color is None else self.color[at]
+
+    # ---- integration ------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def integrate(self, depths, intrinsics, extrinsics, frame_counts=None, colors=None, depth_scale=1000.0, depth_trunc=3.0):
+        """Integrate F frames: the arguments of TSDFVolumes.integrate.  The frames allocate the blocks they touch (contract A), then every
+        touched block integrates its frames (contract B).  Frames may arrive over several calls."""
+        what = 'SparseTSDFVolumes.integrate'
+        V, dev = self.num_volumes, self.device
+        d = _images(what, depths, 'depths', _DEPTH_DTYPES)
+        F = int(d.shape[0])
+        if (colors is not None) != self.has_color:
+            raise ValueError('%s: colours are %s, but the volumes were made %s colour' % (what, 'given' if colors is not None else 'missing',
+                                                                                         'with' if self.has_color else 'without'))
+        c = None
+        if colors is not None:
+            c = _images(what, colors, 'colors', _COLOR_DTYPES, (3,))
+            if tuple(c.shape[:3]) != tuple(d.shape):
+                raise ValueError('%s: colors %s do not match depths %s' % (what, tuple(c.shape), tuple(d.shape)))
+        if frame_counts is None:
+            if V != 1:
+                raise ValueError('%s: frame_counts is required for %d volumes' % (what, V))
+            frame_counts = [F]
+        counts = [int(n) for n in (frame_counts.tolist() if hasattr(frame_counts, 'tolist') else frame_counts)]
+        if len(counts) != V or any(n < 0 for n in counts) or sum(counts) != F:
+            raise ValueError('%s: frame_counts %r must be %d counts >= 0 that sum to the %d frames given' % (what, counts, V, F))
+        scale, far = _positive(what, 'depth_scale', depth_scale), _positive(what, 'depth_trunc', depth_trunc)
+        E = transforms_of(extrinsics, F, what, dev)
+        K = _intrinsics(what, intrinsics, F, torch.float64)
+        table = torch.cat([E[:, :3, :].reshape(F, 12).to(torch.float32), K.to(device=dev, dtype=torch.float32)], 1).contiguous()
+        if not bool(torch.isfinite(table).all()):
+            raise ValueError('%s: an extrinsic or an intrinsic is not finite in float32' % what)
+        P = camera_poses(E, what)
+        poses = torch.cat([torch.from_numpy(P[:, :3, :].reshape(F, 12)), K.cpu()], 1).contiguous()
+        _gpu_only(what, dev, volumes=self.tsdf, depths=d, colors=c)
+        if F == 0:
+            return self
+        keys, frames, bad = _ops.stsdf_touch_stack(d, poses.to(dev), counts, self.voxel_length, self.sdf_trunc, self.stride, scale, far)
+        if bad >= 0:
+            raise ValueError('%s: frame %d touches a block coordinate outside [%d, %d)' % (what, bad, -_BIAS, _BIAS))
+        if keys.shape[0] == 0:
+            return self
+        touched, per_block = torch.unique_consecutive(keys, return_counts=True)
+        csr = torch.zeros((touched.shape[0] + 1,), dtype=torch.int64, device=dev)
+        csr[1:] = torch.cumsum(per_block, 0)
+        slots = self._add_keys(touched)
+        _ops.stsdf_integrate_stack(self.tsdf, self.weight, self.color, touched, slots, csr, frames, self.voxel_length, self.sdf_trunc, d, table, c,
+                                   scale, far)
+        return self
+
+    # ---- extraction -------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def extract_point_clouds(self):
+        """(points_list, normals_list, colors_list): per volume (n, 3) float64 tensors on the device, colours None without colour.  The
+        host reads the volumes' counts, nothing else."""
+        V, dev = self.num_volumes, self.device
+        if self.num_blocks == 0:
+            empty = [torch.zeros((0, 3), dtype=torch.float64, device=dev) for _ in range(V)]
+            return empty, [e.clone() for e in empty], [e.clone() if self.has_color else None for e in empty]
+        if self._neighbors is None:
+            self._neighbors = _ops.stsdf_neighbors(self.keys, self.slots)
+        cuts = torch.searchsorted(self.keys, to_device([v << (3 * _BITS) for v in range(V + 1)], torch.int64, dev))
+        p, n, c, counts = _ops.stsdf_extract_stack(self.tsdf, self.weight, self.color, self.keys, self._neighbors, self.voxel_length, cuts)
+        return list(torch.split(p, counts)), list(torch.split(n, counts)), list(torch.split(c, counts)) if c is not None else [None] * V
+
+
+@torch.no_grad()
+def fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_length, sdf_trunc, colors_list=None, stride=4, depth_scale=1000.0,
+                             depth_trunc=3.0, device=None):
+    """One sparse volume per scene: construct, integrate and extract in one call; the lists of fuse_depth_frames without a resolution or
+    origins.  Returns (points_list, normals_list, colors_list or None)."""
+    what = 'fuse_depth_frames_sparse'
+    V = len(depths_list)
+    if len(extrinsics_list) != V or (colors_list is not None and len(colors_list) != V):
+        raise ValueError('%s: one entry per scene expected in every list (%d scenes)' % (what, V))
+    dev = device_of(device, depths_list)
+    volumes = SparseTSDFVolumes(V, voxel_length, sdf_trunc, colors_list is not None, stride, dev)
+    if V:
+        counts = [int(d.shape[0]) for d in depths_list]
+        if isinstance(intrinsics, (list, tuple)) and len(intrinsics) == V and not np.isscalar(intrinsics[0]):
+            K = torch.cat([_intrinsics(what, k, n, torch.float64).to(dev) for k, n in zip(intrinsics, counts)], 0)
+        else:
+            K = intrinsics
+        E = torch.cat([transforms_of(e, n, what, dev) for e, n in zip(extrinsics_list, counts)], 0)
+        volumes.integrate(_join(what, depths_list), K, E, counts, None if colors_list is None else _join(what, colors_list), depth_scale,
+                          depth_trunc)
+    points, normals, colors = volumes.extract_point_clouds()
+    return points, normals, colors if colors_list is not None else None
+
+
+@torch.no_grad()
+def integrate_scene_rgbd(depths_list, colors_list, intrinsics, frame_poses, fragment_poses, voxel_length, sdf_trunc, stride=4, depth_scale=1000.0,
+                         depth_trunc=3.0, device=None):
+    """Open3D's integrate_scene.py: frame i of fragment g has the camera-to-world pose fragment_poses[g] @ frame_poses[g][i] and is
+    integrated under its rigid inverse, computed on the device; all frames go into one scene volume.  depths_list, colors_list: per
+    fragment (F_g, H, W) and (F_g, H, W, 3) on the device (colors_list None: no colour); frame_poses: per fragment (F_g, 4, 4), what
+    make_fragments_rgbd returns as 'poses'; fragment_poses: (G, 4, 4), what multiway_registration returns as 'poses'; intrinsics (4,) or
+    (sum F_g, 4).  Returns (points, normals, colors or None, volume): (n, 3) float64 on the device and the SparseTSDFVolumes."""
+    what = 'integrate_scene_rgbd'
+    G = len(depths_list)
+    if len(frame_poses) != G or (colors_list is not None and len(colors_list) != G):
+        raise ValueError('%s: one entry per fragment expected in every list (%d fragments)' % (what, G))
+    dev = device_of(device, depths_list)
+    volume = SparseTSDFVolumes(1, voxel_length, sdf_trunc, colors_list is not None, stride, dev)
+    if G:
+        counts = [int(d.shape[0]) for d in depths_list]
+        fragment = transforms_of(fragment_poses, G, what, dev, finite=True)
+        world = torch.cat([fragment[g:g + 1] @ transforms_of(frame_poses[g], n, what, dev, finite=True) for g, n in enumerate(counts)], 0)
+        volume.integrate(_join(what, depths_list), intrinsics, rigid_inverse(world), None, None if colors_list is None else _join(what, colors_list),
+                         depth_scale, depth_trunc)
+    points, normals, colors = volume.extract_point_clouds()
+    return points[0], normals[0], colors[0] if colors_list is not None else None, volume
