@@ -1572,6 +1572,46 @@ int se3_debug_rgbd_odometry_host(const void* depths, int depth_elem, const void*
                                  int* out_status, double* out_information, int64_t* out_count, float* out_pyramids, uint64_t* out_map,
                                  double* out_sums, double* out_scales);
 
+/* ---- triangle meshes from the TSDF volumes (csrc/tsdf_mesh.hip, csrc/tsdf_mesh_core.h, csrc/mesh_table.h) -----------------------------------------
+ * Open3D's extract_triangle_mesh for the uniform and the block-sparse volumes above, up to SE3_PAIR_MAX_PAIRS volumes per call: marching
+ * cubes with a deterministic vertex numbering and no atomics; the contract, the rule of the triangle table included, is the header comment
+ * of csrc/tsdf_mesh.hip.  The state is that of se3_tsdf_extract_stack / se3_stsdf_extract_stack.  Everything on the DEVICE unless it is
+ * called _host.
+ *   se3_tsdf_mesh_stack     two passes.  out_vertices NULL: the count pass and the scans; vertex_offsets and triangle_offsets (V R R + 1)
+ *                           int64 each become the exclusive offsets of the rows (v, x, y) and the totals.  Otherwise the write pass:
+ *                           out_vertices, out_normals and (with color) out_colors (vertex_capacity, 3) float64, out_triangles
+ *                           (triangle_capacity, 3) int64; volume v's vertices at [vertex_offsets[v R R], vertex_offsets[(v + 1) R R]), its
+ *                           triangles likewise, and a triangle names vertices by their number within the volume.  Nothing is written
+ *                           at or past a capacity.  No workspace.
+ *   se3_stsdf_mesh_stack    the same two passes over the groups (block, x) in key order: offsets of (16 B + 1) int64.  The write pass
+ *                           needs vertex_plane, num_slots x 4096 ints of scratch (it need not be zeroed; as many bytes as the tsdf
+ *                           storage), and a vertex_capacity below 2^31.
+ *   se3_debug_tsdf_mesh_host / se3_debug_stsdf_mesh_host   the same text on HOST memory, serially, one volume / one directory.
+ *                           out_vertices NULL: the counts alone.  out_counts: vertices, triangles.  out_block_offsets (2, B + 1): the
+ *                           blocks' vertex offsets, then their triangle offsets.
+ *   se3_debug_mesh_table    the triangle table (256, SE3_MESH_TABLE_WIDTH) signed bytes, -1 terminated rows of cube edges, and (unless
+ *                           NULL) the 256 triangle counts, on the HOST. */
+enum se3_mesh_limit {              /* (NAMED) */
+  SE3_MESH_TABLE_WIDTH = 16,       /* entries of a row of the triangle table */
+  SE3_MESH_MAX_TRIANGLES = 5       /* triangles of one cube at most */
+};
+int se3_tsdf_mesh_stack(const float* tsdf, const float* weight, const float* color, int num_volumes, int resolution, double voxel_length,
+                        const double* origins, int64_t* vertex_offsets, int64_t* triangle_offsets, int64_t vertex_capacity,
+                        int64_t triangle_capacity, double* out_vertices, double* out_normals, double* out_colors, int64_t* out_triangles,
+                        void* stream);
+int se3_stsdf_mesh_stack(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* neighbors,
+                         int64_t num_blocks, double voxel_length, int64_t* vertex_offsets, int64_t* triangle_offsets,
+                         int64_t vertex_capacity, int64_t triangle_capacity, int* vertex_plane, double* out_vertices, double* out_normals,
+                         double* out_colors, int64_t* out_triangles, void* stream);
+int se3_debug_tsdf_mesh_host(const float* tsdf, const float* weight, const float* color, int resolution, double voxel_length,
+                             const double* origin, int64_t vertex_capacity, int64_t triangle_capacity, double* out_vertices,
+                             double* out_normals, double* out_colors, int64_t* out_triangles, int64_t* out_counts);
+int se3_debug_stsdf_mesh_host(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* slots,
+                              int64_t num_blocks, double voxel_length, int64_t vertex_capacity, int64_t triangle_capacity,
+                              double* out_vertices, double* out_normals, double* out_colors, int64_t* out_triangles,
+                              int64_t* out_block_offsets);
+int se3_debug_mesh_table(signed char* out_table, int* out_counts);
+
 #ifdef __cplusplus
 }
 #endif

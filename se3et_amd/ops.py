@@ -3251,6 +3251,67 @@ def stsdf_extract_stack(tsdf, weight, color, keys, neighbors, voxel_length, bloc
     return out[0], out[1], None if color is None else out[2], [cuts[v + 1] - cuts[v] for v in range(len(cuts) - 1)]
 
 
+# ---- triangle meshes from the TSDF volumes (csrc/tsdf_mesh.hip) -------------------------------------------------------------------------------------
+MESH_LIMITS = {name[len('SE3_MESH_'):].lower(): value for name, value in ENUMS['se3_mesh_limit'].items()}
+
+
+def _mesh_outputs(vertices, triangles, has_color, dev):
+    out = [torch.empty((vertices, 3), dtype=torch.float64, device=dev) for _ in range(3 if has_color else 2)]
+    return out, torch.empty((triangles, 3), dtype=torch.int64, device=dev)
+
+
+def tsdf_mesh_stack(tsdf, weight, color, voxel_length, origins):
+    """HIP (csrc/tsdf_mesh.hip): the triangle meshes of the volumes: a count pass, two scans, one host read of the volumes' counts, a write
+    pass; no workspace.  Returns (vertices (n, 3) float64, triangles (m, 3) int64, normals (n, 3) float64, colors (n, 3) float64 or None,
+    vertex_counts, triangle_counts: lists of V ints); volume v owns the next vertex_counts[v] vertices and triangle_counts[v] triangles,
+    and its triangles name its own vertices from 0."""
+    what = 'tsdf_mesh_stack'
+    t, w, color, V, R = _tsdf_state(tsdf, weight, color, what)
+    o = _req(origins, torch.float64, 'origins', 2)
+    if tuple(o.shape) != (V, 3) or o.device != t.device:
+        raise RuntimeError('%s: origins (V, 3) on %s expected' % (what, t.device))
+    dev = t.device
+    rows = torch.empty((2, V * R * R + 1), dtype=torch.int64, device=dev)
+    stream = _stream()
+    cptr = None if color is None else _dp(color)
+    args = (_dp(t), _dp(w), cptr, V, R, float(voxel_length), _dp(o), _dp(rows[0]), _dp(rows[1]))
+    check(lib().se3_tsdf_mesh_stack(*args, 0, 0, None, None, None, None, stream), 'se3_tsdf_mesh_stack')
+    vcuts, tcuts = rows[:, ::R * R].cpu().tolist()          # (the one host read: the volumes' offsets)
+    out, tri = _mesh_outputs(vcuts[-1], tcuts[-1], color is not None, dev)
+    if vcuts[-1]:
+        check(lib().se3_tsdf_mesh_stack(*args, vcuts[-1], tcuts[-1], _dp(out[0]), _dp(out[1]), None if color is None else _dp(out[2]), _dp(tri),
+                                        stream), 'se3_tsdf_mesh_stack')
+    return (out[0], tri, out[1], None if color is None else out[2], [vcuts[v + 1] - vcuts[v] for v in range(V)],
+            [tcuts[v + 1] - tcuts[v] for v in range(V)])
+
+
+def stsdf_mesh_stack(tsdf, weight, color, keys, neighbors, voxel_length, block_cuts):
+    """HIP (csrc/tsdf_mesh.hip): the triangle meshes of the blocks in key order, as tsdf_mesh_stack; the arguments of stsdf_extract_stack.
+    The write pass takes an int32 plane of S x 4096 entries (the blocks' first vertex numbers: as many bytes as the tsdf storage), which
+    lives for the call."""
+    what = 'stsdf_mesh_stack'
+    t, w, color = _stsdf_storage(tsdf, weight, color, what)
+    k, nb = _req(keys, torch.int64, 'keys', 1), _req(neighbors, torch.int32, 'neighbors', 2)
+    n = int(k.shape[0])
+    if tuple(nb.shape) != (n, 27) or k.device != t.device or nb.device != t.device:
+        raise RuntimeError('%s: keys (B,) and neighbors (B, 27) on %s expected' % (what, t.device))
+    dev = t.device
+    rows = torch.empty((2, n * STSDF_BLOCK + 1), dtype=torch.int64, device=dev)
+    stream = _stream()
+    cptr = None if color is None else _dp(color)
+    args = (_dp(t), _dp(w), cptr, _dp(k), _dp(nb), n, float(voxel_length), _dp(rows[0]), _dp(rows[1]))
+    check(lib().se3_stsdf_mesh_stack(*args, 0, 0, None, None, None, None, None, stream), 'se3_stsdf_mesh_stack')
+    vcuts, tcuts = rows[:, block_cuts * STSDF_BLOCK].cpu().tolist()          # (the one host read: the volumes' offsets)
+    out, tri = _mesh_outputs(vcuts[-1], tcuts[-1], color is not None, dev)
+    if vcuts[-1]:
+        plane = torch.empty((int(t.shape[0]) * STSDF_BLOCK ** 3,), dtype=torch.int32, device=dev)
+        check(lib().se3_stsdf_mesh_stack(*args, vcuts[-1], tcuts[-1], _dp(plane), _dp(out[0]), _dp(out[1]), None if color is None else _dp(out[2]),
+                                         _dp(tri), stream), 'se3_stsdf_mesh_stack')
+    V = len(vcuts) - 1
+    return (out[0], tri, out[1], None if color is None else out[2], [vcuts[v + 1] - vcuts[v] for v in range(V)],
+            [tcuts[v + 1] - tcuts[v] for v in range(V)])
+
+
 # ---- RGB-D odometry of frame pairs (csrc/rgbd_odometry.hip) -----------------------------------------------------------------------------------------
 RGBD_LIMITS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_limit'].items()}
 RGBD_STATUS = {name[len('SE3_RGBD_'):].lower(): value for name, value in ENUMS['se3_rgbd_status'].items()}

@@ -6,6 +6,7 @@ csrc/tsdf_core.h) in place of a host sweep of the volume per frame.
         .tsdf, .weight (V, R, R, R) float32 and, with color, .color (V, 3, R, R, R) float32: plain device tensors, zeros at the start
         .integrate(depths, intrinsics, extrinsics, frame_counts=None, colors=None, depth_scale=1000.0, depth_trunc=3.0)
         .extract_point_clouds()      three lists, one entry per volume: points, normals (n, 3) float64, colours (n, 3) float64 or None
+        .extract_triangle_meshes()   four lists: vertices (n, 3) float64, triangles (m, 3) int64, normals, colours or None
   fuse_depth_frames(depths_list, intrinsics, extrinsics_list, resolution, voxel_length, sdf_trunc, ...)
         construct, integrate and extract for a list of fragments: (points_list, normals_list, colors_list or None)
   depth_to_points_clouds(depths, intrinsics, scaling_factor=1000.0, distance_limit=6.0, convention='reference')
@@ -48,6 +49,16 @@ Contract: extraction.  All float64.  Output order is ascending (x, y, z, axis), 
      Open3D's quirk).  n is divided by sqrt((n_x^2 + n_y^2) + n_z^2) when that is positive and returned as it is otherwise.  The reads
      are inside the volume by construction: p_a / vl - 0.5 is in [1, R - 2], so g_a is in [0.01, R - 1.01] and floor(g_a) in [0, R - 2].
 
+Contract: triangle meshes (csrc/tsdf_mesh.hip carries the same text, and the rule of its triangle table).  All float64.
+  1. Cubes have their min corner (x, y, z) in [1, R - 3]^3, the range in which every cube edge satisfies the stencil argument of item 4
+     above.  A cube is taken iff all eight corner weights are != 0 (there is no 0.98 test); a corner is negative iff t < 0, so an exact
+     zero is positive; the cube index has bit i set iff corner i is negative, and indices 0 and 255 emit nothing.
+  2. A vertex exists for the edge (owning voxel, axis) iff the edge changes sign and at least one taken cube contains it, so every vertex is
+     referenced.  Its point, normal and colour are those of extraction items 3 and 4, bit for bit the row that extract_point_clouds emits
+     for the same edge where both exist.
+  3. Vertices are numbered in ascending (x, y, z, axis) of the owner; triangles come in ascending (x, y, z) of the cube, then in table
+     order, as int64 triples of the volume's own vertex numbers, wound so that the right-hand normal points to the positive side.
+
 Contract: depth images as clouds.  All float64, output in row-major pixel order.  z = raw / scaling_factor; z > distance_limit makes z = 0;
 x = ((u - cx) z) / fx, y = ((v - cy) z) / fy.
   'reference'   the reference function, quirks included: v = (row W + u) / W, a true quotient, so the row is fractional; a pixel is kept
@@ -57,7 +68,9 @@ x = ((u - cx) z) / fx, y = ((v - cy) z) / fy.
 Departures from Open3D.  The surface test of extraction item 2 is a sign test, not the float product f0 f1 < 0 (which underflows to 0 for
 two tiny values).  Colours are stored in [0, 1] (Open3D stores 0 .. 255 and divides on extraction).  Weights have no cap.  Depth is
 converted per gather, never as a float image; create_from_depth_image's float32 depth image is float64 arithmetic here.  With float32
-depth the reference convention divides in float64 (numpy would divide a float32 array in float32).
+depth the reference convention divides in float64 (numpy would divide a float32 array in float32).  The mesh leaves out the outer shell
+of cubes that Open3D walks, numbers its vertices by position where Open3D numbers them in the order of first use, and resolves an ambiguous
+cube face by separating the negative corners, which may not be Open3D's choice.
 
 Determinism.  Every voxel is independent and there are no atomics: a volume's state and clouds are bit-identical alone, anywhere in a
 batch, from run to run, and whether its frames arrive in one integrate call or split over several."""
@@ -210,15 +223,30 @@ class TSDFVolumes:
             colors += list(torch.split(c, counts)) if c is not None else [None] * (b - a)
         return points, normals, colors
 
+    @torch.no_grad()
+    def extract_triangle_meshes(self):
+        """(vertices_list, triangles_list, normals_list, colors_list): per volume (n, 3) float64 vertices, normals and colours (None without
+        colour) and (m, 3) int64 triangles that index the volume's own vertices, on the device.  The host reads the volumes' counts,
+        nothing else."""
+        vertices, triangles, normals, colors = [], [], [], []
+        for a, b in chunks(self.num_volumes):
+            v, t, n, c, nv, nt = _ops.tsdf_mesh_stack(self.tsdf[a:b], self.weight[a:b], None if self.color is None else self.color[a:b],
+                                                      self.voxel_length, self.origins[a:b])
+            vertices += list(torch.split(v, nv))
+            triangles += list(torch.split(t, nt))
+            normals += list(torch.split(n, nv))
+            colors += list(torch.split(c, nv)) if c is not None else [None] * (b - a)
+        return vertices, triangles, normals, colors
+
 
 @torch.no_grad()
 def fuse_depth_frames(depths_list, intrinsics, extrinsics_list, resolution, voxel_length, sdf_trunc, origins=None, colors_list=None,
-                      depth_scale=1000.0, depth_trunc=3.0, device=None):
+                      depth_scale=1000.0, depth_trunc=3.0, device=None, mesh=False):
     """One TSDF volume per fragment: construct, integrate and extract in one call.  depths_list: per fragment (F_i, H, W) uint16 or float32
     on the device, all of one image size and dtype; extrinsics_list: per fragment (F_i, 4, 4) world to camera; intrinsics: (4,) for all
     frames or a list of (4,) / (F_i, 4) per fragment; colors_list: per fragment (F_i, H, W, 3), or None.  Returns (points_list,
     normals_list, colors_list or None): (n, 3) float64 tensors on the device, what voxel_downsample_clouds and global_registration_pairs
-    take."""
+    take.  mesh=True: (vertices_list, triangles_list, normals_list, colors_list or None) of extract_triangle_meshes instead."""
     what = 'fuse_depth_frames'
     V = len(depths_list)
     if len(extrinsics_list) != V or (colors_list is not None and len(colors_list) != V):
@@ -234,6 +262,9 @@ def fuse_depth_frames(depths_list, intrinsics, extrinsics_list, resolution, voxe
         E = torch.cat([transforms_of(e, n, what, dev) for e, n in zip(extrinsics_list, counts)], 0)
         volumes.integrate(_join(what, depths_list), K, E, counts, None if colors_list is None else _join(what, colors_list),
                           depth_scale, depth_trunc)
+    if mesh:
+        vertices, triangles, normals, colors = volumes.extract_triangle_meshes()
+        return vertices, triangles, normals, colors if colors_list is not None else None
     points, normals, colors = volumes.extract_point_clouds()
     return points, normals, colors if colors_list is not None else None
 

@@ -7,6 +7,7 @@ csrc/tsdf_core.h, the text of the uniform volumes of se3et_amd/tsdf.py).  Blocks
         .num_blocks, .block_coords (B, 4) int64 (volume, bx, by, bz) in key order
         .state()                     tsdf, weight (B, 16, 16, 16) and color (B, 3, 16, 16, 16) or None, in the same order (copies)
         .extract_point_clouds()      three lists, one entry per volume, as TSDFVolumes.extract_point_clouds
+        .extract_triangle_meshes()   four lists, one entry per volume, as TSDFVolumes.extract_triangle_meshes
         .allocate_blocks(coords)     blocks by hand, zeros; .tsdf, .weight, .color are the storage, block i of the directory at .slots[i]
   fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_length, sdf_trunc, colors_list=None, stride=4, ...)
         construct, integrate and extract for a list of scenes: (points_list, normals_list, colors_list or None)
@@ -49,6 +50,12 @@ Contract C: extraction.  Float64.
   5. T(q) has g_a = q_a / vl - 0.5 in [-0.99, 16.99], so floor(g_a) is in [-1, 16] and the far corner of the stencil is at most 17: every
      read falls in the block or one of its 26 neighbours.
   6. A corner in an absent block reads 0, like an unobserved voxel.
+
+Contract D: triangle meshes (csrc/tsdf_mesh.hip; the uniform contract of se3et_amd/tsdf.py without its border).  Every cube is taken whose
+min corner lies in an allocated block and whose eight corners, read through the block's 27 neighbours, have a weight != 0; a corner in an
+absent block has weight 0.  A vertex exists for an edge that changes sign inside at least one taken cube; its values are those of contract
+C, items 4 to 6.  Vertices are ordered by (block in key order, x, y, z, axis), triangles by (block, x, y, z, table order); a triangle names
+the vertices of its own volume.  The write pass takes an int32 plane of 4096 entries a slot, as many bytes as the tsdf storage.
 
 Departures from Open3D.  Open3D allocates through a hash map, so the order of its units follows the order of insertion; here the order is
 the key order, and the order in which a call's records are deduplicated is irrelevant.  Allocation and integration share one depth rule
@@ -250,12 +257,30 @@ class SparseTSDFVolumes:
         p, n, c, counts = _ops.stsdf_extract_stack(self.tsdf, self.weight, self.color, self.keys, self._neighbors, self.voxel_length, cuts)
         return list(torch.split(p, counts)), list(torch.split(n, counts)), list(torch.split(c, counts)) if c is not None else [None] * V
 
+    @torch.no_grad()
+    def extract_triangle_meshes(self):
+        """(vertices_list, triangles_list, normals_list, colors_list): per volume (n, 3) float64 vertices, normals and colours (None without
+        colour) and (m, 3) int64 triangles that index the volume's own vertices, on the device (contract D).  The host reads the volumes'
+        counts, nothing else."""
+        V, dev = self.num_volumes, self.device
+        if self.num_blocks == 0:
+            empty = [torch.zeros((0, 3), dtype=torch.float64, device=dev) for _ in range(V)]
+            return (empty, [torch.zeros((0, 3), dtype=torch.int64, device=dev) for _ in range(V)], [e.clone() for e in empty],
+                    [e.clone() if self.has_color else None for e in empty])
+        if self._neighbors is None:
+            self._neighbors = _ops.stsdf_neighbors(self.keys, self.slots)
+        cuts = torch.searchsorted(self.keys, to_device([v << (3 * _BITS) for v in range(V + 1)], torch.int64, dev))
+        v, t, n, c, nv, nt = _ops.stsdf_mesh_stack(self.tsdf, self.weight, self.color, self.keys, self._neighbors, self.voxel_length, cuts)
+        return (list(torch.split(v, nv)), list(torch.split(t, nt)), list(torch.split(n, nv)),
+                list(torch.split(c, nv)) if c is not None else [None] * V)
+
 
 @torch.no_grad()
 def fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_length, sdf_trunc, colors_list=None, stride=4, depth_scale=1000.0,
-                             depth_trunc=3.0, device=None):
+                             depth_trunc=3.0, device=None, mesh=False):
     """One sparse volume per scene: construct, integrate and extract in one call; the lists of fuse_depth_frames without a resolution or
-    origins.  Returns (points_list, normals_list, colors_list or None)."""
+    origins.  Returns (points_list, normals_list, colors_list or None); mesh=True: (vertices_list, triangles_list, normals_list,
+    colors_list or None) of extract_triangle_meshes instead."""
     what = 'fuse_depth_frames_sparse'
     V = len(depths_list)
     if len(extrinsics_list) != V or (colors_list is not None and len(colors_list) != V):
@@ -271,18 +296,22 @@ def fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_len
         E = torch.cat([transforms_of(e, n, what, dev) for e, n in zip(extrinsics_list, counts)], 0)
         volumes.integrate(_join(what, depths_list), K, E, counts, None if colors_list is None else _join(what, colors_list), depth_scale,
                           depth_trunc)
+    if mesh:
+        vertices, triangles, normals, colors = volumes.extract_triangle_meshes()
+        return vertices, triangles, normals, colors if colors_list is not None else None
     points, normals, colors = volumes.extract_point_clouds()
     return points, normals, colors if colors_list is not None else None
 
 
 @torch.no_grad()
 def integrate_scene_rgbd(depths_list, colors_list, intrinsics, frame_poses, fragment_poses, voxel_length, sdf_trunc, stride=4, depth_scale=1000.0,
-                         depth_trunc=3.0, device=None):
+                         depth_trunc=3.0, device=None, mesh=False):
     """Open3D's integrate_scene.py: frame i of fragment g has the camera-to-world pose fragment_poses[g] @ frame_poses[g][i] and is
     integrated under its rigid inverse, computed on the device; all frames go into one scene volume.  depths_list, colors_list: per
     fragment (F_g, H, W) and (F_g, H, W, 3) on the device (colors_list None: no colour); frame_poses: per fragment (F_g, 4, 4), what
     make_fragments_rgbd returns as 'poses'; fragment_poses: (G, 4, 4), what multiway_registration returns as 'poses'; intrinsics (4,) or
-    (sum F_g, 4).  Returns (points, normals, colors or None, volume): (n, 3) float64 on the device and the SparseTSDFVolumes."""
+    (sum F_g, 4).  Returns (points, normals, colors or None, volume): (n, 3) float64 on the device and the SparseTSDFVolumes.  mesh=True:
+    (vertices, triangles, normals, colors or None, volume), the scene as a triangle mesh (extract_triangle_meshes)."""
     what = 'integrate_scene_rgbd'
     G = len(depths_list)
     if len(frame_poses) != G or (colors_list is not None and len(colors_list) != G):
@@ -295,5 +324,8 @@ def integrate_scene_rgbd(depths_list, colors_list, intrinsics, frame_poses, frag
         world = torch.cat([fragment[g:g + 1] @ transforms_of(frame_poses[g], n, what, dev, finite=True) for g, n in enumerate(counts)], 0)
         volume.integrate(_join(what, depths_list), intrinsics, rigid_inverse(world), None, None if colors_list is None else _join(what, colors_list),
                          depth_scale, depth_trunc)
+    if mesh:
+        vertices, triangles, normals, colors = volume.extract_triangle_meshes()
+        return vertices[0], triangles[0], normals[0], colors[0] if colors_list is not None else None, volume
     points, normals, colors = volume.extract_point_clouds()
     return points[0], normals[0], colors[0] if colors_list is not None else None, volume
