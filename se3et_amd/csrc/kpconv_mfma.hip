@@ -196,30 +196,51 @@ __global__ __launch_bounds__(64 * NCW * KS) void kpconv_mfma_kernel(const u32x4*
 
 // ---- stage 1: neighbour table ------------------------------------------------------------------------------------------------------------
 // Per query point the VALID neighbours compacted to the front (invalid ones carry weight 0 in the reference: blocks_epn.py:471,377 shadow
-// point / zero feature row), padded with (index 0, weights 0) up to a multiple of 32 entries (NNp):
+// point / zero feature row), repeats of a row folded into its first occurrence, padded with (the first neighbour's row -- row 0 for a point
+// without neighbours --, weights 0) up to NNp entries:
 //   hwt  [P][16][NNp] f32   orbit weights hw[o][n] = sum_{k in orbit o} max(0, 1 - |s_n - q - kp_k| / sigma)   (blocks_epn.py:520-533), orbit-major:
 //                           a lane's 8 neighbours of one orbit are one 32-byte run
 //   nbr  [P][NNp] int32     support row of the j-th valid neighbour
-//   cnt  [P] int32          valid neighbours
+//   cnt  [P] int32          valid neighbours (distinct rows)
 __global__ __launch_bounds__(64) void kpconv_neighbor_table_kernel(const float* __restrict__ q_pts, const float* __restrict__ s_pts,
                                                                    const int64_t* __restrict__ idx, int64_t Ns, int NN, int NNp,
                                                                    const float* __restrict__ kp, float inv_sigma, float* __restrict__ hwt,
                                                                    int* __restrict__ nbr, int* __restrict__ cnt) {
-  __shared__ int order[64];
+  __shared__ int order[64], mult[64];
   const int64_t p = blockIdx.x;
   const int n = threadIdx.x;
   const int64_t j = n < NN ? idx[p * NN + n] : -1;
   const bool valid = j >= 0 && j < Ns;
-  const unsigned long long m = __ballot(valid);
+  // A row that the list names several times counts as often as it appears (the reference gathers it once per entry): the repeats are folded
+  // into the FIRST occurrence, whose weights -- the same row, the same weights -- are multiplied by the multiplicity, so that every consumer
+  // sees lists without repeats (the union plan gives equal rows of one list one union index: csrc/kpconv_union.hip).  Multiplicity 1
+  // multiplies by 1.f: tables without repeats are bit-identical.
+  const int jv = valid ? (int)j : -1;                                     // (valid rows are below 2^31: num_support * 6 * Cin is)
+  int same = 0;
+  bool first = true;
+  for (int i = 0; i < NN; i++) {
+    const bool eq = __shfl(jv, i) == jv;
+    same += eq ? 1 : 0;
+    first = first && !(eq && i < n);
+  }
+  const bool keep = valid && first;
+  const unsigned long long m = __ballot(keep);
   const int nv = __popcll(m);
-  if (valid) order[__popcll(m & ((1ull << n) - 1ull))] = n;
+  if (keep) {
+    const int at = __popcll(m & ((1ull << n) - 1ull));
+    order[at] = n;
+    mult[at] = same;
+  }
   __syncthreads();
   if (n == 0) cnt[p] = nv;
+  // the padding slots (weights 0) name the point's own first neighbour, never a row that no list names: 0 x (a huge or non-finite row 0)
+  // must not reach a point
+  const int pad_row = nv > 0 ? (int)idx[p * NN + order[0]] : 0;
   for (int e = n; e < NNp; e += 64) {
     float hw[kOrbits];
 #pragma unroll
     for (int o = 0; o < kOrbits; o++) hw[o] = 0.f;
-    int row = 0;
+    int row = pad_row;
     if (e < nv) {
       const int64_t js = idx[p * NN + order[e]];
       row = (int)js;
@@ -236,6 +257,9 @@ __global__ __launch_bounds__(64) void kpconv_neighbor_table_kernel(const float* 
 #pragma unroll
         for (int k = 0; k < kK; k++)
           if ((kOrb.mask[o] >> k) & 1) hw[o] += w[k];
+      const float times = (float)mult[e];
+#pragma unroll
+      for (int o = 0; o < kOrbits; o++) hw[o] *= times;
     }
     nbr[p * NNp + e] = row;
 #pragma unroll

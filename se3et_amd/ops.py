@@ -1190,6 +1190,17 @@ def _kpconv_union_plan(tab, q_pts, s_pts, idx, order, G, P, NN, stream):
     return _union_plans.store((q_pts, s_pts, idx, order), stream.value, plan)
 
 
+def _listed_amax(x, idx, Ns):
+    """The largest |x| among the support rows that some neighbour list names, as a one-element device tensor (no host sync): the magnitude
+    word of a plain input.  A row that no list names stays out -- the kernels never multiply it, and its size must not take the split's
+    range away from the rows they do."""
+    with torch.no_grad():
+        rows = torch.linalg.vector_norm(x.detach().reshape(Ns, -1), float('inf'), dim=1)
+        unlisted = torch.ones((Ns + 2,), dtype=torch.bool, device=x.device)          # [below the range | rows | the shadow and beyond]
+        unlisted[(idx.reshape(-1) + 1).clamp_(0, Ns + 1)] = False
+        return rows.masked_fill_(unlisted[1:Ns + 1], 0.0).amax().reshape(1)
+
+
 def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, sigma):
     """Fused matrix-core kernel (csrc/kpconv_mfma.hip) for channel counts that are multiples of (8, 32); otherwise the HIP gather of
     the slot-summed neighbourhood features (csrc/kpconv_so3.hip) + one library GEMM with the (36 Cin, Cout) weight matrix.
@@ -1224,6 +1235,10 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
         # neighbour table (valid neighbours + 16 orbit weights each), then ONE kernel in which producer waves form the f16 hi / lo orbit sums
         # of a 16-point tile on the f32 matrix cores into LDS and consumer waves multiply them on the f16 matrix cores (csrc/kpconv_mfma.hip)
         tab = _kpconv_neighbor_table(q_pts, s_pts, idx, kernel_points, sigma, P, Ns, NN, stream)
+        if not blocked and x_amax is None and path != 'sums' and P > 0 and Ns > 0:
+            # a plain tensor (every call under autograd, a user's tensor through the drop-in modules) carries no magnitude word: the one the
+            # kernels scale by before their f16 split (kpsum::x_split_scale) is formed here; the blocked input keeps the word of its apply pass
+            x_amax = _listed_amax(x, idx, Ns)
         if path == 'sums':
             # two launches: the orbit sums as tile images in HBM, then the contraction (kept for A/B runs)
             Hs = torch.empty((lib().se3_kpconv_sums_bytes(P, Cin),), dtype=torch.uint8, device=x.device)
@@ -1260,9 +1275,13 @@ def kpconv_inter_so3(x, q_pts, s_pts, idx, kernel_points, weights, kidx, ridx, s
                                       kt.data_ptr(), rt.data_ptr(), float(sigma), P, Ns, NN, Cin, G.data_ptr(), _stream()),
           'se3_kpconv_so3_gather')
     Kg = 36 * Cin
-    if not torch.is_grad_enabled() and Kg % 4 == 0 and Kg <= 1024:
+    if not torch.is_grad_enabled() and Kg % 4 == 0 and Kg <= 64:
         # (the first layer of the backbone, Cin = 1: K = 36.)  The streaming kernel multiplies K rounded up to 32 wide: the rows of G are read
         # past their end into the next row (finite values) against weight columns that are zero; the last row reads zeros (buffer bounds).
+        # Only the first layer: the kernel takes a row's f16-split scale from its FIRST 32 values (csrc/dense_norm.hip) and clamps later values
+        # more than 2^8 times those.  The first 32 slot sums of a wider layer (Kg up to 1024 came here before) belong to at most four of
+        # the 36 weight slots: a point with one or two neighbours has them at or next to zero beside live later slots, and its rows came out
+        # clamped (tests/test_gpu_kpconv_edges.py, count ladder: up to 0.2 of the tensor's maximum).  Wider layers take the library GEMM.
         Kp = (Kg + 31) // 32 * 32
         Wt = _padded_transposed_weight(weights, Kg, Kp, Cout)
         out = torch.empty((P * 6, Cout), dtype=torch.float32, device=x.device)

@@ -1260,7 +1260,7 @@ def test_fused_kpconv_edge_shapes(P, Ns, NN, Cin, Cout, box):
 def test_union_kpconv_edge_shapes(P, Ns, NN, Cin, Cout, box, clouds):
     """The union-staged fused kernel (csrc/kpconv_union.hip) at the corners of the per-lane-gather kernel's test: tables wider than 32, odd chunk
     counts, K-split consumers, point counts that are no multiple of the 16-point group, 64 neighbours -- plus what is its own: several
-    clouds (every cloud starts a new group: padding positions), groups whose distinct rows exceed the 160-row cap (dense boxes: several
+    clouds (every cloud starts a new group: padding positions), groups whose distinct rows exceed the 128-row cap kUCap (dense boxes: several
     passes per group), the chunked row layout, the channel split, bit-identical repeats.  Against the float64 formula and the f32 path."""
     from se3et_amd import functional as SF
     from se3et_amd import ops
