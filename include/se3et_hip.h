@@ -1612,6 +1612,41 @@ int se3_debug_stsdf_mesh_host(const float* tsdf, const float* weight, const floa
                               int64_t* out_block_offsets);
 int se3_debug_mesh_table(signed char* out_table, int* out_counts);
 
+/* ---- ray casting of the TSDF volumes (csrc/tsdf_raycast.hip, csrc/tsdf_raycast_core.h) -------------------------------------------------------------
+ * Open3D's VoxelBlockGrid.ray_cast for the uniform and the block-sparse volumes above, up to SE3_PAIR_MAX_PAIRS volumes per call: one ray per
+ * pixel, no atomics, nothing read back; the contract is the header comment of csrc/tsdf_raycast.hip.  The state is that of
+ * se3_tsdf_extract_stack / of the sparse directory (keys ascending with their slots; num_slots: the slots of the storage).  Everything on
+ * the DEVICE unless it is called _host.
+ *   se3_tsdf_raycast_stack / se3_stsdf_raycast_stack   views (F, SE3_RAYCAST_VIEW_WORDS) float64: the 3 x 4 camera-to-world pose by rows,
+ *                           then fx, fy, cx, cy; view_volumes (F) ints: the volume each view looks at (a value outside [0, num_volumes)
+ *                           renders no hit).  Outputs, each NULL or whole: out_depth (F, H, W) float32, out_points and out_normals
+ *                           (F, H, W, 3) float64, out_colors (F, H, W, 3) float32 (only with color), out_mask (F, H, W) bytes.  Every
+ *                           pixel of every map given is written: a pixel without a hit holds 0, NaN, NaN, 0, 0.  No workspace.
+ *   se3_debug_tsdf_raycast_host / se3_debug_stsdf_raycast_host   the same text on HOST memory, serially, the views of one volume. */
+enum se3_raycast_limit {           /* (NAMED) */
+  SE3_RAYCAST_VIEW_WORDS = 16,     /* float64 words of a view's row of the table: SE3_STSDF_POSE_WORDS */
+  SE3_RAYCAST_TILE = 16,           /* a workgroup casts a tile of this many pixels squared */
+  SE3_RAYCAST_MAX_STEPS = 1048576  /* (depth_max - depth_min) / voxel_length at most */
+};
+int se3_tsdf_raycast_stack(const float* tsdf, const float* weight, const float* color, int num_volumes, int resolution, double voxel_length,
+                           double sdf_trunc, const double* origins, const double* views, const int* view_volumes, int64_t num_views,
+                           int height, int width, double depth_min, double depth_max, double weight_threshold, float* out_depth,
+                           double* out_points, double* out_normals, float* out_colors, uint8_t* out_mask, void* stream);
+int se3_stsdf_raycast_stack(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* slots,
+                            int64_t num_blocks, int64_t num_slots, int num_volumes, double voxel_length, double sdf_trunc,
+                            const double* views, const int* view_volumes, int64_t num_views, int height, int width, double depth_min,
+                            double depth_max, double weight_threshold, float* out_depth, double* out_points, double* out_normals,
+                            float* out_colors, uint8_t* out_mask, void* stream);
+int se3_debug_tsdf_raycast_host(const float* tsdf, const float* weight, const float* color, int resolution, double voxel_length,
+                                double sdf_trunc, const double* origin, const double* views, int64_t num_views, int height, int width,
+                                double depth_min, double depth_max, double weight_threshold, float* out_depth, double* out_points,
+                                double* out_normals, float* out_colors, uint8_t* out_mask);
+int se3_debug_stsdf_raycast_host(const float* tsdf, const float* weight, const float* color, const int64_t* keys, const int* slots,
+                                 int64_t num_blocks, int64_t num_slots, int volume, double voxel_length, double sdf_trunc,
+                                 const double* views, int64_t num_views, int height, int width, double depth_min, double depth_max,
+                                 double weight_threshold, float* out_depth, double* out_points, double* out_normals, float* out_colors,
+                                 uint8_t* out_mask);
+
 #ifdef __cplusplus
 }
 #endif

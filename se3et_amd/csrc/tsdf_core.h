@@ -125,6 +125,27 @@ PG_HD int ts_edges(const TsVolume& V, int x, int y, int z) {
   return mask;
 }
 
+// one axis of T's cell at q: g = q / vl - 0.5, fl = floor(g) (kept as float64: the caller knows its range), r = g - fl, s = 1 - r
+PG_HD void ts_cell(double vl, double q, double* fl, double* r, double* s) {
+#pragma clang fp contract(off)
+  const double g = q / vl - 0.5;
+  *fl = floor(g), *r = g - *fl, *s = 1.0 - *r;
+}
+// T's sum over the eight corner values f[dx][dy][dz], z innermost, every product and sum rounded on its own
+PG_HD double ts_mix(const double* r, const double* s, float f000, float f001, float f010, float f011, float f100, float f101, float f110,
+                    float f111) {
+#pragma clang fp contract(off)
+  const double a00 = s[2] * (double)f000, b00 = r[2] * (double)f001;
+  const double a01 = s[2] * (double)f010, b01 = r[2] * (double)f011;
+  const double a10 = s[2] * (double)f100, b10 = r[2] * (double)f101;
+  const double a11 = s[2] * (double)f110, b11 = r[2] * (double)f111;
+  const double z00 = a00 + b00, z01 = a01 + b01, z10 = a10 + b10, z11 = a11 + b11;
+  const double c0 = s[1] * z00, d0 = r[1] * z01, c1 = s[1] * z10, d1 = r[1] * z11;
+  const double y0 = c0 + d0, y1 = c1 + d1;
+  const double e0 = s[0] * y0, e1 = r[0] * y1;
+  return e0 + e1;
+}
+
 // T(q): the trilinear interpolation of the stored tsdf at g = q / vl - 0.5, z innermost.  The eight reads lie inside the volume for every
 // q that ts_emit asks for (the argument is with the contract, item 4 of the extraction).
 PG_HD double ts_trilinear(const TsVolume& V, const double* q) {
@@ -132,22 +153,38 @@ PG_HD double ts_trilinear(const TsVolume& V, const double* q) {
   int i[3];
   double r[3], s[3];
   for (int a = 0; a < 3; a++) {
-    const double g = q[a] / V.vl - 0.5;
-    const double fl = floor(g);
-    i[a] = (int)fl, r[a] = g - fl, s[a] = 1.0 - r[a];
+    double fl;
+    ts_cell(V.vl, q[a], &fl, &r[a], &s[a]);
+    i[a] = (int)fl;
   }
   const float* f = V.tsdf + ts_index(V.R, i[0], i[1], i[2]);
   const int64_t sx = (int64_t)V.R * V.R, sy = V.R;
-  const double a00 = s[2] * (double)f[0], b00 = r[2] * (double)f[1];
-  const double a01 = s[2] * (double)f[sy], b01 = r[2] * (double)f[sy + 1];
-  const double a10 = s[2] * (double)f[sx], b10 = r[2] * (double)f[sx + 1];
-  const double a11 = s[2] * (double)f[sx + sy], b11 = r[2] * (double)f[sx + sy + 1];
-  const double z00 = a00 + b00, z01 = a01 + b01, z10 = a10 + b10, z11 = a11 + b11;
-  const double c0 = s[1] * z00, d0 = r[1] * z01, c1 = s[1] * z10, d1 = r[1] * z11;
-  const double y0 = c0 + d0, y1 = c1 + d1;
-  const double e0 = s[0] * y0, e1 = r[0] * y1;
-  return e0 + e1;
+  return ts_mix(r, s, f[0], f[1], f[sy], f[sy + 1], f[sx], f[sx + 1], f[sx + sy], f[sx + sy + 1]);
 }
+
+// item 4 of the extraction at p (without the origin) for any field T: n_a = T(p + h e_a) - T(p - h e_a), h = 0.99 vl, divided by its
+// length when that is positive.  ts_emit and the ray casting of csrc/tsdf_raycast_core.h share it.
+template <class Field>
+PG_HD void ts_gradient(const Field& T, double vl, const double* p, double* normal) {
+#pragma clang fp contract(off)
+  const double h = 0.99 * vl;
+  double n[3];
+  for (int a = 0; a < 3; a++) {
+    double hi[3] = {p[0], p[1], p[2]}, lo[3] = {p[0], p[1], p[2]};
+    hi[a] = p[a] + h, lo[a] = p[a] - h;
+    const double th = T(hi), tl = T(lo);
+    n[a] = th - tl;
+  }
+  const double xx = n[0] * n[0], yy = n[1] * n[1], zz = n[2] * n[2];
+  const double xy = xx + yy;
+  const double len = pg_sqrt(xy + zz);
+  const bool unit = len > 0.0;
+  for (int a = 0; a < 3; a++) normal[a] = unit ? n[a] / len : n[a];
+}
+struct TsField {
+  const TsVolume& V;
+  PG_HD double operator()(const double* q) const { return ts_trilinear(V, q); }
+};
 
 // items 3 and 4 for the edge of voxel (x, y, z) along `axis`: the point (origin added), its normal and, where V.color, its colour
 PG_HD void ts_emit(const TsVolume& V, int x, int y, int z, int axis, double* point, double* normal, double* color) {
@@ -171,19 +208,7 @@ PG_HD void ts_emit(const TsVolume& V, int x, int y, int z, int axis, double* poi
       const double k0 = (double)V.color[k * cube + at] * r1, k1 = (double)V.color[k * cube + at + step] * r0;
       color[k] = (k0 + k1) / sum;
     }
-  const double h = 0.99 * V.vl;
-  double n[3];
-  for (int a = 0; a < 3; a++) {
-    double hi[3] = {p[0], p[1], p[2]}, lo[3] = {p[0], p[1], p[2]};
-    hi[a] = p[a] + h, lo[a] = p[a] - h;
-    const double th = ts_trilinear(V, hi), tl = ts_trilinear(V, lo);
-    n[a] = th - tl;
-  }
-  const double xx = n[0] * n[0], yy = n[1] * n[1], zz = n[2] * n[2];
-  const double xy = xx + yy;
-  const double len = pg_sqrt(xy + zz);
-  const bool unit = len > 0.0;
-  for (int a = 0; a < 3; a++) normal[a] = unit ? n[a] / len : n[a];
+  ts_gradient(TsField{V}, V.vl, p, normal);
 }
 
 // ---- depth images as clouds ----------------------------------------------------------------------------------------------------------------

@@ -3398,3 +3398,60 @@ def _rgbd_images(depths, colors, what):
         raise RuntimeError('%s: colors must be %s or %s on %s, got %s on %s' % (what, tuple(d.shape) + (3,), tuple(d.shape), d.device, tuple(c.shape),
                                                                               c.device))
     return d, _DEPTH_ELEM[d.dtype], c, _COLOR_ELEM[c.dtype]
+
+
+# ---- ray casting of the TSDF volumes (csrc/tsdf_raycast.hip) -------------------------------------------------------------------------------------------
+RAYCAST_LIMITS = {name[len('SE3_RAYCAST_'):].lower(): value for name, value in ENUMS['se3_raycast_limit'].items()}
+RAYCAST_MAPS = {'depth': (torch.float32, ()), 'points': (torch.float64, (3,)), 'normals': (torch.float64, (3,)), 'color': (torch.float32, (3,)),
+                'mask': (torch.bool, ())}
+
+
+def raycast_outputs(maps, F, H, W, dev):
+    """The maps of a call, uninitialised: the kernels write every pixel of every map."""
+    return {name: torch.empty((F, H, W) + RAYCAST_MAPS[name][1], dtype=RAYCAST_MAPS[name][0], device=dev) for name in maps}
+
+
+def _raycast_views(views, view_volumes, out, height, width, dev, what):
+    v, vv = _req(views, torch.float64, 'views', 2), _req(view_volumes, torch.int32, 'view_volumes', 1)
+    F, H, W = int(v.shape[0]), int(height), int(width)
+    if tuple(v.shape) != (F, RAYCAST_LIMITS['view_words']) or vv.shape[0] != F or v.device != dev or vv.device != dev:
+        raise RuntimeError('%s: views (F, %d) float64 and view_volumes (F,) int32 on %s expected' % (what, RAYCAST_LIMITS['view_words'], dev))
+    ptrs = []
+    for name, (dtype, tail) in RAYCAST_MAPS.items():
+        t = out.get(name)
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (F, H, W) + tail or t.device != dev or not t.is_contiguous()):
+            raise RuntimeError('%s: map %r must be %s %s on %s, contiguous' % (what, name, (F, H, W) + tail, dtype, dev))
+        ptrs.append(None if t is None else _dp(t))
+    if set(out) - set(RAYCAST_MAPS):
+        raise RuntimeError('%s: maps %s are not among %s' % (what, sorted(set(out) - set(RAYCAST_MAPS)), ', '.join(RAYCAST_MAPS)))
+    return v, vv, F, H, W, ptrs
+
+
+def tsdf_raycast_stack(tsdf, weight, color, voxel_length, sdf_trunc, origins, views, view_volumes, out, height, width, depth_min=0.1, depth_max=3.0,
+                       weight_threshold=1.0):
+    """HIP (csrc/tsdf_raycast.hip): the views ray-cast into the maps of `out`, in place, one launch, nothing read back.  The state of
+    tsdf_extract_stack; views (F, RAYCAST_LIMITS['view_words']) float64: the 3 x 4 camera pose by rows, then fx, fy, cx, cy; view_volumes
+    (F,) int32 on the device: the volume of each view; out: raycast_outputs of any of RAYCAST_MAPS ('color' only with color)."""
+    what = 'tsdf_raycast_stack'
+    t, w, color, V, R = _tsdf_state(tsdf, weight, color, what)
+    o = _req(origins, torch.float64, 'origins', 2)
+    if tuple(o.shape) != (V, 3) or o.device != t.device:
+        raise RuntimeError('%s: origins (V, 3) on %s expected' % (what, t.device))
+    v, vv, F, H, W, ptrs = _raycast_views(views, view_volumes, out, height, width, t.device, what)
+    check(lib().se3_tsdf_raycast_stack(_dp(t), _dp(w), None if color is None else _dp(color), V, R, float(voxel_length), float(sdf_trunc), _dp(o),
+                                       _dp(v), _dp(vv), F, H, W, float(depth_min), float(depth_max), float(weight_threshold), *ptrs, _stream()),
+          'se3_tsdf_raycast_stack')
+    return out
+
+
+def stsdf_raycast_stack(tsdf, weight, color, keys, slots, num_volumes, voxel_length, sdf_trunc, views, view_volumes, out, height, width,
+                        depth_min=0.1, depth_max=3.0, weight_threshold=1.0):
+    """HIP (csrc/tsdf_raycast.hip): tsdf_raycast_stack for the block-sparse volumes: the storage with its directory (keys ascending, slots)."""
+    what = 'stsdf_raycast_stack'
+    t, w, color = _stsdf_storage(tsdf, weight, color, what)
+    k, s = _stsdf_directory(keys, slots, what, t.device)
+    v, vv, F, H, W, ptrs = _raycast_views(views, view_volumes, out, height, width, t.device, what)
+    check(lib().se3_stsdf_raycast_stack(_dp(t), _dp(w), None if color is None else _dp(color), _dp(k), _dp(s), int(k.shape[0]), int(t.shape[0]),
+                                        int(num_volumes), float(voxel_length), float(sdf_trunc), _dp(v), _dp(vv), F, H, W, float(depth_min),
+                                        float(depth_max), float(weight_threshold), *ptrs, _stream()), 'se3_stsdf_raycast_stack')
+    return out

@@ -7,6 +7,8 @@ csrc/tsdf_core.h) in place of a host sweep of the volume per frame.
         .integrate(depths, intrinsics, extrinsics, frame_counts=None, colors=None, depth_scale=1000.0, depth_trunc=3.0)
         .extract_point_clouds()      three lists, one entry per volume: points, normals (n, 3) float64, colours (n, 3) float64 or None
         .extract_triangle_meshes()   four lists: vertices (n, 3) float64, triangles (m, 3) int64, normals, colours or None
+        .ray_cast(intrinsics, extrinsics, height, width, frame_counts=None, depth_min=0.1, depth_max=3.0, weight_threshold=1.0,
+                  maps=('depth', 'color'))     a dict of device tensors: the model seen from F cameras (contract: ray casting)
   fuse_depth_frames(depths_list, intrinsics, extrinsics_list, resolution, voxel_length, sdf_trunc, ...)
         construct, integrate and extract for a list of fragments: (points_list, normals_list, colors_list or None)
   depth_to_points_clouds(depths, intrinsics, scaling_factor=1000.0, distance_limit=6.0, convention='reference')
@@ -59,6 +61,37 @@ Contract: triangle meshes (csrc/tsdf_mesh.hip carries the same text, and the rul
   3. Vertices are numbered in ascending (x, y, z, axis) of the owner; triangles come in ascending (x, y, z) of the cube, then in table
      order, as int64 triples of the volume's own vertex numbers, wound so that the right-hand normal points to the positive side.
 
+Contract: ray casting (csrc/tsdf_raycast.hip carries the same text; SparseTSDFVolumes.ray_cast follows it with its own item 3).  All float64,
+every operation rounded on its own, unless said otherwise.  A view has an extrinsic E (world to camera), its inverse P computed on the
+host in float64 (tsdf_sparse.camera_poses) and intrinsics (fx, fy, cx, cy).
+  1. Ray.  For pixel (u, v): xr = (u - cx) / fx, yr = (v - cy) / fy, dir_a = (P[a][0] xr + P[a][1] yr) + P[a][2], e_a = P[a][3] - o_a,
+     q_a(s) = e_a + s dir_a: s is camera depth.  m = sqrt((xr xr + yr yr) + 1) turns a Euclidean step into a step of s.
+  2. Interval.  Starting from [depth_min, depth_max], each axis intersects the interval with the ray's stay in the slab
+     [1.5 vl, (R - 1.5) vl], both ends computed once as 1.5 vl and (f64(R) - 1.5) vl: t = (end - e_a) / dir_a for both ends, the smaller
+     raises the lower end, the larger lowers the upper end.  An axis with dir_a == 0 divides nothing: it leaves the interval alone when
+     e_a lies in the slab and empties it otherwise.  An empty interval is no hit.  A sample is read only where the three computed q_a
+     themselves lie in the slab (a slab end that rounding moved by an ulp may not: it is an unobserved sample).  For such a q,
+     q_a / vl - 0.5 is in [1, R - 2] up to a rounding: the nearest voxel floor(q_a / vl) is in [1, R - 2], T's floor in [0, R - 2] with a
+     far corner of at most R - 1, and the normal's g_a -+ 0.99 in [0.01, R - 1.01] up to 2^-40: extraction item 4's argument.  The refined
+     s* lies in [s0, s1] (item 5) and q_a(s) is monotone in s as computed, so q(s*) lies between two tested points and is in the slab too.
+  3. (Sparse volumes: see se3et_amd/tsdf_sparse.py.)
+  4. March.  s starts at the interval's lower end.  The sample at s is the nearest voxel's stored (f, w); it is observed iff
+     w >= f32(weight_threshold).  Observed: s advances by max(vl, f64(f) sdf_trunc) / m.  Unobserved: by vl / m.  A crossing is an
+     observed sample with f <= 0 whose predecessor on the ray was observed with f > 0: a ray that starts on the negative side has no hit
+     until it has seen a positive observed sample, and no crossing is taken across an unobserved sample.  Marching ends at the first
+     crossing or when s passes the upper end.  Every step advances s by vl / m at least, so a ray takes at most (hi - lo) / (vl / m) + 1
+     samples, and the loop counts them against that number + 1.  (depth_max - depth_min) / vl is at most ops.RAYCAST_LIMITS['max_steps'].
+  5. Refinement.  At the crossing between s0 and s1: F0 = T(q(s0)), F1 = T(q(s1)) (extraction item 4's T: stored values, observed or
+     not).  If F0 > 0 and F1 <= 0 those are used, otherwise the two nearest-voxel values.  s* = ((s1 F0) - (s0 F1)) / (F0 - F1), then
+     limited to [s0, s1], which only rounding can leave.
+  6. Outputs at s*: depth = f32(s*); point = q(s*) + o; normal = extraction item 4 at q(s*), which points to the positive side, towards
+     the camera; a colour channel is T's sum over that colour plane with T's weights, rounded once to float32.  A pixel without a hit
+     holds depth 0, a NaN point and normal, colour 0 and mask False.
+  7. Determinism.  No atomics, every pixel independent: a view is bit-identical alone, anywhere in a batch, across chunks, run to run.
+ray_cast refuses, as a ValueError before any launch: an image side outside [1, max_image]; depth_min not positive or depth_max <= depth_min;
+(depth_max - depth_min) / vl above max_steps; a non-finite intrinsic or a focal length of 0; an extrinsic that camera_poses cannot invert;
+counts that do not sum to the views; an unknown or repeated map name; 'color' of volumes made without colour.
+
 Contract: depth images as clouds.  All float64, output in row-major pixel order.  z = raw / scaling_factor; z > distance_limit makes z = 0;
 x = ((u - cx) z) / fx, y = ((v - cy) z) / fy.
   'reference'   the reference function, quirks included: v = (row W + u) / W, a true quotient, so the row is fractional; a pixel is kept
@@ -70,7 +103,10 @@ two tiny values).  Colours are stored in [0, 1] (Open3D stores 0 .. 255 and divi
 converted per gather, never as a float image; create_from_depth_image's float32 depth image is float64 arithmetic here.  With float32
 depth the reference convention divides in float64 (numpy would divide a float32 array in float32).  The mesh leaves out the outer shell
 of cubes that Open3D walks, numbers its vertices by position where Open3D numbers them in the order of first use, and resolves an ambiguous
-cube face by separating the negative corners, which may not be Open3D's choice.
+cube face by separating the negative corners, which may not be Open3D's choice.  Ray casting (Open3D's VoxelBlockGrid.ray_cast) has no range
+map: every ray marches from depth_min; its step is Euclidean (Open3D advances the ray parameter by the sdf itself); refinement interpolates
+the trilinear field, not the two samples; a uniform volume is cast inside its inner box only; observed is a threshold on the stored weight;
+colours are in [0, 1].
 
 Determinism.  Every voxel is independent and there are no atomics: a volume's state and clouds are bit-identical alone, anywhere in a
 batch, from run to run, and whether its frames arrive in one integrate call or split over several."""
@@ -78,7 +114,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from .stacking import as_tensor, chunks, device_of, exclusive_offsets, transforms_of
+from .stacking import as_tensor, chunks, device_of, exclusive_offsets, to_device, transforms_of
 
 _FAMILY = 'TSDF fusion'
 _LIMITS = _ops.TSDF_LIMITS
@@ -147,6 +183,42 @@ def _intrinsics(what, intrinsics, F, dtype):
     if K.dim() != 2 or tuple(K.shape) != (F, 4):
         raise ValueError('%s: intrinsics must be (fx, fy, cx, cy) as (4,) or one row per frame (%d, 4), got %s' % (what, F, tuple(K.shape)))
     return K.to(dtype).contiguous()
+
+
+def _ray_cast_args(what, V, dev, has_color, voxel_length, intrinsics, extrinsics, height, width, frame_counts, depth_min, depth_max, maps):
+    """What ray_cast refuses, for both volume types.  Returns (views (F, 16) float64 on the device: the 3 x 4 camera pose by rows, then fx, fy,
+    cx, cy; the volume of each view as a host list; the counts; the maps as a tuple; H; W)."""
+    from .tsdf_sparse import camera_poses
+    if int(height) != height or int(width) != width or not (1 <= int(height) <= _LIMITS['max_image'] and 1 <= int(width) <= _LIMITS['max_image']):
+        raise ValueError('%s: an image of %r x %r: each side must be an integer in [1, %d]' % (what, height, width, _LIMITS['max_image']))
+    lo, hi = float(depth_min), float(depth_max)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo > 0 and hi > lo):
+        raise ValueError('%s: depth_min %r, depth_max %r: 0 < depth_min < depth_max expected' % (what, depth_min, depth_max))
+    if not (hi - lo) / voxel_length <= _ops.RAYCAST_LIMITS['max_steps']:
+        raise ValueError('%s: (depth_max - depth_min) / voxel_length is %g (at most %d)' % (what, (hi - lo) / voxel_length, _ops.RAYCAST_LIMITS['max_steps']))
+    maps = (maps,) if isinstance(maps, str) else tuple(maps)
+    if any(m not in _ops.RAYCAST_MAPS for m in maps) or len(set(maps)) != len(maps):
+        raise ValueError('%s: maps %r must be distinct names among %s' % (what, maps, ', '.join(_ops.RAYCAST_MAPS)))
+    if 'color' in maps and not has_color:
+        raise ValueError("%s: the map 'color' of volumes made without colour" % what)
+    if isinstance(extrinsics, (list, tuple)):
+        extrinsics = [as_tensor(e).detach().cpu().to(torch.float64).reshape(4, 4) for e in extrinsics]
+        extrinsics = torch.stack(extrinsics, 0) if extrinsics else torch.zeros((0, 4, 4), dtype=torch.float64)
+    E = as_tensor(extrinsics).detach().to(torch.float64).reshape(-1, 4, 4)
+    F = int(E.shape[0])
+    if frame_counts is None:
+        if V != 1:
+            raise ValueError('%s: frame_counts is required for %d volumes' % (what, V))
+        frame_counts = [F]
+    counts = [int(n) for n in (frame_counts.tolist() if hasattr(frame_counts, 'tolist') else frame_counts)]
+    if len(counts) != V or any(n < 0 for n in counts) or sum(counts) != F:
+        raise ValueError('%s: frame_counts %r must be %d counts >= 0 that sum to the %d views given' % (what, counts, V, F))
+    K = _intrinsics(what, intrinsics, F, torch.float64).cpu()
+    if not bool(torch.isfinite(K).all()) or bool((K[:, :2] == 0).any()):
+        raise ValueError('%s: an intrinsic is not finite, or a focal length is 0' % what)
+    P = camera_poses(E, what)
+    views = torch.cat([torch.from_numpy(P[:, :3, :].reshape(F, 12)), K], 1).contiguous().to(dev)
+    return views, [v for v, n in enumerate(counts) for _ in range(n)], counts, maps, int(height), int(width)
 
 
 class TSDFVolumes:
@@ -237,6 +309,30 @@ class TSDFVolumes:
             normals += list(torch.split(n, nv))
             colors += list(torch.split(c, nv)) if c is not None else [None] * (b - a)
         return vertices, triangles, normals, colors
+
+    @torch.no_grad()
+    def ray_cast(self, intrinsics, extrinsics, height, width, frame_counts=None, depth_min=0.1, depth_max=3.0, weight_threshold=1.0,
+                 maps=('depth', 'color')):
+        """The volumes seen from F cameras (contract: ray casting): extrinsics (F, 4, 4) world to camera, intrinsics as in integrate,
+        frame_counts (V,) on the host: volume v renders the next frame_counts[v] views (default: all views of volume 0 when V = 1; zero
+        views for a volume is fine).  Returns a dict of device tensors for the names in maps: 'depth' (F, H, W) float32, camera z in metres;
+        'points' (F, H, W, 3) float64, world coordinates; 'normals' (F, H, W, 3) float64, unit, towards the positive side; 'color'
+        (F, H, W, 3) float32 in [0, 1]; 'mask' (F, H, W) bool.  A pixel without a hit holds 0, NaN, NaN, 0 and False.  Nothing is read back."""
+        what = 'TSDFVolumes.ray_cast'
+        V, dev = self.num_volumes, self.device
+        views, volume_of, counts, maps, H, W = _ray_cast_args(what, V, dev, self.color is not None, self.voxel_length, intrinsics, extrinsics, height,
+                                                              width, frame_counts, depth_min, depth_max, maps)
+        _gpu_only(what, dev, volumes=self.tsdf)
+        out = _ops.raycast_outputs(maps, len(volume_of), H, W, dev)
+        offsets = exclusive_offsets(counts)
+        for a, b in chunks(V):
+            f0, f1 = offsets[a], offsets[b]
+            if f0 == f1:
+                continue
+            _ops.tsdf_raycast_stack(self.tsdf[a:b], self.weight[a:b], None if self.color is None else self.color[a:b], self.voxel_length,
+                                    self.sdf_trunc, self.origins[a:b], views[f0:f1], to_device([v - a for v in volume_of[f0:f1]], torch.int32, dev),
+                                    {name: x[f0:f1] for name, x in out.items()}, H, W, depth_min, depth_max, weight_threshold)
+        return out
 
 
 @torch.no_grad()

@@ -8,6 +8,8 @@ csrc/tsdf_core.h, the text of the uniform volumes of se3et_amd/tsdf.py).  Blocks
         .state()                     tsdf, weight (B, 16, 16, 16) and color (B, 3, 16, 16, 16) or None, in the same order (copies)
         .extract_point_clouds()      three lists, one entry per volume, as TSDFVolumes.extract_point_clouds
         .extract_triangle_meshes()   four lists, one entry per volume, as TSDFVolumes.extract_triangle_meshes
+        .ray_cast(intrinsics, extrinsics, height, width, frame_counts=None, depth_min=0.1, depth_max=3.0, weight_threshold=1.0,
+                  maps=('depth', 'color'))     as TSDFVolumes.ray_cast (contract E)
         .allocate_blocks(coords)     blocks by hand, zeros; .tsdf, .weight, .color are the storage, block i of the directory at .slots[i]
   fuse_depth_frames_sparse(depths_list, intrinsics, extrinsics_list, voxel_length, sdf_trunc, colors_list=None, stride=4, ...)
         construct, integrate and extract for a list of scenes: (points_list, normals_list, colors_list or None)
@@ -57,16 +59,30 @@ absent block has weight 0.  A vertex exists for an edge that changes sign inside
 C, items 4 to 6.  Vertices are ordered by (block in key order, x, y, z, axis), triangles by (block, x, y, z, table order); a triangle names
 the vertices of its own volume.  The write pass takes an int32 plane of 4096 entries a slot, as many bytes as the tsdf storage.
 
+Contract E: ray casting (csrc/tsdf_raycast.hip; the ray casting contract of se3et_amd/tsdf.py with o = 0 and this item 3 for its item 2:
+the two run one text, so a uniform volume at origin 0 and the same numbers in blocks render the same bits wherever both intervals are
+[depth_min, depth_max]).
+  3. The interval is [depth_min, depth_max].  The global voxel index is i_a = floor(q_a / vl), tested as a float64 against [-2^22, 2^22)
+     before it becomes a 64-bit integer; the block is i_a >> 4, the local voxel i_a & 15.  A block coordinate outside the key's range is an
+     absent block.  T and the normal use g_a = q_a / vl - 0.5 in global coordinates and read their eight corners through the directory; a
+     corner in an absent block reads 0 (contract C, item 6).  A storage index is slot 4096 + a 12-bit local index with the slot tested
+     against the storage, so every read is inside it.
+  4. (March, in addition.)  In an absent block s advances to the ray's exit from the block: the smallest (face_a - e_a) / dir_a over the
+     axes with dir_a != 0, face_a = L (b_a + 1) for dir_a > 0 and L b_a otherwise, b_a = floor(i_a / 16); and at least by vl / m.  The
+     sample counts as unobserved.
+
 Departures from Open3D.  Open3D allocates through a hash map, so the order of its units follows the order of insertion; here the order is
 the key order, and the order in which a call's records are deduplicated is irrelevant.  Allocation and integration share one depth rule
 (item 2; Open3D back-projects a float depth image with its own truncation).  integrate_scene_rgbd inverts a camera pose as a rigid
-transform (R^T, -R^T t), not as a general matrix.  Weights have no cap, colours are stored in [0, 1], the surface test is a sign test."""
+transform (R^T, -R^T t), not as a general matrix.  Weights have no cap, colours are stored in [0, 1], the surface test is a sign test.  Ray
+casting departs from VoxelBlockGrid.ray_cast as se3et_amd/tsdf.py lists: no range map, a Euclidean step, refinement on the trilinear field,
+observed as a threshold on the stored weight, colours in [0, 1]."""
 import numpy as np
 import torch
 
 from . import ops as _ops
 from .stacking import PAIR_MAX_PAIRS, as_tensor, device_of, exclusive_offsets, to_device, transforms_of
-from .tsdf import _COLOR_DTYPES, _DEPTH_DTYPES, _gpu_only, _images, _intrinsics, _join, _positive
+from .tsdf import _COLOR_DTYPES, _DEPTH_DTYPES, _gpu_only, _images, _intrinsics, _join, _positive, _ray_cast_args
 
 _FAMILY = 'sparse TSDF fusion'
 _LIMITS = _ops.STSDF_LIMITS
@@ -273,6 +289,22 @@ class SparseTSDFVolumes:
         v, t, n, c, nv, nt = _ops.stsdf_mesh_stack(self.tsdf, self.weight, self.color, self.keys, self._neighbors, self.voxel_length, cuts)
         return (list(torch.split(v, nv)), list(torch.split(t, nt)), list(torch.split(n, nv)),
                 list(torch.split(c, nv)) if c is not None else [None] * V)
+
+    # ---- ray casting ------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def ray_cast(self, intrinsics, extrinsics, height, width, frame_counts=None, depth_min=0.1, depth_max=3.0, weight_threshold=1.0,
+                 maps=('depth', 'color')):
+        """The volumes seen from F cameras (contract E): the arguments and the dict of maps of TSDFVolumes.ray_cast.  Nothing is read back."""
+        what = 'SparseTSDFVolumes.ray_cast'
+        V, dev = self.num_volumes, self.device
+        views, volume_of, counts, maps, H, W = _ray_cast_args(what, V, dev, self.has_color, self.voxel_length, intrinsics, extrinsics, height, width,
+                                                              frame_counts, depth_min, depth_max, maps)
+        _gpu_only(what, dev, volumes=self.tsdf)
+        out = _ops.raycast_outputs(maps, len(volume_of), H, W, dev)
+        if volume_of:
+            _ops.stsdf_raycast_stack(self.tsdf, self.weight, self.color, self.keys, self.slots, V, self.voxel_length, self.sdf_trunc, views,
+                                     to_device(volume_of, torch.int32, dev), out, H, W, depth_min, depth_max, weight_threshold)
+        return out
 
 
 @torch.no_grad()
