@@ -1647,6 +1647,114 @@ int se3_debug_stsdf_raycast_host(const float* tsdf, const float* weight, const f
                                  double weight_threshold, float* out_depth, double* out_points, double* out_normals, float* out_colors,
                                  uint8_t* out_mask);
 
+/* ---- mesh post-processing of stacked triangle meshes (csrc/mesh_ops.hip, csrc/mesh_ops_core.h) -----------------------------------------------------
+ * Open3D's cluster_connected_triangles, remove_triangles_by_mask + remove_unreferenced_vertices, compute_triangle_normals /
+ * compute_vertex_normals and filter_smooth_simple / _laplacian / _taubin for up to SE3_PAIR_MAX_PAIRS meshes per call, float64; the contract
+ * is the header comment of csrc/mesh_ops.hip.  The meshes are stacked as se3_tsdf_mesh_stack leaves them: vertices (N, 3) float64, triangles
+ * (M, 3) int64 naming vertices by their number within their own mesh, attributes (N, 3) float64, all on the DEVICE unless an entry is called
+ * _host; vertex_offsets_host and triangle_offsets_host (B + 1) int64 on the HOST, from 0, not decreasing; a mesh has fewer than 2^31
+ * vertices and triangles.  out_counts (B, SE3_MESH_OPS_COUNT_WORDS) int64 on the device: word 0 of a mesh is its status (a se3_mesh_ops_status
+ * bit: a triangle names a vertex outside [0, n); such a triangle is skipped, never dereferenced), the other words are named per entry.
+ *   se3_mesh_incidence_stack   two passes.  nbr_rows NULL: tri_row_offsets and nbr_row_offsets (N + 1) int64 become the exclusive offsets of
+ *                           the vertices' rows, tri_rows (3 M) ints holds each vertex's incident triangles ascending; counts words 1, 2: the
+ *                           mesh's incidences and neighbours.  Otherwise the write pass: nbr_rows (nbr_capacity) ints, each vertex's
+ *                           distinct neighbours ascending; nothing is written at or past the capacity.  Rows hold mesh-local numbers.
+ *                           workspace: se3_mesh_incidence_workspace_bytes(N).
+ *   se3_mesh_components_stack  out_clusters (M) int64: 0 .. k - 1 per mesh in ascending order of a cluster's lowest triangle;
+ *                           out_cluster_n_triangles (M) int64: cluster c of mesh b at triangle_offsets[b] + c, the slots past k hold 0;
+ *                           counts word 1: k.  workspace: se3_mesh_components_workspace_bytes(M).
+ *   se3_mesh_cluster_area_stack  out_cluster_area (M) float64 in the same slots.  order (M) int64: the stacked triangle rows sorted by
+ *                           (slot, row), i.e. a stable sort of out_clusters + triangle_offsets[mesh]; a place that names no row adds 0.
+ *                           workspace: se3_mesh_cluster_area_workspace_bytes(M).
+ *   se3_mesh_select_stack   two passes over one workspace (se3_mesh_select_workspace_bytes(N, M)), keep (M) bytes.  out_vertex_offsets_host
+ *                           NULL: out_vertex_map (N) int64 (the new number, -1 for a dropped vertex) and counts words 1, 2: the vertices and
+ *                           triangles kept.  Otherwise the write pass into the rows the output offsets name; normals and colors may be NULL.
+ *   se3_mesh_normals_stack  out_triangle_normals (M, 3) and out_vertex_normals (N, 3), either NULL; the tables only for the latter.  out_counts
+ *                           may be NULL; given, the triangle normals' pass sets the status words.
+ *   se3_mesh_smooth_stack   method: a se3_mesh_smooth_method; every step of `iterations` iterations is issued by the call, one launch per
+ *                           step; normals and colors may be NULL and are filtered like the positions.  0 iterations copies.  The outputs
+ *                           must not alias the inputs.  workspace: se3_mesh_smooth_workspace_bytes(N, arrays given).
+ *   se3_mesh_cluster_vertices_stack   simplify_vertex_clustering with the mean as contraction, in the four passes of se3_mesh_cluster_pass over one
+ *                           workspace (se3_mesh_cluster_vertices_workspace_bytes(N, M)); the caller sorts between them.  KEYS: keys (N) int64, a
+ *                           vertex's cell with x in the high bits (0 for a refused mesh), and the status words.  VERTICES: sorted_keys and
+ *                           vertex_order (N) int64, the stacked vertex rows sorted by (mesh, key, row); writes vertex_map (N) int64, rotated
+ *                           (M, 3) int64 (the remapped triangle with its lowest vertex first, -1 for a dropped one) and counts word 1, the new
+ *                           vertices.  TRIANGLES: triangle_order (M) int64, the stacked triangle rows sorted by (mesh, rotated triple, row), the
+ *                           dropped ones anywhere; counts word 2: the triangles that stay.  WRITE: into the rows the output offsets name.  A
+ *                           place of an order that names no row of its mesh is passed over.
+ *   se3_debug_mesh_*_host   the same text on HOST memory, serially, one mesh of n vertices and m triangles; the cluster outputs have m
+ *                           slots of which the first k are used; se3_debug_mesh_smooth_host filters one (n, 3) array. */
+enum se3_mesh_ops_limit {              /* (NAMED) */
+  SE3_MESH_OPS_COUNT_WORDS = 4,        /* int64 words of a mesh's row of out_counts */
+  SE3_MESH_OPS_AREA_LANES = 64,        /* lanes of the reduction tree of a cluster's area */
+  SE3_MESH_OPS_MAX_ITERATIONS = 100000 /* smoothing iterations of one call at most */
+};
+enum se3_mesh_ops_status {             /* (NAMED) */
+  SE3_MESH_OPS_BAD_TRIANGLE = 1,       /* a triangle names a vertex outside [0, n) */
+  SE3_MESH_OPS_NONFINITE = 2,          /* vertex clustering: a vertex or an attribute is not finite */
+  SE3_MESH_OPS_TOO_MANY_CELLS = 4      /* vertex clustering: an axis would need 2^21 cells or more */
+};
+enum se3_mesh_cluster_pass {           /* (NAMED) */
+  SE3_MESH_CLUSTER_KEYS = 0,
+  SE3_MESH_CLUSTER_VERTICES = 1,
+  SE3_MESH_CLUSTER_TRIANGLES = 2,
+  SE3_MESH_CLUSTER_WRITE = 3
+};
+enum se3_mesh_smooth_method {          /* (NAMED) */
+  SE3_MESH_SMOOTH_SIMPLE = 0,
+  SE3_MESH_SMOOTH_LAPLACIAN = 1,
+  SE3_MESH_SMOOTH_TAUBIN = 2
+};
+size_t se3_mesh_incidence_workspace_bytes(int64_t n_total);
+int se3_mesh_incidence_stack(const int64_t* triangles, const int64_t* vertex_offsets_host, const int64_t* triangle_offsets_host, int num_meshes,
+                             int64_t* tri_row_offsets, int* tri_rows, int64_t* nbr_row_offsets, int64_t nbr_capacity, int* nbr_rows,
+                             int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+size_t se3_mesh_components_workspace_bytes(int64_t m_total);
+int se3_mesh_components_stack(const int64_t* triangles, const int64_t* vertex_offsets_host, const int64_t* triangle_offsets_host, int num_meshes,
+                              const int64_t* tri_row_offsets, const int* tri_rows, int64_t* out_clusters, int64_t* out_cluster_n_triangles,
+                              int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+size_t se3_mesh_cluster_area_workspace_bytes(int64_t m_total);
+int se3_mesh_cluster_area_stack(const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                                const int64_t* triangle_offsets_host, int num_meshes, const int64_t* cluster_n_triangles, const int64_t* order,
+                                double* out_cluster_area, void* workspace, size_t workspace_bytes, void* stream);
+size_t se3_mesh_select_workspace_bytes(int64_t n_total, int64_t m_total);
+int se3_mesh_select_stack(const double* vertices, const double* normals, const double* colors, const int64_t* triangles, const uint8_t* keep,
+                          const int64_t* vertex_offsets_host, const int64_t* triangle_offsets_host, int num_meshes,
+                          const int64_t* out_vertex_offsets_host, const int64_t* out_triangle_offsets_host, double* out_vertices,
+                          double* out_normals, double* out_colors, int64_t* out_triangles, int64_t* out_vertex_map, int64_t* out_counts,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int se3_mesh_normals_stack(const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                           const int64_t* triangle_offsets_host, int num_meshes, const int64_t* tri_row_offsets, const int* tri_rows,
+                           int normalized, double* out_triangle_normals, double* out_vertex_normals, int64_t* out_counts, void* stream);
+size_t se3_mesh_cluster_vertices_workspace_bytes(int64_t n_total, int64_t m_total);
+int se3_mesh_cluster_vertices_stack(int pass, const double* vertices, const double* normals, const double* colors, const int64_t* triangles,
+                                    const int64_t* vertex_offsets_host, const int64_t* triangle_offsets_host, int num_meshes, double voxel_size,
+                                    int64_t* keys, const int64_t* sorted_keys, const int64_t* vertex_order, int64_t* vertex_map, int64_t* rotated,
+                                    const int64_t* triangle_order, const int64_t* out_vertex_offsets_host,
+                                    const int64_t* out_triangle_offsets_host, double* out_vertices, double* out_normals, double* out_colors,
+                                    int64_t* out_triangles, int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_mesh_cluster_vertices_host(const double* vertices, const double* normals, const double* colors, const int64_t* triangles, int64_t n,
+                                         int64_t m, double voxel_size, int64_t vertex_capacity, int64_t triangle_capacity, double* out_vertices,
+                                         double* out_normals, double* out_colors, int64_t* out_triangles, int64_t* out_vertex_map,
+                                         int64_t* out_counts);
+size_t se3_mesh_smooth_workspace_bytes(int64_t n_total, int num_arrays);
+int se3_mesh_smooth_stack(const double* vertices, const double* normals, const double* colors, const int64_t* vertex_offsets_host, int num_meshes,
+                          const int64_t* nbr_row_offsets, const int* nbr_rows, int method, int iterations, double lambda, double mu,
+                          double* out_vertices, double* out_normals, double* out_colors, void* workspace, size_t workspace_bytes, void* stream);
+int se3_debug_mesh_incidence_host(const int64_t* triangles, int64_t n, int64_t m, int64_t* tri_row_offsets, int* tri_rows,
+                                  int64_t* nbr_row_offsets, int64_t nbr_capacity, int* nbr_rows, int64_t* out_counts);
+int se3_debug_mesh_components_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const int64_t* tri_row_offsets,
+                                   const int* tri_rows, int64_t* out_clusters, int64_t* out_cluster_n_triangles, double* out_cluster_area,
+                                   int64_t* out_counts);
+int se3_debug_mesh_select_host(const double* vertices, const double* normals, const double* colors, const int64_t* triangles,
+                               const uint8_t* keep, int64_t n, int64_t m, int64_t vertex_capacity, int64_t triangle_capacity,
+                               double* out_vertices, double* out_normals, double* out_colors, int64_t* out_triangles, int64_t* out_vertex_map,
+                               int64_t* out_counts);
+int se3_debug_mesh_normals_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const int64_t* tri_row_offsets,
+                                const int* tri_rows, int normalized, double* out_triangle_normals, double* out_vertex_normals);
+int se3_debug_mesh_smooth_host(const double* values, int64_t n, const int64_t* nbr_row_offsets, const int* nbr_rows, int method, int iterations,
+                               double lambda, double mu, double* out_values);
+
 #ifdef __cplusplus
 }
 #endif

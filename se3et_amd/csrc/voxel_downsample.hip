@@ -32,24 +32,17 @@
 
 #include "common.h"
 #include "stack_rows.h"
+#include "voxel_key.h"
 
 namespace {
 
 constexpr int kVoxelThreads = 256;
 constexpr int kVoxelSerialMax = 64;                   // members that one thread orders; larger voxels are ordered by a workgroup
-constexpr double kVoxelAxisCap = 2097152.0;          // 2^21 voxels per axis: three indices make a 63-bit key
 constexpr int kVoxelNonFinite = 1, kVoxelTooMany = 2;
 constexpr unsigned long long kVoxelEmptyKey = ~0ull;
 constexpr int64_t kVoxelMaxPoints = (1ll << 30) - 64;          // table slots (2 n + clouds) and every index stay below 2^31
 
 // ---- the contract's arithmetic: the same text on the host and on the device -------------------------------------------------------------------
-PG_HD double vd_origin(double mn, double voxel_size) { return mn - 0.5 * voxel_size; }
-PG_HD bool vd_axis_ok(double mx, double org, double voxel_size) { return (mx - org) / voxel_size < kVoxelAxisCap; }
-PG_HD unsigned long long vd_key(const double* p, const double* org, double voxel_size) {
-  unsigned long long key = 0;
-  for (int d = 0; d < 3; d++) key |= (unsigned long long)(long long)floor((p[d] - org[d]) / voxel_size) << (21 * d);
-  return key;
-}
 // mean of rows members[0 .. count) (ascending) of `src` (cloud-local rows from row0)
 PG_HD void vd_mean(const void* src, int elem, int64_t row0, const int* members, int count, double* out) {
   double s[3] = {0.0, 0.0, 0.0};

@@ -3,9 +3,26 @@
   write_triangle_mesh_ply(path, vertices, triangles, normals=None, colors=None)      a binary little-endian PLY file
   mesh_edge_census(triangles)      how often every directed edge and its reverse occur: the watertightness check
 
-Both take tensors (from any device) or arrays."""
+Both take tensors (from any device) or arrays.
+
+And what happens between marching cubes and the file, on the DEVICE (csrc/mesh_ops.hip carries the contract): lists of GPU tensors in, one
+entry per mesh, as extract_triangle_meshes returns them (vertices (n, 3) float64, triangles (m, 3) int64; an attribute list of Nones counts
+as not given), lists of GPU tensors out; longer lists are cut into calls of at most PAIR_MAX_PAIRS meshes.  A host tensor raises RuntimeError: there is no CPU implementation.  A triangle
+that names a vertex outside [0, n) raises ValueError (the kernels set a status word and never read through the number).
+
+  triangle_normals_meshes / vertex_normals_meshes             compute_triangle_normals / compute_vertex_normals
+  cluster_connected_triangles_meshes                          cluster_connected_triangles
+  select_triangles_meshes                                     remove_triangles_by_mask + remove_unreferenced_vertices
+  remove_small_components_meshes                              the tutorial's "remove small / keep the largest component" recipe
+  filter_smooth_meshes                                        filter_smooth_simple / _laplacian / _taubin
+  simplify_vertex_clustering_meshes                           simplify_vertex_clustering (contraction = Average), with a defined output order
+  postprocess_triangle_meshes                                 components, smoothing, simplification and fresh normals in that order
+
+Every output is bit-identical alone or in a batch, and from run to run."""
 import numpy as np
 import torch
+
+from . import ops, stacking
 
 
 def _host(x, dtype, what, name, rows=None):
@@ -66,3 +83,178 @@ def mesh_edge_census(triangles):
     at = np.searchsorted(code, reverse).clip(max=len(code) - 1)
     backward = np.where(code[at] == reverse, forward[at], 0)
     return edges, forward.astype(np.int64), backward.astype(np.int64)
+
+
+# ---- on the device ----------------------------------------------------------------------------------------------------------------------------------
+_FAMILY = 'mesh post-processing'
+
+
+def _stacked(what, vertices_list, triangles_list, a, b, attributes=()):
+    """the meshes a .. b - 1 of the lists as one StackedMeshes, and each attribute list (or None) stacked the same way"""
+    v = stacking.gpu_rows_each(vertices_list[a:b], None, what + ': vertices', _FAMILY, dtypes=(torch.float64,))
+    dev = v[0].device
+    t = stacking.gpu_rows_each(triangles_list[a:b], dev, what + ': triangles', _FAMILY, dtypes=(torch.int64,))
+    S = ops.StackedMeshes(stacking.stack(v), stacking.stack(t), stacking.lengths(v), stacking.lengths(t), what)
+    out = []
+    for name, lst in attributes:
+        if lst is None:
+            out.append(None)
+            continue
+        x = stacking.gpu_rows_each(lst[a:b], dev, '%s: %s' % (what, name), _FAMILY, dtypes=(torch.float64,))
+        if stacking.lengths(x) != S.vertex_counts:
+            raise RuntimeError('%s: %s must have one row per vertex' % (what, name))
+        out.append(stacking.stack(x))
+    return S, out
+
+
+def _lists(what, vertices_list, triangles_list, *others):
+    P = len(vertices_list)
+    if len(triangles_list) != P or any(o is not None and len(o) != P for o in others):
+        raise RuntimeError('%s: one entry per mesh in every list' % what)
+    return P
+
+
+def _given(lst):
+    """an attribute list, or None for no list or the list of Nones that extract_triangle_meshes returns without colour"""
+    return None if lst is None or all(x is None for x in lst) else lst
+
+
+def _split(x, counts):
+    return None if x is None else list(torch.split(x, counts))
+
+
+def triangle_normals_meshes(vertices_list, triangles_list, normalized=True):
+    """cross(v1 - v0, v2 - v0) of every triangle, (m, 3) float64 per mesh; normalized: divided by its length, (0, 0, 1) for a zero length."""
+    what = 'triangle_normals_meshes'
+    out = []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list)):
+        S, _ = _stacked(what, vertices_list, triangles_list, a, b)
+        out += _split(ops.mesh_normals_stack(S, None, normalized, True, False)[0], S.triangle_counts)
+    return out
+
+
+def vertex_normals_meshes(vertices_list, triangles_list):
+    """The sum of the un-normalised normals of a vertex's triangles in ascending triangle order (area weighting, as Open3D), normalised;
+    (0, 0, 1) for a vertex of no triangle or a zero sum.  (n, 3) float64 per mesh."""
+    what = 'vertex_normals_meshes'
+    out = []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list)):
+        S, _ = _stacked(what, vertices_list, triangles_list, a, b)
+        out += _split(ops.mesh_normals_stack(S, ops.mesh_incidence_stack(S), True, False, True)[1], S.vertex_counts)
+    return out
+
+
+def cluster_connected_triangles_meshes(vertices_list, triangles_list):
+    """Open3D's cluster_connected_triangles: (triangle_clusters (m,) int64, cluster_n_triangles (k,) int64, cluster_area (k,) float64), a list
+    per mesh each.  Triangles are adjacent iff they share an undirected edge; clusters are numbered in ascending order of their lowest
+    triangle, which is the order of Open3D's search."""
+    what = 'cluster_connected_triangles_meshes'
+    out = [], [], []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list)):
+        S, _ = _stacked(what, vertices_list, triangles_list, a, b)
+        clusters, count, area, k = ops.mesh_components_stack(S, ops.mesh_incidence_stack(S))
+        for x, lst in zip((clusters, count, area), out):
+            lst += _split(x, S.triangle_counts)
+        for lst in out[1:]:
+            lst[a:] = [x[:kk] for x, kk in zip(lst[a:], k)]
+    return out
+
+
+def select_triangles_meshes(vertices_list, triangles_list, keep_list, normals_list=None, colors_list=None):
+    """Open3D's remove_triangles_by_mask (with the mask inverted: keep is what stays) followed by remove_unreferenced_vertices.  keep: (m,)
+    bool or uint8 per mesh.  Returns (vertices_list, triangles_list, normals_list, colors_list, vertex_maps): the kept triangles and the
+    vertices they name in their original order, renumbered; vertex_maps (n,) int64: old -> new, -1 for a dropped vertex."""
+    what = 'select_triangles_meshes'
+    normals_list, colors_list = _given(normals_list), _given(colors_list)
+    out = [], [], [], [], []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list, keep_list, normals_list, colors_list)):
+        S, (nrm, col) = _stacked(what, vertices_list, triangles_list, a, b, (('normals', normals_list), ('colors', colors_list)))
+        keep = []
+        for i, k in enumerate(keep_list[a:b]):
+            if not torch.is_tensor(k) or not k.is_cuda or k.dim() != 1 or k.shape[0] != S.triangle_counts[i] or k.dtype not in (torch.bool, torch.uint8):
+                raise RuntimeError('%s: keep %d must be a GPU tensor (m,) bool or uint8 (%s has no CPU implementation)' % (what, a + i, _FAMILY))
+            keep.append(k.to(torch.uint8))
+        v, t, n, c, vmap, vc, tc = ops.mesh_select_stack(S, stacking.stack(keep), nrm, col)
+        for x, counts, lst in zip((v, t, n, c, vmap), (vc, tc, vc, vc, S.vertex_counts), out):
+            lst += [None] * S.B if x is None else _split(x, counts)
+    return out[0], out[1], None if normals_list is None else out[2], None if colors_list is None else out[3], out[4]
+
+
+def remove_small_components_meshes(vertices_list, triangles_list, normals_list=None, colors_list=None, min_triangles=None, min_area=None,
+                                   keep_largest=None):
+    """The clusters of cluster_connected_triangles_meshes with at least min_triangles triangles and at least min_area area, or (keep_largest)
+    the keep_largest largest by triangle count, equal counts going to the lower cluster number; then select_triangles_meshes.  The mask is
+    computed on the device.  Returns what select_triangles_meshes returns."""
+    what = 'remove_small_components_meshes'
+    if keep_largest is not None and (min_triangles is not None or min_area is not None):
+        raise ValueError('%s: keep_largest or the thresholds, not both' % what)
+    if keep_largest is None and min_triangles is None and min_area is None:
+        raise ValueError('%s: one of min_triangles, min_area, keep_largest is needed' % what)
+    clusters, count, area = cluster_connected_triangles_meshes(vertices_list, triangles_list)
+    keep = []
+    for cl, n, ar in zip(clusters, count, area):
+        if keep_largest is not None:
+            good = torch.zeros_like(n, dtype=torch.bool)
+            good[torch.sort(n, descending=True, stable=True).indices[:max(int(keep_largest), 0)]] = True
+        else:
+            good = torch.ones_like(n, dtype=torch.bool)
+            if min_triangles is not None:
+                good &= n >= int(min_triangles)
+            if min_area is not None:
+                good &= ar >= float(min_area)
+        keep.append(good[cl])
+    return select_triangles_meshes(vertices_list, triangles_list, keep, normals_list, colors_list)
+
+
+def filter_smooth_meshes(vertices_list, triangles_list, iterations, method='taubin', lambda_filter=0.5, mu=-0.53, normals_list=None,
+                         colors_list=None):
+    """Open3D's filter_smooth_simple ('simple'), filter_smooth_laplacian ('laplacian') and filter_smooth_taubin ('taubin').  With N the
+    distinct neighbours of a vertex x in ascending order and s their sum in that order: simple (x + s) / (|N| + 1); laplacian
+    x + lambda_filter (s / |N| - x); taubin: per iteration a laplacian step with lambda_filter, then one with mu.  Normals and colours are
+    filtered by the same rule (normals are not renormalised).  Deviation from Open3D: a vertex without neighbours keeps its value in all
+    three filters, where Open3D's Laplacian divides by zero.  Returns (vertices_list, normals_list, colors_list); the triangles stay."""
+    what = 'filter_smooth_meshes'
+    normals_list, colors_list = _given(normals_list), _given(colors_list)
+    out = [], [], []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list, normals_list, colors_list)):
+        S, (nrm, col) = _stacked(what, vertices_list, triangles_list, a, b, (('normals', normals_list), ('colors', colors_list)))
+        res = ops.mesh_smooth_stack(S, ops.mesh_incidence_stack(S), method, iterations, lambda_filter, mu, nrm, col)
+        for x, lst in zip(res, out):
+            lst += [None] * S.B if x is None else _split(x, S.vertex_counts)
+    return out[0], None if normals_list is None else out[1], None if colors_list is None else out[2]
+
+
+def simplify_vertex_clustering_meshes(vertices_list, triangles_list, voxel_size, normals_list=None, colors_list=None):
+    """Open3D's simplify_vertex_clustering with contraction = Average.  Per mesh voxel_min_bound = min_bound - voxel_size / 2 and the cell of a
+    vertex is floor((v - voxel_min_bound) / voxel_size) per axis; the vertices of a cell become one vertex, the mean of positions and
+    attributes (summed in ascending vertex order, divided once).  Where Open3D's order is that of a hash map, here it is defined: new vertices
+    in ascending (x, y, z) cell order; triangles remapped, one with two equal new vertices dropped, every survivor rotated (not sorted) so that
+    its lowest vertex comes first, of equal triangles the first in the original order kept, survivors in their original order.  ValueError
+    for a voxel_size that is not positive and finite or for which an axis would need 2^21 cells or more, and for a mesh that is not finite.
+    Returns (vertices_list, triangles_list, normals_list, colors_list, vertex_maps): vertex_maps (n,) int64, old -> new."""
+    what = 'simplify_vertex_clustering_meshes'
+    normals_list, colors_list = _given(normals_list), _given(colors_list)
+    out = [], [], [], [], []
+    for a, b in stacking.chunks(_lists(what, vertices_list, triangles_list, normals_list, colors_list)):
+        S, (nrm, col) = _stacked(what, vertices_list, triangles_list, a, b, (('normals', normals_list), ('colors', colors_list)))
+        v, t, n, c, vmap, vc, tc = ops.mesh_cluster_vertices_stack(S, voxel_size, nrm, col)
+        for x, counts, lst in zip((v, t, n, c, vmap), (vc, tc, vc, vc, S.vertex_counts), out):
+            lst += [None] * S.B if x is None else _split(x, counts)
+    return out[0], out[1], None if normals_list is None else out[2], None if colors_list is None else out[3], out[4]
+
+
+def postprocess_triangle_meshes(vertices_list, triangles_list, normals_list=None, colors_list=None, min_component_triangles=None,
+                                smooth_iterations=0, simplify_voxel_size=None):
+    """The tutorial's recipe after extract_triangle_meshes, in this order: drop the connected components below min_component_triangles
+    triangles, smooth_iterations Taubin iterations (lambda 0.5, mu -0.53), simplify_vertex_clustering_meshes at simplify_voxel_size, and,
+    when normals were given, fresh vertex normals.  Returns (vertices_list, triangles_list, normals_list, colors_list)."""
+    v, t, n, c = vertices_list, triangles_list, _given(normals_list), _given(colors_list)
+    if min_component_triangles is not None:
+        v, t, n, c, _ = remove_small_components_meshes(v, t, n, c, min_triangles=min_component_triangles)
+    if smooth_iterations:
+        v, _, c = filter_smooth_meshes(v, t, smooth_iterations, 'taubin', colors_list=c)
+    if simplify_voxel_size is not None:
+        v, t, _, c, _ = simplify_vertex_clustering_meshes(v, t, simplify_voxel_size, colors_list=c)
+    if n is not None:
+        n = vertex_normals_meshes(v, t)
+    return v, t, n, c

@@ -3455,3 +3455,218 @@ def stsdf_raycast_stack(tsdf, weight, color, keys, slots, num_volumes, voxel_len
                                         int(num_volumes), float(voxel_length), float(sdf_trunc), _dp(v), _dp(vv), F, H, W, float(depth_min),
                                         float(depth_max), float(weight_threshold), *ptrs, _stream()), 'se3_stsdf_raycast_stack')
     return out
+
+
+# ---- mesh post-processing of stacked triangle meshes (csrc/mesh_ops.hip) ---------------------------------------------------------------------------
+MESH_OPS_LIMITS = {name[len('SE3_MESH_OPS_'):].lower(): value for name, value in ENUMS['se3_mesh_ops_limit'].items()}
+MESH_OPS_STATUS = {name[len('SE3_MESH_OPS_'):].lower(): value for name, value in ENUMS['se3_mesh_ops_status'].items()}
+MESH_SMOOTH_METHODS = {name[len('SE3_MESH_SMOOTH_'):].lower(): value for name, value in ENUMS['se3_mesh_smooth_method'].items()}
+_MESH_WORDS = MESH_OPS_LIMITS['count_words']
+
+
+class StackedMeshes:
+    """The meshes of one call end to end: vertices (N, 3) float64, triangles (M, 3) int64 naming vertices by their number within their own
+    mesh, the host offsets of both.  At most PAIR_MAX_PAIRS meshes, each below 2^31 vertices and triangles."""
+
+    def __init__(self, vertices, triangles, vertex_counts, triangle_counts, what='StackedMeshes'):
+        self.vertices, self.triangles = _req(vertices, torch.float64, 'vertices', 2), _req(triangles, torch.int64, 'triangles', 2)
+        if vertices.shape[1] != 3 or triangles.shape[1] != 3 or triangles.device != vertices.device:
+            raise RuntimeError('%s: vertices (N, 3) and triangles (M, 3) on one device expected' % what)
+        if len(vertex_counts) != len(triangle_counts):
+            raise RuntimeError('%s: one vertex count and one triangle count per mesh' % what)
+        if any(int(n) >= 1 << 31 for n in list(vertex_counts) + list(triangle_counts)):
+            raise ValueError('%s: a mesh has 2^31 vertices or triangles or more' % what)
+        self.vertex_counts, self.triangle_counts = [int(n) for n in vertex_counts], [int(m) for m in triangle_counts]
+        self.voff, self.toff = _pair_offsets(vertex_counts, vertices.shape[0], what), _pair_offsets(triangle_counts, triangles.shape[0], what)
+        self.B, self.N, self.M, self.device = len(self.vertex_counts), int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+
+    def attribute(self, x, name):
+        if x is None:
+            return None
+        x = _req(x, torch.float64, name, 2)
+        if tuple(x.shape) != (self.N, 3) or x.device != self.device:
+            raise RuntimeError('%s must be (%d, 3) on %s' % (name, self.N, self.device))
+        return x
+
+    def counts(self):
+        return torch.empty((self.B, _MESH_WORDS), dtype=torch.int64, device=self.device)
+
+    def read(self, counts, what):
+        """the counts on the host (the one read of a pass); ValueError for a mesh whose status word is set"""
+        rows = counts.cpu().tolist()
+        bad = [b for b, row in enumerate(rows) if row[0] & MESH_OPS_STATUS['bad_triangle']]
+        if bad:
+            raise ValueError('%s: a triangle of mesh %s names a vertex outside [0, n) of its mesh' % (what, ', '.join(map(str, bad))))
+        return rows
+
+
+def _mesh_bytes(nbytes, dev):
+    return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+
+
+def _optr(t):
+    return None if t is None else _dp(t)
+
+
+class MeshIncidence:
+    """The two CSR tables of mesh_incidence_stack: tri_offsets, nbr_offsets (N + 1) int64, tri_rows, nbr_rows int32 (mesh-local numbers)."""
+
+
+def mesh_incidence_stack(meshes):
+    """HIP (csrc/mesh_ops.hip): the vertex -> incident triangles and vertex -> neighbours tables of the stacked meshes: the count pass, one
+    host read of the totals and the status, the write pass.  ValueError for a triangle out of range."""
+    what, S, dev = 'mesh_incidence_stack', meshes, meshes.device
+    inc = MeshIncidence()
+    inc.tri_offsets = torch.empty((S.N + 1,), dtype=torch.int64, device=dev)
+    inc.nbr_offsets = torch.empty((S.N + 1,), dtype=torch.int64, device=dev)
+    inc.tri_rows = torch.empty((3 * S.M,), dtype=torch.int32, device=dev)
+    counts = S.counts()
+    nbytes = lib().se3_mesh_incidence_workspace_bytes(S.N)
+    ws, stream = _mesh_bytes(nbytes, dev), _stream()
+    args = (_dp(S.triangles), S.voff, S.toff, S.B, _dp(inc.tri_offsets), _dp(inc.tri_rows), _dp(inc.nbr_offsets))
+    check(lib().se3_mesh_incidence_stack(*args, 0, None, _dp(counts), ws.data_ptr(), nbytes, stream), 'se3_mesh_incidence_stack')
+    rows = S.read(counts, what)
+    inc.incidences, inc.neighbors = sum(r[1] for r in rows), sum(r[2] for r in rows)
+    inc.tri_rows = inc.tri_rows[:inc.incidences]
+    inc.nbr_rows = torch.empty((inc.neighbors,), dtype=torch.int32, device=dev)
+    if inc.neighbors:
+        check(lib().se3_mesh_incidence_stack(*args, inc.neighbors, _dp(inc.nbr_rows), _dp(counts), ws.data_ptr(), nbytes, stream),
+              'se3_mesh_incidence_stack')
+    return inc
+
+
+def mesh_components_stack(meshes, inc):
+    """HIP (csrc/mesh_ops.hip): the connected components of the triangles under shared edges.  Returns (clusters (M,) int64, cluster
+    n_triangles (M,) int64, cluster area (M,) float64, k: a list of B ints); cluster c of mesh b stands in slot triangle offset of b + c.
+    The areas need each cluster's triangles in ascending order: one stable sort of the slots (torch.sort) between the two entries."""
+    what, S, dev = 'mesh_components_stack', meshes, meshes.device
+    clusters = torch.empty((S.M,), dtype=torch.int64, device=dev)
+    n_triangles = torch.empty((S.M,), dtype=torch.int64, device=dev)
+    area = torch.zeros((S.M,), dtype=torch.float64, device=dev)
+    counts = S.counts()
+    nbytes = lib().se3_mesh_components_workspace_bytes(S.M)
+    ws, stream = _mesh_bytes(nbytes, dev), _stream()
+    check(lib().se3_mesh_components_stack(_dp(S.triangles), S.voff, S.toff, S.B, _dp(inc.tri_offsets), _dp(inc.tri_rows), _dp(clusters), _dp(n_triangles),
+                                          _dp(counts), ws.data_ptr(), nbytes, stream), 'se3_mesh_components_stack')
+    if S.M:
+        first = torch.repeat_interleave(to_device(list(S.toff)[:S.B], torch.int64, dev), to_device(S.triangle_counts, torch.int64, dev))
+        order = torch.sort(clusters + first, stable=True).indices
+        nbytes = lib().se3_mesh_cluster_area_workspace_bytes(S.M)
+        ws = _mesh_bytes(nbytes, dev)
+        check(lib().se3_mesh_cluster_area_stack(_dp(S.vertices), _dp(S.triangles), S.voff, S.toff, S.B, _dp(n_triangles), _dp(order), _dp(area),
+                                                ws.data_ptr(), nbytes, stream), 'se3_mesh_cluster_area_stack')
+    return clusters, n_triangles, area, [r[1] for r in S.read(counts, what)]
+
+
+def mesh_select_stack(meshes, keep, normals=None, colors=None):
+    """HIP (csrc/mesh_ops.hip): the triangles whose keep byte is set and the vertices they name, in their order, renumbered.  Returns
+    (vertices, triangles, normals, colors, vertex_map (N,) int64 with -1 for a dropped vertex, vertex_counts, triangle_counts)."""
+    what, S, dev = 'mesh_select_stack', meshes, meshes.device
+    keep = _req(keep, torch.uint8, 'keep', 1)
+    if keep.shape[0] != S.M or keep.device != dev:
+        raise RuntimeError('%s: keep must be (%d,) uint8 on %s' % (what, S.M, dev))
+    nrm, col = S.attribute(normals, 'normals'), S.attribute(colors, 'colors')
+    vmap = torch.empty((S.N,), dtype=torch.int64, device=dev)
+    counts = S.counts()
+    nbytes = lib().se3_mesh_select_workspace_bytes(S.N, S.M)
+    ws, stream = _mesh_bytes(nbytes, dev), _stream()
+    head = (_dp(S.vertices), _optr(nrm), _optr(col), _dp(S.triangles), _dp(keep), S.voff, S.toff, S.B)
+    check(lib().se3_mesh_select_stack(*head, None, None, None, None, None, None, _dp(vmap), _dp(counts), ws.data_ptr(), nbytes, stream),
+          'se3_mesh_select_stack')
+    rows = S.read(counts, what)
+    vc, tc = [r[1] for r in rows], [r[2] for r in rows]
+    out = [None if x is None else torch.empty((sum(vc), 3), dtype=torch.float64, device=dev) for x in (S.vertices, nrm, col)]
+    tri = torch.empty((sum(tc), 3), dtype=torch.int64, device=dev)
+    check(lib().se3_mesh_select_stack(*head, _i64_array(exclusive_offsets(vc)), _i64_array(exclusive_offsets(tc)), _dp(out[0]), _optr(out[1]),
+                                      _optr(out[2]), _dp(tri), _dp(vmap), _dp(counts), ws.data_ptr(), nbytes, stream), 'se3_mesh_select_stack')
+    return out[0], tri, out[1], out[2], vmap, vc, tc
+
+
+def mesh_normals_stack(meshes, inc=None, normalized=True, triangle_normals=True, vertex_normals=True):
+    """HIP (csrc/mesh_ops.hip): (triangle normals (M, 3), vertex normals (N, 3)) float64, either None when not asked for; the vertex normals
+    gather the incidence rows `inc`.  Without `inc` (whose build checks the triangles) the status words are read here."""
+    S, dev = meshes, meshes.device
+    counts = S.counts() if inc is None and triangle_normals else None
+    if vertex_normals and inc is None:
+        raise RuntimeError('mesh_normals_stack: the vertex normals need the incidence tables')
+    tn = torch.empty((S.M, 3), dtype=torch.float64, device=dev) if triangle_normals else None
+    vn = torch.empty((S.N, 3), dtype=torch.float64, device=dev) if vertex_normals else None
+    check(lib().se3_mesh_normals_stack(_dp(S.vertices), _dp(S.triangles), S.voff, S.toff, S.B, _dp(inc.tri_offsets) if vertex_normals else None,
+                                       _dp(inc.tri_rows) if vertex_normals else None, int(bool(normalized)), _optr(tn), _optr(vn), _optr(counts), _stream()),
+          'se3_mesh_normals_stack')
+    if counts is not None:
+        S.read(counts, 'mesh_normals_stack')
+    return tn, vn
+
+
+def mesh_smooth_stack(meshes, inc, method, iterations, lambda_filter=0.5, mu=-0.53, normals=None, colors=None):
+    """HIP (csrc/mesh_ops.hip): `iterations` iterations of the filter over the neighbour rows of `inc`, every step issued by one call.
+    Returns (vertices, normals, colors) as new tensors (None where none was given)."""
+    what, S, dev = 'mesh_smooth_stack', meshes, meshes.device
+    if method not in MESH_SMOOTH_METHODS:
+        raise ValueError('%s: method %r is none of %s' % (what, method, ', '.join(MESH_SMOOTH_METHODS)))
+    if int(iterations) < 0 or int(iterations) > MESH_OPS_LIMITS['max_iterations']:
+        raise ValueError('%s: %d iterations (0 .. %d)' % (what, iterations, MESH_OPS_LIMITS['max_iterations']))
+    src = [S.vertices, S.attribute(normals, 'normals'), S.attribute(colors, 'colors')]
+    out = [None if x is None else torch.empty_like(x) for x in src]
+    nbytes = lib().se3_mesh_smooth_workspace_bytes(S.N, sum(x is not None for x in src))
+    ws = _mesh_bytes(nbytes, dev)
+    check(lib().se3_mesh_smooth_stack(_dp(src[0]), _optr(src[1]), _optr(src[2]), S.voff, S.B, _dp(inc.nbr_offsets), _dp(inc.nbr_rows),
+                                      MESH_SMOOTH_METHODS[method], int(iterations), float(lambda_filter), float(mu), _dp(out[0]), _optr(out[1]),
+                                      _optr(out[2]), ws.data_ptr(), nbytes, _stream()), 'se3_mesh_smooth_stack')
+    return tuple(out)
+
+
+MESH_CLUSTER_PASSES = {name[len('SE3_MESH_CLUSTER_'):].lower(): value for name, value in ENUMS['se3_mesh_cluster_pass'].items()}
+
+
+def _sorted_rows(columns, cuts):
+    """the stacked rows sorted mesh by mesh by their columns (the first the most significant), equal rows in their order: stable sorts from
+    the last column to the first"""
+    parts = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        o = torch.arange(b - a, device=columns[0].device)
+        for col in reversed(columns):
+            o = o[torch.sort(col[a:b][o], stable=True).indices]
+        parts.append(o + a)
+    return torch.cat(parts) if parts else torch.zeros((0,), dtype=torch.int64, device=columns[0].device)
+
+
+def mesh_cluster_vertices_stack(meshes, voxel_size, normals=None, colors=None):
+    """HIP (csrc/mesh_ops.hip): simplify_vertex_clustering with the mean as contraction: the four passes of se3_mesh_cluster_vertices_stack with
+    the two orders (vertices by cell, triangles by their rotated triple) sorted in between (torch.sort, stable) and one host read of the
+    counts.  Returns (vertices, triangles, normals, colors, vertex_map (N,) int64, vertex_counts, triangle_counts).  ValueError for a voxel
+    size that is not positive and finite, a mesh that is not finite or needs 2^21 cells or more on an axis, a triangle out of range."""
+    what, S, dev = 'mesh_cluster_vertices_stack', meshes, meshes.device
+    vs = float(voxel_size)
+    if not (math.isfinite(vs) and vs > 0.0):
+        raise ValueError('%s: voxel_size %r is not a positive finite number' % (what, voxel_size))
+    nrm, col = S.attribute(normals, 'normals'), S.attribute(colors, 'colors')
+    keys = torch.empty((S.N,), dtype=torch.int64, device=dev)
+    vmap = torch.empty((S.N,), dtype=torch.int64, device=dev)
+    rotated = torch.empty((S.M, 3), dtype=torch.int64, device=dev)
+    counts = S.counts()
+    nbytes = lib().se3_mesh_cluster_vertices_workspace_bytes(S.N, S.M)
+    ws, stream = _mesh_bytes(nbytes, dev), _stream()
+
+    def run(name, sorted_keys=None, vorder=None, torder=None, out=(None,) * 6):
+        check(lib().se3_mesh_cluster_vertices_stack(MESH_CLUSTER_PASSES[name], _dp(S.vertices), _optr(nrm), _optr(col), _dp(S.triangles), S.voff, S.toff, S.B,
+                                                    vs, _dp(keys), _optr(sorted_keys), _optr(vorder), _dp(vmap), _dp(rotated), _optr(torder), out[0], out[1],
+                                                    _optr(out[2]), _optr(out[3]), _optr(out[4]), _optr(out[5]), _dp(counts), ws.data_ptr(), nbytes, stream),
+              'se3_mesh_cluster_vertices_stack')
+    run('keys')
+    vorder = _sorted_rows([keys], list(S.voff)[:S.B + 1])
+    run('vertices', keys[vorder], vorder)
+    torder = _sorted_rows([rotated[:, 0], rotated[:, 1], rotated[:, 2]], list(S.toff)[:S.B + 1])
+    run('triangles', None, None, torder)
+    rows = counts.cpu().tolist()
+    for bit, why in (('nonfinite', 'has a vertex or an attribute that is not finite'), ('too_many_cells', 'needs 2^21 cells or more on an axis: voxel_size is too small')):
+        bad = [b for b, row in enumerate(rows) if row[0] & MESH_OPS_STATUS[bit]]
+        if bad:
+            raise ValueError('%s: mesh %s %s' % (what, ', '.join(map(str, bad)), why))
+    rows = S.read(counts, what)
+    vc, tc = [r[1] for r in rows], [r[2] for r in rows]
+    out = [None if x is None else torch.empty((sum(vc), 3), dtype=torch.float64, device=dev) for x in (S.vertices, nrm, col)]
+    tri = torch.empty((sum(tc), 3), dtype=torch.int64, device=dev)
+    run('write', None, vorder, torder, (_i64_array(exclusive_offsets(vc)), _i64_array(exclusive_offsets(tc)), out[0], out[1], out[2], tri))
+    return out[0], tri, out[1], out[2], vmap, vc, tc
