@@ -44,6 +44,11 @@ extern "C" {
 
 #define SE3_MAX_BATCH 32          /* clouds per stacked call = 16 registration pairs per forward (the reference always stacks 2: ref, src) */
 #define SE3_MAX_NEIGHBOR_LIMIT 64 /* radius search keeps at most this many nearest neighbours */
+/* Counter prefixes of the three workspaces of the conventions above, in bytes.  The prefix holds int32 arrival counters and nothing else: it
+ * is zero before the first use and every completed call leaves it zero.  The rest of such a workspace (partial statistics, split partial
+ * sums) has NO required content: every word of it that a call reads was written earlier in that same call. */
+#define SE3_GN_COUNTER_BYTES 1024          /* se3_dense_norm_fwd, se3_group_norm_stats: 16 segments x 16 column blocks x one int32 */
+#define SE3_KPCONV_SPLIT_COUNTER_BYTES 65536          /* se3_kpconv_so3_fused, split form (both kernels): one int32 per (tile or group, 32 output channels) */
 
 /* Library / build identification. */
 const char* se3_version(void);

@@ -117,11 +117,13 @@ class Derived:
 class Workspace:
     """get(device, stream, nbytes): the grow-only uint8 buffer of ONE purpose on that stream (calls on a stream are ordered: one user at a
     time), at least nbytes long; allocated anew (size: a floor in bytes, or a function of nbytes) when there is none or it is too small.
-    zeroed: zero when first handed out, never cleared again by the cache (its users leave it zero; ops._check_counters after an error)."""
+    zeroed: zero when first handed out, never cleared again by the cache (its users leave it zero; ops._check_counters after an error).
+    counters: the bytes at the start that hold arrival counters -- the only part whose content one call owes the next (zero); no call
+    may depend on what any other byte of a workspace held when it began (tests/hygiene.py poisons them)."""
     weights = False
 
-    def __init__(self, size, zeroed=False):
-        self.buffers, self.size, self.new = {}, size, (torch.zeros if zeroed else torch.empty)
+    def __init__(self, size, zeroed=False, counters=0):
+        self.buffers, self.size, self.new, self.counters = {}, size, (torch.zeros if zeroed else torch.empty), counters
         _registered.add(self)
 
     def get(self, device, stream, nbytes):

@@ -130,6 +130,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 // segment's chunks [cb0, cb1), a butterfly merges the lanes, lanes < channels-per-group write the affine map of their channel.
 constexpr int kGNMaxColumnBlocks = 16;
 constexpr size_t kGNCounterB = kGNMaxSegments * kGNMaxColumnBlocks * sizeof(int);
+static_assert(kGNCounterB == SE3_GN_COUNTER_BYTES, "the counter prefix that include/se3et_hip.h declares");
 __device__ __forceinline__ void gn_store_partial(float* p, const WF& w) {          // read back by another compute unit in the same launch
   __hip_atomic_store(p + 0, w.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(p + 1, w.mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -931,6 +931,7 @@ static int fused_colblocks(int out_channels) {
 // write partial sums over each other's counters; ZERO before the first call, left zero by every call][partial outputs]; 0 = this shape
 // does not split (the workspace may then be NULL).
 constexpr size_t kSplitCounterB = 64 * 1024;
+static_assert(kSplitCounterB == SE3_KPCONV_SPLIT_COUNTER_BYTES, "the counter prefix that include/se3et_hip.h declares");
 extern "C" size_t se3_kpconv_fused_split_workspace_bytes(int64_t num_queries, int in_channels, int out_channels) {
   if (num_queries <= 0 || in_channels % kCC || out_channels % 32) return 0;
   const int64_t tiles = fused_tiles(num_queries);

@@ -824,6 +824,7 @@ int union_colblocks(int out_channels) {
   return NCT % 4 == 0 ? NCT / 4 : NCT % 2 == 0 ? NCT / 2 : NCT;
 }
 constexpr size_t kSplitCounterB = 64 * 1024;
+static_assert(kSplitCounterB == SE3_KPCONV_SPLIT_COUNTER_BYTES, "the counter prefix that include/se3et_hip.h declares");
 
 }  // namespace
 

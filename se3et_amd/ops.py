@@ -656,7 +656,10 @@ _ws_gn, _ws_gn_bwd = Workspace(1 << 22), Workspace(1 << 22)          # GroupNorm
 _ws_attn = Workspace(1 << 22)             # f16 hi / lo pieces of K and V^T of a stack-mode attention call
 _ws_x6, _ws_emb = Workspace(1 << 24), Workspace(1 << 24)          # operand pieces of the equivariant cross attention; records of the embedding kernels
 # ... that begin with arrival counters (in-kernel finalize / split reduction): zero when first used; every call leaves the counters zero
-_ws_dense, _ws_kpconv_split, _ws_kpconv_union_split = (Workspace(1 << 20, zeroed=True) for _ in range(3))
+# (COUNTER_BYTES: the length of that prefix, from include/se3et_hip.h; the bytes behind it have no required content)
+COUNTER_BYTES = {'_ws_dense': CONSTANTS['SE3_GN_COUNTER_BYTES'], '_ws_kpconv_split': CONSTANTS['SE3_KPCONV_SPLIT_COUNTER_BYTES'],
+                 '_ws_kpconv_union_split': CONSTANTS['SE3_KPCONV_SPLIT_COUNTER_BYTES']}
+_ws_dense, _ws_kpconv_split, _ws_kpconv_union_split = (Workspace(1 << 20, zeroed=True, counters=n) for n in COUNTER_BYTES.values())
 
 
 def group_norm_rows(x, weight, bias, groups, eps, leaky_slope, residual, x_bias=None, segments=None):

@@ -72,14 +72,16 @@ def test_limits_are_the_headers_defines():
     from se3et_amd import _lib, cdriver, data, ops
     assert _lib.CONSTANTS == {'SE3_OK': 0, 'SE3_ERR_INVALID_ARG': 1, 'SE3_ERR_UNSUPPORTED': 2, 'SE3_ERR_LAUNCH': 3, 'SE3_ERR_WORKSPACE': 4,
                               'SE3_MAX_BATCH': 32, 'SE3_MAX_NEIGHBOR_LIMIT': 64, 'SE3_MAX_BLOCKS': 16, 'SE3_PAIR_MAX_PAIRS': 32,
-                              'SE3_KNN_MAX': 64,
+                              'SE3_KNN_MAX': 64, 'SE3_GN_COUNTER_BYTES': 1024, 'SE3_KPCONV_SPLIT_COUNTER_BYTES': 65536,
                               # the enumerators of the header's enum block, with the values it spells (ops.ICP_MODES / ICP_STATUS / ICP_MAX_ITERATION)
                               'SE3_ICP_POINT_TO_POINT': 0, 'SE3_ICP_POINT_TO_PLANE': 1, 'SE3_ICP_NONFINITE': 1, 'SE3_ICP_TOO_FEW': 2,
                               'SE3_ICP_SINGULAR': 4, 'SE3_ICP_EMPTY': 8, 'SE3_ICP_STEP_REFUSED': 16, 'SE3_ICP_MAX_ITERATION': 1000}
     assert ops.ICP_MODES == {'point_to_point': 0, 'point_to_plane': 1} and ops.ICP_MAX_ITERATION == 1000
     assert ops.ICP_STATUS == {'nonfinite': 1, 'too_few': 2, 'singular': 4, 'empty': 8, 'step_refused': 16}
     got = {'SE3_MAX_BATCH': data.SE3_MAX_BATCH, 'SE3_MAX_NEIGHBOR_LIMIT': data.SE3_MAX_NEIGHBOR_LIMIT, 'SE3_MAX_BLOCKS': cdriver.MAX_BLOCKS,
-           'SE3_PAIR_MAX_PAIRS': ops.PAIR_MAX_PAIRS, 'SE3_KNN_MAX': ops.KNN_MAX}
+           'SE3_PAIR_MAX_PAIRS': ops.PAIR_MAX_PAIRS, 'SE3_KNN_MAX': ops.KNN_MAX, 'SE3_GN_COUNTER_BYTES': ops.COUNTER_BYTES['_ws_dense'],
+           'SE3_KPCONV_SPLIT_COUNTER_BYTES': ops.COUNTER_BYTES['_ws_kpconv_split']}
+    assert ops.COUNTER_BYTES['_ws_kpconv_union_split'] == ops.COUNTER_BYTES['_ws_kpconv_split'] and len(ops.COUNTER_BYTES) == 3
     for name, value in got.items():
         assert type(value) is int and value == _lib.CONSTANTS[name], name
     assert type(cdriver.MAX_BATCH) is int and cdriver.MAX_BATCH == _lib.CONSTANTS['SE3_MAX_BATCH']
