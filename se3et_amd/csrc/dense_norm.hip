@@ -109,10 +109,17 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
   // the f16 range and COUNTED (se3_debug_dense_saturated_rows): loud instead of Inf; a NaN / Inf input value makes its row's outputs NaN
   // (both pieces NaN), as the reference's matmul would.  A row's scale is a function of that row's values
   // only: rows -- the padding rows of a packed batch included -- do not influence each other.
+  // MODE 3 walks two rows of two tensors per output row, T(x) and x2, whose magnitudes have nothing to do with each other: the row takes a
+  // scale from the first 32 values of EACH (the second at the first K-step of x2), and where the two differ the rescale between the two
+  // products takes the difference out of the accumulators (row_mid).  Each input is held to the headroom of its own scale.
   __shared__ __align__(16) int row_exp[2][TR];                           // per image: exponent - 141 of a scaled row, valid for the tile ending in step ...
   __shared__ __align__(16) int row_exp_step[2][TR];                      // ... row_exp_step (any other tile: 0)
   __shared__ int row_run[TR];                                            // exponent of the rows of the tile being staged (only while a wave is off the plain path)
   __shared__ int row_scl[2];                                             // per image: the step number if some row of the tile ending in it is scaled
+  constexpr int kMidRows = MODE == 3 ? TR : 4;                           // MODE 3: exponent of source 1 - exponent of source 2 of a row whose scale changes
+  __shared__ __align__(16) int row_mid[2][kMidRows];                     // ... at the first K-step of x2, tagged and flagged like row_exp
+  __shared__ __align__(16) int row_mid_step[2][kMidRows];
+  __shared__ int row_mid_scl[2];
   extern __shared__ __align__(16) float aff[];                           // [stage][2][K] of this workgroup's segment
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
@@ -138,6 +145,10 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
     for (int i = tid; i < 2 * K; i += 256) aff[st * 2 * K + i] = a.in_affine[st][(size_t)seg * 2 * K + i];
   if (tid < 2) row_scl[tid] = -1;
   for (int i = tid; i < 2 * TR; i += 256) row_exp_step[0][i] = -1;
+  if constexpr (kDual) {
+    if (tid < 2) row_mid_scl[tid] = -1;
+    for (int i = tid; i < 2 * TR; i += 256) row_mid_step[0][i] = -1;
+  }
   const int nk1 = K >> 5, nk2 = kDual ? (K2 >> 5) : 0, nkt = nk1 + nk2;
   const int ntiles = (int)((r1 - r0 + TR - 1) / TR);
   const int total = ntiles * nkt;
@@ -190,6 +201,8 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
     // here, not multiplied: an Inf / NaN / > 65504 in the neighbouring row would turn 0 * x into NaN.  Uniform condition.)
     const bool tail_mask = kPlain && XS < K && a.seg_steps == 0 && k + 4 > XS;
     const bool first_step = p.kk == 0, last_step = p.kk == nkt - 1;      // (uniform) of the row tile
+    const bool second_start = kDual && p.kk == nk1;                      // (uniform) the first K-step of x2
+    const bool fresh = first_step || second_start;                       // the rows take a scale from this step's 32 values
     auto transformed = [&](const f32x4& raw) {                          // T(v): tail mask, the pending norm stages
       f32x4 t = raw;
       if constexpr (kPlain) {
@@ -220,13 +233,13 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
       const f32x4 t = transformed(v[j]);
       tv[j] = t;
       const float m = fmaxf(fmaxf(__builtin_fabsf(t[0]), __builtin_fabsf(t[1])), fmaxf(__builtin_fabsf(t[2]), __builtin_fabsf(t[3])));
-      odd |= __builtin_amdgcn_ballot_w64(!(m < (first_step ? 128.f : 32768.f)));
+      odd |= __builtin_amdgcn_ballot_w64(!(m < (fresh ? 128.f : 32768.f)));
       // a row = 8 adjacent lanes = one byte of the ballot: the bytes are OR-folded on the scalar unit, a zero byte is a row below 2^-4
       unsigned long long ge = __builtin_amdgcn_ballot_w64(m >= 0.0625f);
       ge |= ge >> 4;
       ge |= ge >> 2;
       ge |= ge >> 1;
-      odd |= first_step ? (~ge & 0x0101010101010101ull) : 0ull;
+      odd |= fresh ? (~ge & 0x0101010101010101ull) : 0ull;
     }
     auto split_store = [&](int j, const f32x4& t) {
       f16x4 hi, lo;
@@ -245,10 +258,12 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
       plain_rows = true;
       return;
     }
+    // (at x2's first step the straight-line path above is open only to a wave whose rows are all at exponent 141 already: the accumulators
+    // of a scaled row have to be moved to its second scale, which is noted below)
     // ---- the exact path: per row the largest magnitude of this K-step -> (first step) the row's scale, (later) the saturation check.  NOT
     // unrolled over the units (the unit is picked with selects): the code of this cold path sits inside the hot loop, and its size alone
     // costs the loop time (measured: the same branch, never taken, with the unrolled body: +5 % on the unary shapes).
-    bool any_scaled = false;
+    bool any_scaled = false, any_moved = false;
     int saturated = 0;
 #pragma unroll 1
     for (int j = 0; j < U; j++) {
@@ -265,11 +280,21 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
       const int e_here = (mb >> 23) & 0xff;                              // biased exponent of the row's largest magnitude in this step
       const int row = urow + 32 * j;
       int e_row;
-      if (first_step)        // plain inside [2^-4, 2^7) (exponents 123 .. 133) and for an all-zero start; else the magnitude goes to [2^6, 2^7)
+      const int e_run = (first_step || plain_rows) ? 141 : row_run[row]; // the scale the row has had so far in this tile
+      if (fresh)             // plain inside [2^-4, 2^7) (exponents 123 .. 133) and for an all-zero start; else the magnitude goes to [2^6, 2^7)
         e_row = ((e_here >= 123 && e_here <= 133) || e_here == 0) ? 141 : (e_here >= 255 ? 141 : min(e_here + 8, 254));
       else
-        e_row = plain_rows ? 141 : row_run[row];
-      if (first_step && q == 0) row_run[row] = e_row;
+        e_row = e_run;
+      if constexpr (kDual) {
+        if (second_start && e_row != e_run) {                            // the accumulators hold source 1 at 2^(141 - e_run): -> 2^(141 - e_row)
+          if (q == 0) {
+            row_mid[buf][row] = e_run - e_row;
+            row_mid_step[buf][row] = p.tile * nkt + p.kk;
+          }
+          any_moved = true;
+        }
+      }
+      if (fresh && q == 0) row_run[row] = e_row;                         // (behind the read above: the row's 8 lanes run in one wave)
       const bool sat = e_here > e_row;                                   // beyond the row's headroom (NaN / Inf: 255)
       f16x4 hi, lo;
 #pragma unroll
@@ -293,6 +318,9 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
     const bool w_scaled = __builtin_amdgcn_ballot_w64(any_scaled) != 0;
     plain_rows = !w_scaled;
     if (last_step && w_scaled && lane == 0) row_scl[buf] = p.tile * nkt + p.kk;      // (every writer stores the same number)
+    if constexpr (kDual) {
+      if (__builtin_amdgcn_ballot_w64(any_moved) != 0 && lane == 0) row_mid_scl[buf] = p.tile * nkt + p.kk;
+    }
     if (saturated) atomicAdd(&g_dense_saturated_rows, (unsigned long long)saturated);
   };
   const int a_read = (wm * (RT * 32) + i32) * kRowB + h * 16;           // + rt * 32 * kRowB + ks * 32 + piece * kPieceB
@@ -369,6 +397,24 @@ __global__ __launch_bounds__(256, MODE == 3 ? 2 : 3) void dense_norm_kernel(cons
   auto multiply = [&](int buf, const StepPos& p, u32x4 (&bq)[2][CT][2]) {
     if constexpr (kDual) {
       if (p.kk == nk1) {                                                 // between the two products: S1 G1 -> S2 G1 a1 / a2
+        if (__builtin_expect(row_mid_scl[buf] == p.tile * nkt + p.kk, 0)) {
+          // rows whose scale changes between T(x) and x2: the accumulators go from the first scale to the second (exact, as at the tile's end)
+          const int step_id = p.tile * nkt + p.kk;
+#pragma unroll
+          for (int r = 0; r < RT; r++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+              const int base = (wm * RT + r) * 32 + 8 * g + 4 * h;
+              const i32x4 tag = *reinterpret_cast<const i32x4*>(&row_mid_step[buf][base]);
+              const i32x4 ex = *reinterpret_cast<const i32x4*>(&row_mid[buf][base]);
+#pragma unroll
+              for (int j = 0; j < 4; j++) {
+                const int ev = tag[j] == step_id ? ex[j] : 0;
+#pragma unroll
+                for (int c = 0; c < CT; c++) acc[r][c][4 * g + j] = __builtin_ldexpf(acc[r][c][4 * g + j], ev);
+              }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RT; r++)
 #pragma unroll
