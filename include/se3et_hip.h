@@ -1760,6 +1760,75 @@ int se3_debug_mesh_normals_host(const double* vertices, const int64_t* triangles
 int se3_debug_mesh_smooth_host(const double* values, int64_t n, const int64_t* nbr_row_offsets, const int* nbr_rows, int method, int iterations,
                                double lambda, double mu, double* out_values);
 
+/* ---- ray casting and closest points on stacked triangle meshes (csrc/mesh_query.hip, csrc/mesh_query_core.h) ----------------------------------------
+ * Open3D's RaycastingScene (cast_rays, test_occlusions, compute_closest_points, compute_distance) and a depth rendering for up to
+ * SE3_PAIR_MAX_PAIRS meshes per call, float64, over a bounding volume hierarchy built on the device; the contract is the header comment
+ * of csrc/mesh_query.hip.  The meshes are stacked as for the mesh post-processing above.  nodes: 2 max(M, 1) nodes of
+ * SE3_MESH_QUERY_NODE_BYTES bytes; counts (B, SE3_MESH_OPS_COUNT_WORDS) int64 on the device: status (SE3_MESH_OPS_BAD_TRIANGLE,
+ * SE3_MESH_QUERY_NONFINITE_VERTEX), live triangles, zero-area triangles, root.  Everything on the DEVICE unless an entry is called _host.
+ *   se3_mesh_bvh_stack      two passes over one workspace (se3_mesh_bvh_workspace_bytes(M)) and one counts array.  SE3_MESH_BVH_KEYS: keys (M)
+ *                           int64, a live triangle's 63-bit Morton key, -1 for an inert one, and the first three count words.
+ *                           SE3_MESH_BVH_TREE: sorted_keys and order (M) int64, the stacked triangle rows sorted per mesh by (key < 0, key,
+ *                           row); writes the nodes and each mesh's root.
+ *   se3_mesh_cast_rays_stack   rays (R, 6) float64 origin and direction, ray_meshes (R) ints (outside [0, B): a miss); out_t (R) float64,
+ *                           out_ids (R) int64, out_uvs (R, 2), out_normals (R, 3), each NULL or whole.  any_hit: only out_hit (R) bytes is
+ *                           written and a ray's walk ends at its first hit.
+ *   se3_mesh_render_stack   views (F, SE3_RAYCAST_VIEW_WORDS) float64 as se3_tsdf_raycast_stack takes them, view_meshes (F) ints; out_depth
+ *                           (F, H, W) float32, out_points and out_normals (F, H, W, 3) float64, out_primitive_ids (F, H, W) int64, out_mask
+ *                           (F, H, W) bytes, each NULL or whole; a pixel without a hit holds 0, NaN, NaN, -1, 0.
+ *   se3_mesh_closest_points_stack   queries (Q, 3) float64, query_meshes (Q) ints; out_points (Q, 3), out_distances (Q), out_ids (Q) int64,
+ *                           out_uvs (Q, 2), out_normals (Q, 3), each NULL or whole.
+ *   se3_debug_mesh_bvh_host   the same two passes on HOST memory, serially, one mesh: order (m) holds the triangle of every sorted place.
+ *   se3_debug_mesh_cast_rays_host / _closest_points_host / _render_host   BRUTE FORCE over every triangle on HOST memory, one mesh: no tree.
+ *   se3_debug_mesh_walk_rays_host / _walk_points_host   the kernels' walk over a tree of se3_debug_mesh_bvh_host, on HOST memory. */
+enum se3_mesh_query_limit {            /* (NAMED) */
+  SE3_MESH_QUERY_NODE_BYTES = 64,      /* bytes of a node: six float64 bounds, two children, the parent, padding */
+  SE3_MESH_QUERY_KEY_BITS = 21,        /* bits of a Morton key per axis */
+  SE3_MESH_QUERY_MAX_DEPTH = 94,       /* inner nodes on a path from the root at most: 63 key bits + 31 position bits */
+  SE3_MESH_QUERY_TRAIL_BITS = 128      /* levels that the walk can remember */
+};
+enum se3_mesh_query_status {           /* (NAMED) a bit of the status word beside those of se3_mesh_ops_status */
+  SE3_MESH_QUERY_NONFINITE_VERTEX = 8  /* a triangle has a vertex that is not finite */
+};
+enum se3_mesh_bvh_pass {               /* (NAMED) */
+  SE3_MESH_BVH_KEYS = 0,
+  SE3_MESH_BVH_TREE = 1
+};
+size_t se3_mesh_bvh_workspace_bytes(int64_t m_total);
+int se3_mesh_bvh_stack(int pass, const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                       const int64_t* triangle_offsets_host, int num_meshes, int64_t* keys, const int64_t* sorted_keys, const int64_t* order,
+                       void* out_nodes, int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int se3_mesh_cast_rays_stack(const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                             const int64_t* triangle_offsets_host, int num_meshes, const void* nodes, const int64_t* tree_counts,
+                             const double* rays, const int* ray_meshes, int64_t num_rays, double t_min, double t_max, int any_hit,
+                             double* out_t, int64_t* out_ids, double* out_uvs, double* out_normals, uint8_t* out_hit, void* stream);
+int se3_mesh_render_stack(const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                          const int64_t* triangle_offsets_host, int num_meshes, const void* nodes, const int64_t* tree_counts,
+                          const double* views, const int* view_meshes, int64_t num_views, int height, int width, double depth_min,
+                          double depth_max, float* out_depth, double* out_points, double* out_normals, int64_t* out_primitive_ids,
+                          uint8_t* out_mask, void* stream);
+int se3_mesh_closest_points_stack(const double* vertices, const int64_t* triangles, const int64_t* vertex_offsets_host,
+                                  const int64_t* triangle_offsets_host, int num_meshes, const void* nodes, const int64_t* tree_counts,
+                                  const double* queries, const int* query_meshes, int64_t num_queries, double* out_points,
+                                  double* out_distances, int64_t* out_ids, double* out_uvs, double* out_normals, void* stream);
+int se3_debug_mesh_bvh_host(int pass, const double* vertices, const int64_t* triangles, int64_t n, int64_t m, int64_t* keys,
+                            const int64_t* sorted_keys, const int64_t* order, void* out_nodes, int64_t* out_counts);
+int se3_debug_mesh_cast_rays_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const double* rays, int64_t num_rays,
+                                  double t_min, double t_max, int any_hit, double* out_t, int64_t* out_ids, double* out_uvs,
+                                  double* out_normals, uint8_t* out_hit);
+int se3_debug_mesh_closest_points_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const double* queries,
+                                       int64_t num_queries, double* out_points, double* out_distances, int64_t* out_ids, double* out_uvs,
+                                       double* out_normals);
+int se3_debug_mesh_walk_rays_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const void* nodes, int64_t root,
+                                  const double* rays, int64_t num_rays, double t_min, double t_max, int any_hit, double* out_t,
+                                  int64_t* out_ids, double* out_uvs, double* out_normals, uint8_t* out_hit);
+int se3_debug_mesh_walk_points_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const void* nodes, int64_t root,
+                                    const double* queries, int64_t num_queries, double* out_points, double* out_distances, int64_t* out_ids,
+                                    double* out_uvs, double* out_normals);
+int se3_debug_mesh_render_host(const double* vertices, const int64_t* triangles, int64_t n, int64_t m, const double* views, int64_t num_views,
+                               int height, int width, double depth_min, double depth_max, float* out_depth, double* out_points,
+                               double* out_normals, int64_t* out_primitive_ids, uint8_t* out_mask);
+
 #ifdef __cplusplus
 }
 #endif

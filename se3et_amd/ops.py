@@ -3500,6 +3500,9 @@ class StackedMeshes:
         bad = [b for b, row in enumerate(rows) if row[0] & MESH_OPS_STATUS['bad_triangle']]
         if bad:
             raise ValueError('%s: a triangle of mesh %s names a vertex outside [0, n) of its mesh' % (what, ', '.join(map(str, bad))))
+        bad = [b for b, row in enumerate(rows) if row[0] & MESH_QUERY_STATUS['nonfinite_vertex']]          # (set by csrc/mesh_query.hip alone)
+        if bad:
+            raise ValueError('%s: a triangle of mesh %s has a vertex that is not finite' % (what, ', '.join(map(str, bad))))
         return rows
 
 
@@ -3673,3 +3676,113 @@ def mesh_cluster_vertices_stack(meshes, voxel_size, normals=None, colors=None):
     tri = torch.empty((sum(tc), 3), dtype=torch.int64, device=dev)
     run('write', None, vorder, torder, (_i64_array(exclusive_offsets(vc)), _i64_array(exclusive_offsets(tc)), out[0], out[1], out[2], tri))
     return out[0], tri, out[1], out[2], vmap, vc, tc
+
+
+# ---- ray casting and closest points on stacked triangle meshes (csrc/mesh_query.hip) -------------------------------------------------------------------
+MESH_QUERY_LIMITS = {name[len('SE3_MESH_QUERY_'):].lower(): value for name, value in ENUMS['se3_mesh_query_limit'].items()}
+MESH_QUERY_STATUS = {name[len('SE3_MESH_QUERY_'):].lower(): value for name, value in ENUMS['se3_mesh_query_status'].items()}
+MESH_BVH_PASSES = {name[len('SE3_MESH_BVH_'):].lower(): value for name, value in ENUMS['se3_mesh_bvh_pass'].items()}
+MESH_RENDER_MAPS = {'depth': (torch.float32, ()), 'points': (torch.float64, (3,)), 'normals': (torch.float64, (3,)), 'primitive_ids': (torch.int64, ()),
+                    'mask': (torch.bool, ())}
+
+
+class MeshBVH:
+    """The trees of mesh_bvh_stack over the stacked `meshes`: nodes (2 max(M, 1), MESH_QUERY_LIMITS['node_bytes']) uint8, counts (B, 4) int64 on
+    the device (status, live triangles, zero-area triangles, root), and the host's copy of the live and zero-area counts."""
+
+
+def mesh_bvh_stack(meshes, strict=True):
+    """HIP (csrc/mesh_query.hip): the bounding volume hierarchies of the stacked meshes: the key pass, one stable sort per mesh by
+    (key < 0, key) (torch.sort), the tree pass, one host read of the counts.  ValueError for a triangle out of range or not finite
+    (strict=False: no error, the status words stay in .status and the inert triangles are in no tree)."""
+    what, S, dev = 'mesh_bvh_stack', meshes, meshes.device
+    bvh = MeshBVH()
+    bvh.meshes = S
+    bvh.nodes = torch.empty((2 * max(S.M, 1), MESH_QUERY_LIMITS['node_bytes']), dtype=torch.uint8, device=dev)
+    bvh.counts = S.counts()
+    keys = torch.empty((S.M,), dtype=torch.int64, device=dev)
+    nbytes = lib().se3_mesh_bvh_workspace_bytes(S.M)
+    ws, stream = _mesh_bytes(nbytes, dev), _stream()
+    head = (_dp(S.vertices), _dp(S.triangles), S.voff, S.toff, S.B)
+    check(lib().se3_mesh_bvh_stack(MESH_BVH_PASSES['keys'], *head, _dp(keys), None, None, None, _dp(bvh.counts), ws.data_ptr(), nbytes, stream),
+          'se3_mesh_bvh_stack')
+    order = _sorted_rows([(keys < 0).to(torch.int64), keys], list(S.toff)[:S.B + 1])
+    sorted_keys = keys[order]
+    check(lib().se3_mesh_bvh_stack(MESH_BVH_PASSES['tree'], *head, None, _dp(sorted_keys), _dp(order), bvh.nodes.data_ptr(), _dp(bvh.counts),
+                                   ws.data_ptr(), nbytes, stream), 'se3_mesh_bvh_stack')
+    rows = S.read(bvh.counts, what) if strict else bvh.counts.cpu().tolist()
+    bvh.status, bvh.live, bvh.zero_area = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+    return bvh
+
+
+def _query_rows(x, owners, cols, name, what, dev):
+    x, o = _req(x, torch.float64, name, 2), _req(owners, torch.int32, name + ' meshes', 1)
+    if x.shape[1] != cols or o.shape[0] != x.shape[0] or x.device != dev or o.device != dev:
+        raise RuntimeError('%s: %s (R, %d) float64 and their meshes (R,) int32 on %s expected' % (what, name, cols, dev))
+    return x, o, int(x.shape[0])
+
+
+def _bvh_head(bvh):
+    S = bvh.meshes
+    return (_dp(S.vertices), _dp(S.triangles), S.voff, S.toff, S.B, bvh.nodes.data_ptr(), _dp(bvh.counts))
+
+
+def mesh_cast_rays_stack(bvh, rays, ray_meshes, t_min=0.0, t_max=math.inf, any_hit=False):
+    """HIP (csrc/mesh_query.hip): rays (R, 6) float64 origin and direction against the mesh ray_meshes (R,) int32 names (outside [0, B): a
+    miss).  Returns {'t_hit' (R,) float64, inf on a miss; 'primitive_ids' (R,) int64, -1; 'primitive_uvs' (R, 2); 'primitive_normals'
+    (R, 3)}, or with any_hit the hit flags (R,) bool alone: the walk of a ray ends at its first hit."""
+    what, dev = 'mesh_cast_rays_stack', bvh.meshes.device
+    r, o, R = _query_rows(rays, ray_meshes, 6, 'rays', what, dev)
+    if math.isnan(float(t_min)) or math.isnan(float(t_max)):
+        raise ValueError('%s: t_min %r, t_max %r' % (what, t_min, t_max))
+    if any_hit:
+        hit = torch.empty((R,), dtype=torch.uint8, device=dev)
+        outs = (None, None, None, None, _dp(hit))
+    else:
+        out = {'t_hit': torch.empty((R,), dtype=torch.float64, device=dev), 'primitive_ids': torch.empty((R,), dtype=torch.int64, device=dev),
+               'primitive_uvs': torch.empty((R, 2), dtype=torch.float64, device=dev),
+               'primitive_normals': torch.empty((R, 3), dtype=torch.float64, device=dev)}
+        outs = tuple(_dp(x) for x in out.values()) + (None,)
+    check(lib().se3_mesh_cast_rays_stack(*_bvh_head(bvh), _dp(r), _dp(o), R, float(t_min), float(t_max), int(bool(any_hit)), *outs, _stream()),
+          'se3_mesh_cast_rays_stack')
+    return hit.to(torch.bool) if any_hit else out
+
+
+def mesh_closest_points_stack(bvh, queries, query_meshes):
+    """HIP (csrc/mesh_query.hip): the closest point of mesh query_meshes (Q,) int32 to every row of queries (Q, 3) float64.  Returns {'points'
+    (Q, 3), 'distances' (Q,), 'primitive_ids' (Q,) int64, 'primitive_uvs' (Q, 2), 'primitive_normals' (Q, 3)}; a mesh without a live
+    triangle answers inf and -1, a query point that is not finite NaN and -1."""
+    what, dev = 'mesh_closest_points_stack', bvh.meshes.device
+    q, o, Q = _query_rows(queries, query_meshes, 3, 'queries', what, dev)
+    out = {'points': torch.empty((Q, 3), dtype=torch.float64, device=dev), 'distances': torch.empty((Q,), dtype=torch.float64, device=dev),
+           'primitive_ids': torch.empty((Q,), dtype=torch.int64, device=dev), 'primitive_uvs': torch.empty((Q, 2), dtype=torch.float64, device=dev),
+           'primitive_normals': torch.empty((Q, 3), dtype=torch.float64, device=dev)}
+    check(lib().se3_mesh_closest_points_stack(*_bvh_head(bvh), _dp(q), _dp(o), Q, *(_dp(x) for x in out.values()), _stream()),
+          'se3_mesh_closest_points_stack')
+    return out
+
+
+def mesh_render_outputs(maps, F, H, W, dev):
+    """The maps of a rendering, uninitialised: the kernel writes every pixel of every map."""
+    return {name: torch.empty((F, H, W) + MESH_RENDER_MAPS[name][1], dtype=MESH_RENDER_MAPS[name][0], device=dev) for name in maps}
+
+
+def mesh_render_stack(bvh, views, view_meshes, out, height, width, depth_min=0.1, depth_max=3.0):
+    """HIP (csrc/mesh_query.hip): the meshes seen from the views of tsdf_raycast_stack (F, RAYCAST_LIMITS['view_words']) float64, view_meshes
+    (F,) int32 on the device, into the maps of `out` (mesh_render_outputs of any of MESH_RENDER_MAPS), in place."""
+    what, dev = 'mesh_render_stack', bvh.meshes.device
+    v, vm = _req(views, torch.float64, 'views', 2), _req(view_meshes, torch.int32, 'view_meshes', 1)
+    F, H, W = int(v.shape[0]), int(height), int(width)
+    if tuple(v.shape) != (F, RAYCAST_LIMITS['view_words']) or vm.shape[0] != F or v.device != dev or vm.device != dev:
+        raise RuntimeError('%s: views (F, %d) float64 and view_meshes (F,) int32 on %s expected' % (what, RAYCAST_LIMITS['view_words'], dev))
+    if set(out) - set(MESH_RENDER_MAPS):
+        raise RuntimeError('%s: maps %s are not among %s' % (what, sorted(set(out) - set(MESH_RENDER_MAPS)), ', '.join(MESH_RENDER_MAPS)))
+    ptrs = []
+    for name, (dtype, tail) in MESH_RENDER_MAPS.items():
+        t = out.get(name)
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (F, H, W) + tail or t.device != dev or not t.is_contiguous()):
+            raise RuntimeError('%s: map %r must be %s %s on %s, contiguous' % (what, name, (F, H, W) + tail, dtype, dev))
+        ptrs.append(None if t is None else _dp(t))
+    check(lib().se3_mesh_render_stack(*_bvh_head(bvh), _dp(v), _dp(vm), F, H, W, float(depth_min), float(depth_max), *ptrs, _stream()),
+          'se3_mesh_render_stack')
+    return out
