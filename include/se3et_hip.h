@@ -829,6 +829,7 @@ int se3_vgtk_initial_anchor_query(const float* centers, const float* xyz, const 
  * edge cases; float sums are gathers in a fixed order (the reference scatters with atomicAdd), errors come back as status codes, every
  * launch takes a stream.  Called from se3et_amd/vgtk.py (mirror of vgtk/spconv/functional.py, vgtk/pc/sample.py).
  *   gather_points: out[b, c, j] = points[b, c, idx[b, j]]; backward scatter-adds in ascending j           (gathering_cuda_kernel.cu:42-98)
+ *     (num_indices == 0: idx and the (b, c, 0) tensor may be NULL; the backward then writes an all-zero gradient)
  *   ball_query: the first nsample support indices (ascending) within `radius` of each query, a short list repeats itself, a list short
  *     by exactly one keeps a trailing 0, an empty one is all 0                                            (grouping_cuda_kernel.cu:52-99)
  *   furthest_point_sampling: idxs[b, 0] = 0, then iteratively the point furthest from the chosen set; points with |p|^2 <= 1e-3 are

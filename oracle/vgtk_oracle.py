@@ -3,7 +3,10 @@
 Only tests/ may import this.  numpy loops, small cases only.  The kernels that DO have an importable twin
 (vgtk/spconv/functional.py:373-399 inter_zpconv_grouping_naive; gather = torch.gather) are pinned by fixtures generated from the
 genuine reference (tests/golden/vgtk_ops.npz); the three below restate the .cu sources -- the reference holds no test for them:
-'parity unpinned' beyond the sources for ball_query, furthest_point_sampling, the intra convolution and the two anchor queries."""
+'parity unpinned' beyond the sources for ball_query, furthest_point_sampling, the intra convolution and the two anchor queries.
+A second, independent statement of every operation (float64 / integer twins, furthest point sampling as the reference's literal
+reduction tree) is tests/vgtk_twin.py; tests/test_vgtk_twin_cpu.py holds the two to each other and to the fixture on crafted edge cases,
+tests/test_gpu_vgtk_edges.py holds the kernels to the twins."""
 import math
 
 import numpy as np
@@ -30,9 +33,14 @@ def ball_query(new_xyz, xyz, radius, nsample):
 
 def furthest_point_sampling(dataset, m):
     """grouping_cuda_kernel.cu:337-452 including the block-reduction tie order (thread t of bs = 2^floor(log2 n) <= 1024 threads scans
-    k = t, t + bs, ... keeping its first maximum; the tree keeps the lower thread on equal distances).  dataset (b, 3, n)."""
+    k = t, t + bs, ... keeping its first maximum; the tree folds slot t + s into slot t at strides s = bs / 2 .. 1 and keeps slot t on
+    equal distances, so among tied threads the smallest BIT-REVERSED thread number wins: the last stride prefers even threads, the one
+    before it t mod 4 = 0 over 2, ...).  The same selection key as csrc/vgtk_ops.hip; tests/vgtk_twin.py runs the literal tree and
+    tests/test_vgtk_twin_cpu.py holds this key to it.  dataset (b, 3, n)."""
     b, _, n = dataset.shape
     bs = max(min(1 << int(math.log(float(n)) / math.log(2.0)), 1024), 1)
+    bits = bs.bit_length() - 1
+    rev = lambda t: int(format(t, '0%db' % bits)[::-1], 2) if bits else 0
     out = np.zeros((b, m), np.int32)
     x = dataset.astype(np.float32)
     for bi in range(b):
@@ -48,7 +56,7 @@ def furthest_point_sampling(dataset, m):
             if len(cand):
                 top = temp[cand].max()
                 ties = cand[temp[cand] == top]
-                k = min(ties, key=lambda kk: (kk % bs, kk))
+                k = min(ties, key=lambda kk: (rev(kk % bs), kk))
                 best = (float(top), int(k % bs), int(k))
             old = best[2] if best[0] >= 0 else 0
             out[bi, j] = old

@@ -27,15 +27,19 @@ __global__ void gather_points_fwd_kernel(const float* __restrict__ points, const
 // grad_points[b, c, i] = sum_{j: idx[b, j] = i} grad_out[b, c, j], summed in ascending j (the reference scatters with atomicAdd: arrival order).
 // Gather form, no atomics, no workspace: a workgroup owns 64 target points of one batch element; every thread (target, channel group) scans
 // the index list -- staged through LDS in chunks, read as broadcasts -- and adds the matching columns of its channels as it meets them.
+// Uniform passes: the number of passes over the index list depends on c alone, never on the wave, so all four waves reach every barrier
+// and all 256 threads stage every chunk; a wave whose channels lie past c in the last pass stages and scans with nothing to add or store.
 constexpr int kGatherChunk = 2048;
 __global__ __launch_bounds__(256) void gather_points_bwd_kernel(const float* __restrict__ grad_out, const int* __restrict__ idx, int c, int n,
                                                                 int m, float* __restrict__ grad_points) {
   __shared__ int sidx[kGatherChunk];
-  const int b = blockIdx.y, i = blockIdx.x * 64 + (threadIdx.x & 63), cg = threadIdx.x >> 6;       // 4 channel groups
+  const int b = blockIdx.y, i = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int cg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // 4 channel groups, one per wave: the channel guards are scalar
   const int* ib = idx + (int64_t)b * m;
   const float* go = grad_out + (int64_t)b * c * m;
   // channels cg, cg + 4, ...: up to 8 running sums in registers per pass over the indices
-  for (int c0 = cg; c0 < c; c0 += 32) {
+  for (int p = 0; 32 * p < c; p++) {
+    const int c0 = 32 * p + cg;
     float acc[8];
 #pragma unroll
     for (int u = 0; u < 8; u++) acc[u] = 0.f;
@@ -153,9 +157,12 @@ __global__ void ball_query_kernel(const float* __restrict__ new_xyz, const float
 
 // ---- furthest point sampling ----------------------------------------------------------------------------------------------------------
 // One workgroup per cloud.  The reference's result depends on its reduction shape on exact distance ties: thread t of `bs` threads
-// (bs = 2^floor(log2 n), at most 1024) scans k = t, t + bs, ... keeping the FIRST maximum, the tree keeps the lower thread on ties.
-// Equivalent selection key, used here with any workgroup size: (distance descending, k mod bs ascending, k ascending).
-struct FpsBest { float d; int t; int k; };
+// (bs = 2^floor(log2 n), at most 1024) scans k = t, t + bs, ... keeping the FIRST maximum; the tree folds slot t + s into slot t at
+// strides s = bs/2 ... 1 and keeps slot t on ties.  The last stride decides between even and odd threads, the one before between
+// t mod 4 = 0 and 2, ...: among tied threads the one with the smallest BIT-REVERSED number wins (threads 1 and 2 tied: 2 wins).
+// Equivalent selection key, used here with any workgroup size: (distance descending, bit-reversed (k mod bs) ascending, k ascending);
+// t holds the 32-bit reversal, which orders like the log2(bs)-bit one.  tests/vgtk_twin.py runs the literal tree.
+struct FpsBest { float d; unsigned t; int k; };
 __device__ __forceinline__ bool fps_better(const FpsBest& a, const FpsBest& b) {      // a strictly preferred over b
   if (a.d != b.d) return a.d > b.d;
   if (a.t != b.t) return a.t < b.t;
@@ -176,21 +183,20 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ dat
   __syncthreads();
   for (int j = 1; j < m; j++) {
     const float x1 = x[old], y1 = x[n + old], z1 = x[2 * n + old];
-    FpsBest best = {-1.f, 0, 0};            // the reference starts every thread at (best = -1, besti = 0)
-    best.t = 1 << 30;
+    FpsBest best = {-1.f, 0xffffffffu, 0};  // the reference starts every thread at (best = -1, besti = 0)
     for (int k = tid; k < n; k += blockDim.x) {
       const float x2 = x[k], y2 = x[n + k], z2 = x[2 * n + k];
       if (x2 * x2 + y2 * y2 + z2 * z2 <= 1e-3f) continue;
       const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
       const float d2 = fminf(dx * dx + dy * dy + dz * dz, tp[k]);
       tp[k] = d2;
-      const FpsBest c = {d2, k % bs, k};
+      const FpsBest c = {d2, __brev((unsigned)(k & (bs - 1))), k};
       if (fps_better(c, best)) best = c;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       FpsBest c;
-      c.d = __shfl_xor(best.d, o); c.t = __shfl_xor(best.t, o); c.k = __shfl_xor(best.k, o);
+      c.d = __shfl_xor(best.d, o); c.t = (unsigned)__shfl_xor((int)best.t, o); c.k = __shfl_xor(best.k, o);
       if (fps_better(c, best)) best = c;
     }
     if (lane == 0) red[wave] = best;
@@ -328,7 +334,7 @@ __global__ void intra_zpconv_bwd_kernel(const int* __restrict__ nbr, const float
 
 extern "C" int se3_vgtk_gather_points_fwd(const float* points, const int32_t* idx, int batch, int channels, int num_points,
                                           int num_indices, float* out, void* stream) {
-  SE3_REQUIRE(points && idx && out, SE3_ERR_INVALID_ARG, "vgtk_gather_points_fwd: null pointer");
+  SE3_REQUIRE(points && ((idx && out) || num_indices == 0), SE3_ERR_INVALID_ARG, "vgtk_gather_points_fwd: null pointer");       // (no indices: nothing to read)
   SE3_REQUIRE(batch >= 1 && channels >= 1 && num_points >= 1 && num_indices >= 0, SE3_ERR_INVALID_ARG, "vgtk_gather_points_fwd: bad sizes");
   if (num_indices == 0) return SE3_OK;
   const dim3 grid((unsigned)se3_cdiv((int64_t)channels * num_indices, 256), (unsigned)batch);
@@ -339,7 +345,7 @@ extern "C" int se3_vgtk_gather_points_fwd(const float* points, const int32_t* id
 
 extern "C" int se3_vgtk_gather_points_bwd(const float* grad_out, const int32_t* idx, int batch, int channels, int num_points,
                                           int num_indices, float* grad_points, void* stream) {
-  SE3_REQUIRE(grad_out && idx && grad_points, SE3_ERR_INVALID_ARG, "vgtk_gather_points_bwd: null pointer");
+  SE3_REQUIRE(((grad_out && idx) || num_indices == 0) && grad_points, SE3_ERR_INVALID_ARG, "vgtk_gather_points_bwd: null pointer");
   SE3_REQUIRE(batch >= 1 && channels >= 1 && num_points >= 1 && num_indices >= 0, SE3_ERR_INVALID_ARG, "vgtk_gather_points_bwd: bad sizes");
   gather_points_bwd_kernel<<<dim3((unsigned)se3_cdiv(num_points, 64), (unsigned)batch), 256, 0, (hipStream_t)stream>>>(
       grad_out, idx, channels, num_points, num_indices, grad_points);
@@ -362,7 +368,8 @@ extern "C" int se3_vgtk_anchor_query(const float* grouped_xyz, const float* anch
 extern "C" int se3_vgtk_initial_anchor_query(const float* centers, const float* xyz, const float* kernel_points, int batch, int num_centers,
                                              int num_points, int num_anchors, int kernel_size, float radius, float sigma,
                                              float* anchor_weights, float* anchor_counts, void* stream) {
-  SE3_REQUIRE(centers && xyz && kernel_points && anchor_weights && anchor_counts, SE3_ERR_INVALID_ARG, "vgtk_initial_anchor_query: null pointer");
+  SE3_REQUIRE(centers && (xyz || num_points == 0) && kernel_points && anchor_weights && anchor_counts, SE3_ERR_INVALID_ARG,
+              "vgtk_initial_anchor_query: null pointer");
   SE3_REQUIRE(batch >= 1 && num_centers >= 1 && num_points >= 0 && num_anchors >= 1 && kernel_size >= 1, SE3_ERR_INVALID_ARG,
               "vgtk_initial_anchor_query: bad sizes");
   const dim3 grid((unsigned)se3_cdiv((int64_t)kernel_size * num_centers * num_anchors, 256), (unsigned)batch);
@@ -420,6 +427,8 @@ extern "C" int se3_vgtk_inter_zpconv_bwd(const int32_t* neighbors, const float* 
                                          int num_support, int num_anchors, int kernel_size, int num_nn, int channels, float* grad_feats,
                                          void* workspace, size_t workspace_bytes, void* stream) {
   SE3_REQUIRE(neighbors && weights && grad_out && grad_feats && workspace, SE3_ERR_INVALID_ARG, "vgtk_inter_zpconv_bwd: null pointer");
+  SE3_REQUIRE(batch >= 1 && num_samples >= 1 && num_support >= 1 && num_anchors >= 1 && kernel_size >= 1 && num_nn >= 1 && channels >= 1,
+              SE3_ERR_INVALID_ARG, "vgtk_inter_zpconv_bwd: bad sizes");
   SE3_REQUIRE(workspace_bytes >= se3_vgtk_inter_zpconv_bwd_workspace_bytes(batch, num_samples, num_support, num_anchors, kernel_size, num_nn),
               SE3_ERR_INVALID_ARG, "vgtk_inter_zpconv_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;

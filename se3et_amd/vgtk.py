@@ -31,6 +31,8 @@ def gather_points(points, idx):
     points, idx = _req(points.contiguous(), torch.float32, 'points', 3), _req(idx.contiguous(), torch.int32, 'idx', 2)
     b, c, n = points.shape
     m = idx.shape[1]
+    if idx.shape[0] != b:
+        raise RuntimeError('gather_points: points (b, c, n) and idx (b, m) disagree on b: %s, %s' % (tuple(points.shape), tuple(idx.shape)))
     out = torch.empty((b, c, m), dtype=torch.float32, device=points.device)
     check(lib().se3_vgtk_gather_points_fwd(points.data_ptr(), idx.data_ptr(), b, c, n, m, out.data_ptr(), _stream()), 'se3_vgtk_gather_points_fwd')
     return out
@@ -48,6 +50,8 @@ class Gathering(torch.autograd.Function):
         idx, = ctx.saved_tensors
         g = _req(grad_out.contiguous(), torch.float32, 'grad_out', 3)
         b, c, m = g.shape
+        if tuple(idx.shape) != (b, m):
+            raise RuntimeError('Gathering.backward: grad_out %s does not fit idx %s' % (tuple(g.shape), tuple(idx.shape)))
         grad = torch.empty((b, c, ctx.n), dtype=torch.float32, device=g.device)
         check(lib().se3_vgtk_gather_points_bwd(g.data_ptr(), idx.data_ptr(), b, c, ctx.n, m, grad.data_ptr(), _stream()), 'se3_vgtk_gather_points_bwd')
         return grad, None
@@ -117,6 +121,9 @@ class InterZPConvGrouping(torch.autograd.Function):
         f = _req(feats.contiguous(), torch.float32, 'feats', 4)
         b, np_, na, ks, ann = idx.shape
         c, nq = f.shape[1], f.shape[2]
+        if w.shape != idx.shape or f.shape[0] != b or f.shape[3] != na:
+            raise RuntimeError('inter_zpconv_grouping: inter_idx, inter_w (b, np, na, ks, ann) and feats (b, c, nq, na) disagree: %s, %s, %s'
+                               % (tuple(idx.shape), tuple(w.shape), tuple(f.shape)))
         out = torch.empty((b, c, ks, np_, na), dtype=torch.float32, device=f.device)
         check(lib().se3_vgtk_inter_zpconv_fwd(idx.data_ptr(), w.data_ptr(), f.data_ptr(), b, np_, nq, na, ks, ann, c, out.data_ptr(), _stream()),
               'se3_vgtk_inter_zpconv_fwd')
@@ -130,6 +137,8 @@ class InterZPConvGrouping(torch.autograd.Function):
         g = _req(grad_out.contiguous(), torch.float32, 'grad_out', 5)
         b, np_, na, ks, ann = idx.shape
         c = g.shape[1]
+        if tuple(g.shape) != (b, c, ks, np_, na):
+            raise RuntimeError('InterZPConvGrouping.backward: grad_out %s is not (b, c, ks, np, na) of inter_idx %s' % (tuple(g.shape), tuple(idx.shape)))
         grad = torch.empty((b, c, ctx.nq, na), dtype=torch.float32, device=g.device)
         nbytes = lib().se3_vgtk_inter_zpconv_bwd_workspace_bytes(b, np_, ctx.nq, na, ks, ann)
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
@@ -152,6 +161,8 @@ class IntraZPConvGrouping(torch.autograd.Function):
         na_out, ann = idx.shape
         ks = w.shape[1]
         b, c, np_, na_in = f.shape
+        if tuple(w.shape) != (na_out, ks, ann):
+            raise RuntimeError('intra_zpconv_grouping: intra_w %s is not (na_out, ks, ann) of intra_idx %s' % (tuple(w.shape), tuple(idx.shape)))
         out = torch.empty((b, c, ks, np_, na_out), dtype=torch.float32, device=f.device)
         check(lib().se3_vgtk_intra_zpconv_fwd(idx.data_ptr(), w.data_ptr(), f.data_ptr(), b, np_, na_in, na_out, ks, ann, c, out.data_ptr(), _stream()),
               'se3_vgtk_intra_zpconv_fwd')
@@ -165,6 +176,8 @@ class IntraZPConvGrouping(torch.autograd.Function):
         g = _req(grad_out.contiguous(), torch.float32, 'grad_out', 5)
         na_out, ann = idx.shape
         b, c, ks, np_, _ = g.shape
+        if g.shape[4] != na_out or tuple(w.shape) != (na_out, ks, ann):
+            raise RuntimeError('IntraZPConvGrouping.backward: grad_out %s is not (b, c, ks, np, na_out) of intra_w %s' % (tuple(g.shape), tuple(w.shape)))
         grad = torch.empty((b, c, np_, ctx.na_in), dtype=torch.float32, device=g.device)
         check(lib().se3_vgtk_intra_zpconv_bwd(idx.data_ptr(), w.data_ptr(), g.data_ptr(), b, np_, ctx.na_in, na_out, ks, ann, c, grad.data_ptr(),
                                               _stream()), 'se3_vgtk_intra_zpconv_bwd')

@@ -96,12 +96,17 @@ def test_furthest_point_sampling_matches_source_restatement(n, m):
 
 
 def test_furthest_point_sampling_tie_order():
-    """Exact distance ties (points on an integer lattice) resolve as in the reference's block reduction."""
+    """Exact distance ties (points on an integer lattice) resolve as in the reference's block reduction: the literal reduction tree of
+    tests/vgtk_twin.py (among tied threads the smallest bit-reversed thread number wins), and the oracle's selection key, which states the
+    same order.  Until the tree was written down, kernel and oracle shared the key `k mod bs ascending`, which is not the tree's order:
+    36 of the 40 expected indices of this test changed with it (from sample 2 on)."""
+    import vgtk_twin
     from oracle import vgtk_oracle as VO
     from se3et_amd import vgtk
     ax = np.arange(6, dtype=np.float32) + 1.0
     pc = np.stack(np.meshgrid(ax, ax, ax, indexing='ij'), 0).reshape(1, 3, -1)          # 216 lattice points
     got = vgtk.furthest_sample_index(torch.from_numpy(pc).cuda(), 40).cpu().numpy()
+    assert np.array_equal(got, vgtk_twin.furthest_point_sampling(pc, 40))
     assert np.array_equal(got, VO.furthest_point_sampling(pc, 40))
 
 
